@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- decode throughput of the W4A8KV4 hot path on MI355X (contract: see the task statement).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {2,3,4,5}]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {2,3,4,5}] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -15,7 +15,12 @@ global batch).  `python bench.py --gpus N` without a launcher re-executes itself
 `--config` selects the other BASELINE.json configurations (3: g128 bs=128; 4: Qwen1.5-72B TP=8 global bs=64, strong;
 5: KV8, 8k context, bs=8); they are parity-test cases first and bench lines only on request.
 
-Prints ONE JSON line on rank 0 with the contract's keys plus
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0 with the contract's keys
+(`ms_per_step` = milliseconds of one timed step).  W + K may exceed one generation (max_new - 1 decode steps): the
+generation then starts over at its first decode position each time its page budget is used up.  `--dump-outputs DIR` writes what the last timed step returned to its
+caller (next_tokens.npy: the greedy tokens, float64 [batch]; final_hidden.npy: the normed hidden state the lm_head
+consumed, float32 [batch, hidden]) - same arguments, same inputs, so two builds compare output for output.
+`--full` adds everything else the benchmark measures:
   roofline         the single kernel with the largest per-step time, timed live with HIP events on the launch stream
   roofline_family  the W4A8 GEMM family (all four decode GEMMs of a layer): family bytes / family time
   cpu_baseline     the PyTorch-CPU dequant + matmul / attention path (oracle/torch_cpu.py) on this box's host cores
@@ -60,6 +65,12 @@ def parse():
     ap.add_argument("--kv8", action="store_true", default=None)
     ap.add_argument("--model", default=None, choices=["llama3-8b", "llama2-7b", "llama2-70b", "qwen1.5-72b", "tiny"])
     ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: per-kernel timings and rooflines, the CPU baseline, "
+                         "context sweep, eager / op-by-op rates, prompt phase and end-to-end protocol, other configurations, "
+                         "collective cost (N > 1); the --no-* switches below trim a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-bench", action="store_true")
     ap.add_argument("--no-prefill", action="store_true", help="skip the prompt phase / end-to-end protocol measurement")
@@ -91,6 +102,8 @@ def parse():
     if a.gpus is None:
         a.gpus = 1
     a.kv8 = bool(a.kv8)
+    if not a.full:
+        a.no_cpu_baseline = a.no_kernel_bench = a.no_prefill = a.no_extras = True
     return a
 
 
@@ -266,6 +279,15 @@ def time_steps(eng, n, torch):
         eng.run()
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) / n * 1e3
+
+
+def dump_outputs(eng, out_dir):
+    """What the last timed step handed to its caller: the greedy next tokens (int64 -> float64, exact) and the final
+    normed hidden state the lm_head read (fp16 -> float32, exact)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "next_tokens.npy"), eng.tokens.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(out_dir, "final_hidden.npy"), eng.final.float().cpu().numpy())
 
 
 def kernel_bench(eng, args, torch, contexts):
@@ -590,18 +612,32 @@ def main():
                   file=sys.stderr)
             os._exit(3)
     eng.lengths.fill_(start_len)
-    assert args.warmup + args.steps + 1 <= args.max_new, "steps exceed the page budget (prompt_len + max_new)"
+    # the pages hold one generation (prompt_len + max_new positions): max_new - 1 decode steps from start_len.  A run with
+    # more warm-up + timed steps than that starts the generation over at its first decode position whenever the budget is
+    # used up (one fill of `lengths` on the step's stream; the cache positions are rewritten in place, as a new generation
+    # of the same batch would).  Runs that fit take exactly the steps they always took.
+    budget = args.max_new - 1
+    assert budget >= 1, "--max-new must be at least 2"
+    taken = [0]                         # decode steps since the generation (re)started
+
+    def decode_steps(n):
+        for _ in range(n):
+            if taken[0] == budget:
+                eng.lengths.fill_(start_len)
+                taken[0] = 0
+            eng.run()
+            taken[0] += 1
+    ctx0 = start_len + args.warmup % budget             # context of the first timed step
+    wraps = args.warmup + args.steps > budget
 
     # ---- the contract's timed region: W warm-up steps, then exactly K steps between barriers + synchronize ----------
-    for _ in range(args.warmup):
-        eng.run()
+    decode_steps(args.warmup)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        eng.run()
+    decode_steps(args.steps)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -614,6 +650,8 @@ def main():
     ms = dt / args.steps * 1e3
     extra = {}
     eng.check()                         # bounded in-launch waits (direct all-reduce): raise if one gave up
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, args.dump_outputs)
 
     # ---- per-kernel timing (feeds the roofline objects below): taken HERE, straight after the timed steps and in the same
     # thermal / clock state - not behind the prompt phase, the end-to-end protocol and the reference-engine child process,
@@ -621,7 +659,7 @@ def main():
     kernels = None
     if not args.no_kernel_bench:
         try:
-            ctxs = [start_len + args.warmup]
+            ctxs = [ctx0]
             if world == 1 and not args.no_extras:
                 ctxs += [args.prompt_len + args.max_new // 2, args.prompt_len + args.max_new - 1]
             kernels = kernel_bench(eng, args, torch, ctxs)      # every rank times its own shard's kernels; rank 0 reports
@@ -642,7 +680,7 @@ def main():
             eng.lengths.fill_(L)
             eng.run()
             sweep[L + 1] = round(args.batch / (time_steps(eng, n2, torch) / 1e3), 1)
-        extra["decode_tokens_per_s_by_context"] = {str(start_len + args.warmup): round(args.batch / (ms / 1e3), 1),
+        extra["decode_tokens_per_s_by_context"] = {str(ctx0): round(args.batch / (ms / 1e3), 1),
                                                   **{str(k): v for k, v in sweep.items()}}
         extra["decode_tokens_per_s_mid"] = sweep[mid_len + 1]
         if graphed:
@@ -713,7 +751,7 @@ def main():
                                   f"flash attention) + {args.max_new - 1} decode steps; tokens = batch x {args.max_new}")
         except RuntimeError as e:                      # e.g. out of memory for the [tokens, 2*inter] buffer
             print(f"[bench] end-to-end protocol skipped: {e}", file=sys.stderr)
-        eng.lengths.fill_(start_len + args.warmup)
+        eng.lengths.fill_(ctx0)
 
     # ---- the reference's OWN engine running its own benchmark protocol over this backend (when its tree is staged under the
     # git-ignored oracle/_ref/, scripts/stage_reference.sh): qserve_benchmark.py:process_requests, LLMEngine, scheduler, block
@@ -736,7 +774,7 @@ def main():
             print(f"[bench] reference engine leg skipped: {type(e).__name__}: {str(e)[:200]}", file=sys.stderr)
 
     # ---- collective cost (N > 1): one fp16 all-reduce of the row-parallel partial [batch, hidden] ---------------------
-    if world > 1:
+    if world > 1 and args.full:
         buf = torch.zeros_like(eng.proj_out)
         for _ in range(5):
             dist.all_reduce(buf)
@@ -760,6 +798,7 @@ def main():
             torch.cuda.synchronize()
             extra.update(direct_all_reduce_us=round(e0.elapsed_time(e1) * 1e3 / 50, 2),
                          direct_all_reduce_timeouts=bool(direct.error()))
+    if world > 1:
         extra.update(step_collectives=collective_note or "torch.distributed all-reduce (--collective rccl)",
                      all_reduces_per_step=2 * cfg["layers"] + int(eng.vocab_parallel),
                      lm_head=("vocabulary-parallel: every rank multiplies its V/N rows, the ranks' greedy candidates meet in "
@@ -857,7 +896,7 @@ def main():
                                    f"{f' ({per_gpu_batch} per GPU x tp{world})' if world > 1 and args.scaling == 'weak' else ''}"
                                    f", context {args.prompt_len}->+{args.max_new}"
                                    f"{f' (BASELINE.json configs[{cfg_idx - 1}])' if cfg_idx else ''}",
-                       "global_batch": args.batch, "context_start": start_len + args.warmup,
+                       "global_batch": args.batch, "context_start": ctx0,
                        "parallelism": f"tp{world}",
                        "hipgraph": ("piecewise (collectives issued eagerly between the pieces)"
                                     if graphed and world > 1 and not full_graph and direct is None else graphed),
@@ -869,8 +908,11 @@ def main():
                                                           "norm + quant launch behind it finishes the GEMM" for n, p in eng.planes.items())
                          if getattr(eng, "planes", None) else "")),
                        "launches_per_layer": 8 if not args.op_by_op else 12,
-                       "value_context": f"decode steps at context {start_len + args.warmup}..{start_len + args.warmup + args.steps - 1} "
-                                        "(start of the 1024 -> +512 generation); mid / end of generation: "
+                       "value_context": (f"decode steps at context {ctx0}..{ctx0 + args.steps - 1} (start of the "
+                                         f"{args.prompt_len} -> +{args.max_new} generation)" if not wraps else
+                                         f"decode steps from context {ctx0} through the {args.prompt_len} -> +{args.max_new} "
+                                         f"generation, restarted at context {start_len} every {budget} steps (the page "
+                                         "budget of one generation)") + "; mid / end of generation: "
                                         "decode_tokens_per_s_by_context, whole generation: e2e_decode_only_tokens_per_s",
                        **extra},
             "roofline": roof,

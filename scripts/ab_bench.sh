@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 VARS=${1:-"-1"}
 shift
 for v in $VARS; do
-  timeout 300 python bench.py --steps 64 --no-cpu-baseline --no-prefill --gemm-variant $v "$@" 2>/dev/null > /tmp/ab_$$.json
+  timeout 300 python bench.py --steps 64 --full --no-cpu-baseline --no-prefill --gemm-variant $v "$@" 2>/dev/null > /tmp/ab_$$.json
   python - "$v" /tmp/ab_$$.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[2]))

@@ -4,7 +4,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 ROOT=$(pwd)
 TAG=${1:-prefill}
 export TMPDIR=/tmp
-( cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$TAG -o trace -- python $ROOT/bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-extras --no-kernel-bench > /tmp/prof_$TAG.log 2>&1 )
+( cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$TAG -o trace -- python $ROOT/bench.py --steps 4 --warmup 2 --full --no-cpu-baseline --no-extras --no-kernel-bench > /tmp/prof_$TAG.log 2>&1 )
 tail -2 /tmp/prof_$TAG.log | cut -c1-300
 for f in $(find /tmp/prof_$TAG -name "*kernel_stats*.csv" | head -1); do cp "$f" gpurun_out/${TAG}_kernel_stats.csv; done
 python - <<PY

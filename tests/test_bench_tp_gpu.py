@@ -16,7 +16,7 @@ def _run(extra, port):
     env = dict(os.environ, QS_DIST_BACKEND="gloo", QS_DIST_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--model", "tiny",
-           "--batch", "4", "--prompt-len", "96", "--max-new", "48", "--steps", "4", "--warmup", "2", "--no-prefill"] + extra
+           "--batch", "4", "--prompt-len", "96", "--max-new", "48", "--steps", "4", "--warmup", "2", "--full", "--no-prefill"] + extra
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
