@@ -215,10 +215,11 @@ int qs_get_row_sum_order(void);
  * load.  buf = device memory of 16 * workgroups bytes owned by the caller; (NULL, 0) stops it.  Results are unaffected. */
 int qs_debug_gemm_clock_probe(void* buf, int workgroups);
 
-/* Plan only: runs the W4A8 GEMM dispatcher for an (M, N, K) problem without touching the device and reports its choice
- * in plan5 = {family, p0, p1, p2, p3}: family 1 = split-K kernel (m_tiles, waves, cross-block slices, xcd mapping),
- * 2 = LDS-pair kernel, 3 = ring kernel (m_tiles, units, token blocks, K slices), 4 = tiled kernel (8 = 256-token tile,
- * 4 = 128-token tile).  No reference counterpart: it makes the selection heuristics testable on a CPU-only machine
+/* Plan only: the W4A8 GEMM dispatcher's kernel choice for an (M, N, K) problem - the same planning function the launches
+ * use, without touching the device - in plan5 = {family, p0, p1, p2, p3}: family 1 = split-K kernel (m_tiles, waves,
+ * cross-block slices, xcd mapping), 2 = LDS-pair kernel, 3 = ring kernel (m_tiles, units, token blocks, K slices; K slices
+ * assume the split-K workspace, without which a launch runs un-split), 4 = tiled kernel (8 = 256-token tile, 4 = 128-token
+ * tile), 5 = four-wave tiled kernel (8); all zero for M = 0.  No reference counterpart: it makes the selection heuristics testable on a CPU-only machine
  * (tests/test_dispatch_plan.py).  per_group: 0 = per-channel, 1 = per-group-128.  Honours qs_set_gemm_variant. */
 int qs_w4a8_gemm_plan(int per_group, int M, int N, int K, int* plan5);
 
@@ -272,10 +273,11 @@ int qs_single_query_attention_quant(const void* q, const void* k, const void* v,
  * (200 + bits: ablation / trace instantiations of the KV4 kernel, QS_TIMING builds only; ignored by the shipped library.) */
 void qs_set_attention_variant(int variant);
 
-/* Plan only (no device access, CPU-testable like qs_w4a8_gemm_plan): which decode attention kernel the dispatcher
- * takes for (batch, heads, kv heads, page-table width, longest context) and how it splits the context:
+/* Plan only (no device access, CPU-testable like qs_w4a8_gemm_plan): which decode attention kernel the dispatcher's planning
+ * function takes for (batch, heads, kv heads, page-table width, longest context) and how it splits the context:
  * plan3 = {family, kv_splits, waves per workgroup}; family 1 = matrix-core KV4 kernel, 2 = matrix-core KV8 kernel,
- * 3 = VALU kernel (page tables wider than 192 entries, or forced by qs_set_attention_variant(1)). */
+ * 3 = VALU kernel (page tables wider than 192 entries, or forced by qs_set_attention_variant(1)).  kv_splits is the plan;
+ * a launch runs fewer where the split workspace cannot hold them.  All zero for batch = 0. */
 int qs_attention_plan(int batch, int num_heads, int num_kv_heads, int max_blocks, int timestep, int int4_kv_cache,
                       int* plan3);
 

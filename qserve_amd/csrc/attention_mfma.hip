@@ -44,7 +44,7 @@ constexpr int DH = 128;
 constexpr int DHB = 64;        // KV4 bytes per token per head
 constexpr int UT = 32;         // tokens per pipeline unit (half a page)
 constexpr int USB = UT * DHB;  // bytes of K (or V) data per unit and KV head
-constexpr int NW = 8;          // waves per workgroup; all of them may own units
+constexpr int NW = QS_ATTN_WAVES_KV4;   // waves per workgroup; all of them may own units
 constexpr int NWT = NW;
 typedef u32 v2u __attribute__((ext_vector_type(2)));
 constexpr int QS_ATTNQ_CAP = 4096;   // sequences the attention + quant fusion can hand over (larger batches run the pair)
@@ -1108,36 +1108,6 @@ float* qs_split_workspace(size_t bytes, hipStream_t st) {
 }
 size_t qs_split_workspace_capacity() { return SPLIT_WS_BYTES; }
 
-// Split-KV factor of the matrix-core decode kernels (KV4: this file, KV8: attention_mfma8.hip): the number of workgroups a
-// (sequence, KV head) pair's page range is cut into.  Cost model fitted to a sweep on the MI355X (profiles/round5_split_sweep*.txt:
-// 1 .. 48 sequences x 8 KV heads, 1 030 .. 7 700 tokens, 1 .. 32 splits; mean regret 0.7 %, worst 10 %, against the forced best;
-// the round-2 rule "aim at >= 512 workgroups" it replaces: 8 % / 39 %):
-//   time(n) = rounds * F + max(rounds * pages / n * t_cu,  blocks * pages * t_hbm) + merge(n)
-// rounds = ceil(blocks * n / 256): workgroups land on the 256 CUs round-robin and a CU streams at its own request budget whatever
-// the number of resident workgroups, so 320 workgroups take as long as 512; F = a workgroup's head + tail; t_cu = one CU's time
-// per page (64 tokens of K and V), t_hbm = the chip's; merge = the second launch (boundary + n partials per head).
-// ns / ps units, integer arithmetic (the plan is part of the ABI: tests/test_dispatch_plan.py pins it).
-int qs_attn_choose_splits(int blocks, int pages, int kv8, int fused_quant) {
-    if (blocks >= 512 || pages < 4) return 1;
-    const long F = kv8 ? 5000 : 4000, t_cu = kv8 ? 450 : 340, t_hbm_ps = kv8 ? 2540 : 1330;
-    long best = -1;
-    int best_n = 1;
-    // (n <= 8: within this kernel's range - page tables of <= 192 entries, 12 288 tokens; longer tables go to the VALU kernels -
-    //  more splits do not pay: 1 / 2 / 4 sequences at 8 191 and 12 200 tokens, forced 4 / 8 / 12 / 16 / 24 splits against this
-    //  choice, KV4 and KV8: the choice is the best or within 1 % of it everywhere except one sequence of 12 200 tokens over an INT8
-    //  cache, where 12 splits measure 20.4 against 21.7 us - profiles/round6_split_long.txt.  ADVICE r05 extrapolated the cost
-    //  formula to 512 pages, which this function is never asked about.)
-    for (int n = 1; n <= 8; ++n) {
-        if (n > 1 && pages / n < 2) break;
-        const long rounds = ((long)blocks * n + 255) / 256;
-        const long per_cu = rounds * pages * t_cu / n, chip = (long)blocks * pages * t_hbm_ps / 1000;
-        // (fused_quant: qs_single_query_attention_quant - only the un-split launch can finish the row itself; a split one is
-        // followed by the quantiser as a launch of its own, 3.2 us + boundary)
-        const long cost = rounds * F + (per_cu > chip ? per_cu : chip) + (n > 1 ? 2500 + 300 * n + (fused_quant ? 3500 : 0) : 0);
-        if (best < 0 || cost < best) best = cost, best_n = n;
-    }
-    return best_n;
-}
 // timing tool (scripts/trace_attn.py): copy the first `bytes` of the split workspace (the EXP & 32 timeline stamps) to dst
 extern "C" int qs_debug_copy_split_workspace(void* dst, size_t bytes) {
     int dev = 0;
@@ -1200,29 +1170,15 @@ int qs_attn_reset_handoff() {
     return QS_OK;
 }
 
-// called from attention.hip's dispatcher for KV4.  force_split: 0 = heuristic, n > 0 = exactly n splits (tests)
+// called from attention.hip's dispatcher for KV4 with its plan (nsplit, kflags, exp_flags); quant (nullable): the request of
+// qs_single_query_attention_quant, *fused = whether this launch finished the quantised row too
 int qs_launch_decode_mfma(int G, dim3 grid, hipStream_t st, const _Float16* q, const _Float16* k, const _Float16* v,
                           const int64_t* kvp, const int* len, _Float16* out, int H, int Hkv, int64_t qs, int64_t kvs,
-                          int mb, int timestep, float base, int max_pos, int force_split, int kflags) {
-    if (G < 1 || G > 8) {
-        qs_set_error("single_query_attention: num_heads/num_kv_heads = %d not in 1..8", G);
-        return QS_ENOSUP;
-    }
-    int exp_flags = 0;                      // qs_set_attention_variant(200 + EXP): ablation builds of the G = 4 kernel
-    if (force_split >= 100) {
-        exp_flags = force_split - 100;
-        force_split = 0;
-    }
+                          int mb, int timestep, float base, int max_pos, int nsplit, int kflags, int exp_flags,
+                          const QsAttnQuant* quant, bool* fused) {
     int tab_len = 0;
-    const float2* tab = g_qs_attn_plan.active ? nullptr : qs_rope_table(base, max_pos, st, &tab_len);
-    // split-KV (qs_attn_choose_splits above)
+    const float2* tab = qs_rope_table(base, max_pos, st, &tab_len);
     const int blocks = (int)(grid.x * grid.y);
-    const int pages_max = (timestep + PAGE_TOK - 1) / PAGE_TOK;
-    int nsplit = force_split > 0 ? force_split : qs_attn_choose_splits(blocks, pages_max, 0, g_qs_attn_quant.qout != nullptr && H * DH <= 4096);
-    if (g_qs_attn_plan.active) {
-        g_qs_attn_plan.family = 1, g_qs_attn_plan.nsplit = nsplit, g_qs_attn_plan.waves = NW;
-        return QS_OK;
-    }
     float* ws = nullptr;
     if (nsplit > 1) {
         const size_t per_split = (size_t)blocks * G * (DH + 2) * sizeof(float);
@@ -1238,12 +1194,12 @@ int qs_launch_decode_mfma(int G, dim3 grid, hipStream_t st, const _Float16* q, c
     unsigned* qcnt = nullptr;
     // (qs_set_row_sum_order(1) with a row sum asked for: the finisher reproduces THIS library's order of invoke_quant_fuse_sum, not the
     //  reference's - the pair is issued instead, so that the fused entry stays bit-identical to the two calls in both modes)
-    const bool sum_order_ok = !(qs_get_row_sum_order() && g_qs_attn_quant.qsum);
-    if (g_qs_attn_quant.qout && sum_order_ok && nsplit == 1 && H * DH <= 4096 && (qcnt = qs_attn_quant_counters(st, (int)grid.y))) {
-        qout = g_qs_attn_quant.qout;
-        qscale = reinterpret_cast<__half*>(g_qs_attn_quant.qscale);
-        qsum = reinterpret_cast<__half*>(g_qs_attn_quant.qsum);
-        g_qs_attn_quant.done = 1;
+    const bool sum_order_ok = !(quant && qs_get_row_sum_order() && quant->qsum);
+    if (quant && sum_order_ok && nsplit == 1 && H * DH <= 4096 && (qcnt = qs_attn_quant_counters(st, (int)grid.y))) {
+        qout = quant->qout;
+        qscale = reinterpret_cast<__half*>(quant->qscale);
+        qsum = reinterpret_cast<__half*>(quant->qsum);
+        *fused = true;
         if (g_inject_fault & 2) kflags |= 64, g_inject_fault &= ~2;   // one-shot (qs_debug_inject_fault)
     }
 #define QS_LAUNCH_G(GG)                                                                                             \

@@ -20,7 +20,7 @@ namespace {
 constexpr int PAGE_TOK = 64;
 constexpr int DH = 128;
 constexpr int DHB = 128;       // KV8 bytes per token per head
-constexpr int NW = 4;          // waves per workgroup
+constexpr int NW = QS_ATTN_WAVES_KV8;   // waves per workgroup
 constexpr int MAXP = 192;      // page-table entries cached in LDS per sequence (dispatcher: max_blocks <= MAXP)
 constexpr int NVM = 9;         // VMEM instructions of one page-slice fetch (8 x 1 KiB + scales|zeros)
 
@@ -487,26 +487,15 @@ __global__ __launch_bounds__(NW * 64, 2) void decode_attention_mfma8_kernel(
 const float2* qs_rope_table(float base, int max_pos, hipStream_t st, int* len_out);
 float* qs_split_workspace(size_t bytes, hipStream_t st);
 size_t qs_split_workspace_capacity();
-int qs_attn_choose_splits(int blocks, int pages, int kv8, int fused_quant);
 void qs_launch_attention_merge(const float* ws, _Float16* out, int H, int Hkv, int G, int nsplit, int batch, hipStream_t st);
 
-// called from attention.hip's dispatcher for KV8.  force_split: 0 = heuristic, n > 0 = exactly n splits (tests)
+// called from attention.hip's dispatcher for KV8 with its plan (nsplit: fewer where the split workspace cannot hold them)
 int qs_launch_decode_mfma8(int G, dim3 grid, hipStream_t st, const _Float16* q, const _Float16* k, const _Float16* v,
                            const int64_t* kvp, const int* len, _Float16* out, int H, int Hkv, int64_t qs, int64_t kvs,
-                           int mb, int timestep, float base, int max_pos, int force_split) {
-    if (G < 1 || G > 8) {
-        qs_set_error("single_query_attention: num_heads/num_kv_heads = %d not in 1..8", G);
-        return QS_ENOSUP;
-    }
+                           int mb, int timestep, float base, int max_pos, int nsplit) {
     int tab_len = 0;
-    const float2* tab = g_qs_attn_plan.active ? nullptr : qs_rope_table(base, max_pos, st, &tab_len);
+    const float2* tab = qs_rope_table(base, max_pos, st, &tab_len);
     const int blocks = (int)(grid.x * grid.y);
-    const int pages_max = (timestep + PAGE_TOK - 1) / PAGE_TOK;
-    int nsplit = force_split > 0 ? force_split : qs_attn_choose_splits(blocks, pages_max, 1, 0);   // attention_mfma.hip
-    if (g_qs_attn_plan.active) {
-        g_qs_attn_plan.family = 2, g_qs_attn_plan.nsplit = nsplit, g_qs_attn_plan.waves = NW;
-        return QS_OK;
-    }
     float* ws = nullptr;
     if (nsplit > 1) {
         const size_t per_split = (size_t)blocks * G * (DH + 2) * sizeof(float);

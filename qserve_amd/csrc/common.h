@@ -190,9 +190,6 @@ __device__ __forceinline__ float wave_sum_dpp(float v) {
     return wave_allreduce_dpp(v, [](float a, float b) { return a + b; });
 }
 
-// cvt.rni.sat.{s8,u8}.f32 equivalents: round-to-nearest-even then saturate (NaN -> 0)
-// Plan-only mode of the GEMM dispatcher (qs_w4a8_gemm_plan): the launchers record which kernel family / geometry they
-// were asked for and return without touching the device - the selection heuristics become testable on a CPU-only box.
 // K-sliced ring GEMM: the word a slab holds where no partial sum has been delivered (gemm_w4a8_ring.hip, the seam); the workspace
 // is filled with it byte-wise (0x80), and no partial sum of a slice of at most 32 768 k can reach it (128 * 255 * 32768 < 2^30)
 constexpr int QS_SLAB_SENTINEL = (int)0x80808080u;
@@ -220,28 +217,16 @@ unsigned* qs_attn_error_word(int slot);       // attention_mfma.hip: nullptr unt
 int qs_gemm_reset_handoff();                  // gemm_w4a8.hip: sentinel-fill the K-slice slabs, clear the error word
 int qs_attn_reset_handoff();                  // attention_mfma.hip: zero generation words / exchange rows, clear the error word
 
-struct QsGemmPlan {
-    int active;   // 1 while qs_w4a8_gemm_plan runs the dispatcher
-    int family;   // 1 split-K, 2 LDS-pair, 3 ring, 4 tiled
-    int p[4];     // ring: m_tiles, units, token blocks, K slices; tiled: m-tiles per wave (8 = 256-token tile, 4 = 128);
-                  // split-K: m_tiles, waves, cross-block slices, xcd mapping
-};
-extern thread_local QsGemmPlan g_qs_plan;
-// the same for the decode attention dispatcher (qs_attention_plan): family 1 = matrix-core KV4, 2 = matrix-core KV8,
-// 3 = VALU kernel; nsplit = KV splits (workgroups per sequence and KV head), waves = waves per workgroup
-struct QsAttnPlan {
-    int active, family, nsplit, waves;
-};
-extern thread_local QsAttnPlan g_qs_attn_plan;
-// request of qs_single_query_attention_quant to the attention launchers: fuse invoke_quant(_fuse_sum) of the output
-// into the kernel when the chosen kernel can (sets `done`); otherwise the entry point runs the row kernel itself
+// waves per workgroup of the matrix-core decode attention kernels (attention_mfma.hip, attention_mfma8.hip; qs_attention_plan)
+constexpr int QS_ATTN_WAVES_KV4 = 8;
+constexpr int QS_ATTN_WAVES_KV8 = 4;
+// request of qs_single_query_attention_quant to the KV4 launcher: fuse invoke_quant(_fuse_sum) of the output into the
+// kernel when it can (the launcher reports whether it did); otherwise the entry point runs the row kernel itself
 struct QsAttnQuant {
     int8_t* qout;
     void* qscale;
     void* qsum;     // may be null (invoke_quant without the row sum)
-    int done;
 };
-extern thread_local QsAttnQuant g_qs_attn_quant;
 
 // butterfly exchange with an explicitly supplied lane id: __shfl_xor derives its own (loop-invariant) lane id, which the
 // register allocator then keeps alive - or spills - across a long loop
@@ -254,6 +239,7 @@ __device__ __forceinline__ unsigned fresh_lane_id() {   // opaque to CSE: not sh
     return lid;
 }
 
+// cvt.rni.sat.{s8,u8}.f32 equivalents: round-to-nearest-even then saturate (NaN -> 0)
 __device__ __forceinline__ int rni_sat_s8(float x) {
     float r = rintf(x);
     r = fminf(fmaxf(r, -128.f), 127.f);   // fmaxf/fminf drop NaN -> -128 ; handle below

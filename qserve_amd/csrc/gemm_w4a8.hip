@@ -265,9 +265,6 @@ __global__ __launch_bounds__(MT <= 2 ? 512 : 256, 2) void w4a8_gemm_splitk(const
 }
 
 qs_flag g_variant = QS_GEMM_DEFAULT;   // process-global test / measurement hook (include/qserve_amd.h qs_gemm_variant_code): not thread-safe
-}  // namespace
-thread_local QsGemmPlan g_qs_plan = {0, 0, {0, 0, 0, 0}};
-namespace {
 
 // Split-K workspace (per device): int32 slabs + arrival counters, allocated lazily on first use (never while a
 // stream is being captured: a failed allocation simply disables cross-block split-K).
@@ -340,11 +337,6 @@ template <int MT, int MODE, int OUTK, int NSTAGE>
 int launch_splitk(const int8_t* A, const uint8_t* W, const int8_t* zeros, const int8_t* scales8, const void* wscales,
                   const void* ascales, const void* wszs, const void* assums, void* out, int M, int N, int K, int NW,
                   int S, bool xcd_map, hipStream_t stream) {
-    if (g_qs_plan.active) {
-        g_qs_plan.family = 1;
-        g_qs_plan.p[0] = MT, g_qs_plan.p[1] = NW, g_qs_plan.p[2] = S, g_qs_plan.p[3] = xcd_map ? 1 : 0;
-        return QS_OK;
-    }
     auto kern = w4a8_gemm_splitk<MT, MODE, OUTK, NSTAGE>;
     size_t smem = NW > 1 ? (size_t)NW * MT * 16 * 64 * sizeof(int) : 16;
     static size_t configured_dev[QS_MAX_DEVICES] = {};   // per instantiation and device
@@ -407,23 +399,27 @@ namespace {
 
 constexpr int QS_UNFUSED = 1 << 20;   // internal: the chosen kernel has no activation epilogue
 
-template <int MODE, int OUTK>
-int dispatch(const int8_t* A, const int8_t* W, const int8_t* zeros, const int8_t* scales8, const void* wscales,
-             const void* ascales, const void* wszs, const void* assums, void* out, int M, int N, int K,
-             qs_stream_t stream_, bool act = false) {
-    // act: `out` is [M, N/2] = silu(gate) * up of the stacked gate_up result (epilogue of the ring / tiled kernels,
-    // OUTK = 2 there); QS_UNFUSED when the shape is served by a kernel without that epilogue (the caller runs the two ops)
-    const int outk = act ? 2 : OUTK;
+// What the dispatcher launches for a problem: family (the plan5[0] codes of qs_w4a8_gemm_plan) and its geometry.
+enum { GEMM_INVALID = -1, GEMM_NONE = 0, GEMM_SPLITK = 1, GEMM_PAIR = 2, GEMM_RING = 3, GEMM_TILED = 4, GEMM_WIDE = 5 };
+struct GemmPlan {
+    int family;   // GEMM_NONE: `act` asked for, no kernel with the activation epilogue serves the shape (QS_UNFUSED);
+                  // GEMM_INVALID: a forced geometry that does not fit (qs_last_error says why)
+    int p[4];     // ring: mt, wn, mblocks, ksplit; tiled / wide: m-tiles per wave (8 = 256-token tile, 4 = 128);
+                  // split-K: MT, NW, S, xcd_map
+};
+
+int check_shape(int M, int N, int K) {
     QS_REQUIRE(M >= 0 && N > 0 && K > 0, "w4a8 gemm: bad shape M=%d N=%d K=%d", M, N, K);
     QS_REQUIRE(N % 64 == 0, "w4a8 gemm: N=%d must be a multiple of 64", N);
     QS_REQUIRE(K % 128 == 0, "w4a8 gemm: K=%d must be a multiple of 128", K);
-    if (M == 0) return QS_OK;   // empty batch: nothing to do (zero-size tensors carry null pointers)
-    QS_REQUIRE(A && W && out, "w4a8 gemm: null pointer");
-    if (OUTK == 0) QS_REQUIRE(wscales && ascales, "w4a8 gemm: null scale pointer");
-    if (MODE == 0 && OUTK == 0) QS_REQUIRE(wszs && assums, "w4a8 per-channel gemm: null w_szs / a_ssums");
-    if (MODE == 1) QS_REQUIRE(zeros && scales8, "w4a8 per-group gemm: null zeros / scales_i8");
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    const uint8_t* Wu = reinterpret_cast<const uint8_t*>(W);
+    return QS_OK;
+}
+
+// The kernel choice for a validated shape with M > 0, from the shape and the selection hook `variant` alone (no device access,
+// no global state: qs_w4a8_gemm_plan reports it, dispatch launches it; K slices assume the split-K workspace).  act: `out` is
+// [M, N/2] = silu(gate) * up of the stacked gate_up result (epilogue of the ring / tiled kernels) - GEMM_NONE when no kernel
+// with that epilogue serves the shape (the caller runs the two ops).
+GemmPlan plan_w4a8(int mode, bool act, int M, int N, int K, int variant) {
     const int nsteps = K / 128;
     // Heuristic (measured, scripts/bench_gemm*.py):
     //  * every 64-channel unit is one workgroup whose waves split K (exact int32 reduction in LDS);
@@ -436,63 +432,42 @@ int dispatch(const int8_t* A, const int8_t* W, const int8_t* zeros, const int8_t
     // tiles fill the chip; variant 3000 disables it, 3001 / 3002 force the 256- / 128-token tile
     if (N % 256 == 0 && K >= 256 && K < (1 << 24) && (size_t)M * K < (1ull << 32) && (size_t)N * K / 2 < (1ull << 32)) {
         int tmt = 0;
-        if (g_variant == QS_GEMM_TILED_256 || g_variant == QS_GEMM_WIDE_256) tmt = 8;
-        else if (g_variant == QS_GEMM_TILED_128) tmt = 4;
-        else if (g_variant < QS_GEMM_SPLITK_BASE || g_variant > QS_GEMM_WIDE_256) {
+        if (variant == QS_GEMM_TILED_256 || variant == QS_GEMM_WIDE_256) tmt = 8;
+        else if (variant == QS_GEMM_TILED_128) tmt = 4;
+        else if (variant < QS_GEMM_SPLITK_BASE || variant > QS_GEMM_WIDE_256) {
             const long nb = N / 256;
             // measured crossovers (scripts/bench_gemm_big.py, N=4096..28672): the tiles must (nearly) fill 256 CUs
             // (M >= 192: a 256-token tile must be mostly real tokens - without this bound every N >= 49 152 took the tiled
             // kernel even at M = 64 and ran at 2 TB/s)
             if (M >= 192 && ((M + 255) / 256) * nb >= 192) tmt = 8;
-            else if (M >= 256 && ((M + 127) / 128) * nb >= (MODE == 0 ? 96 : 192)) tmt = 4;
+            else if (M >= 256 && ((M + 127) / 128) * nb >= (mode == 0 ? 96 : 192)) tmt = 4;
         }
         // 256-token tiles, PER-GROUP: the four-wave kernel (gemm_w4a8_wide.hip; round 5) - one level-2 dequant per weight byte for
         // 256 tokens instead of two: +10 ... 18 % in-run (profiles/round5_wide_ab.txt: 4096^3 70.2 -> 64.0 us, 8192 x 4096 x 14336
         // 436 -> 369 us).  Per-channel the two tiles measure the same within +-3 % (both ~3.2 POPS marginal): the eight-wave one
         // stays.  Variant 3003 forces the four-wave tile for any problem, 3001 the eight-wave one (A/B, tests).
-        if (tmt == 8 && (g_variant == QS_GEMM_WIDE_256 || (MODE == 1 && g_variant != QS_GEMM_TILED_256)))
-            return qs_launch_gemm_wide(MODE, outk, A, Wu, zeros, scales8, wscales, ascales, wszs, assums, out, M, N, K,
-                                       g_tiled_order / 10, stream);
-        if (tmt)
-            return qs_launch_gemm_tiled(MODE, outk, A, Wu, zeros, scales8, wscales, ascales, wszs, assums, out, M, N, K,
-                                        tmt, stream);
+        if (tmt == 8 && (variant == QS_GEMM_WIDE_256 || (mode == 1 && variant != QS_GEMM_TILED_256))) return {GEMM_WIDE, {8}};
+        if (tmt) return {GEMM_TILED, {tmt}};
     }
     // decode shapes: LDS-DMA ring kernel with operands read one stage ahead (gemm_w4a8_ring.hip); variant 4000
     // disables it (A/B tests against the two older decode kernels below)
-    // K slices need the slab / counter workspace: tiles * ksplit * (mt KiB * 4) bytes, one counter per tile
-    auto ring_ws = [&](int mt, int mb, int ks, int** slabs, unsigned** counters) -> bool {
-        *slabs = nullptr;
-        *counters = nullptr;
-        if (ks <= 1) return true;
-        if (g_qs_plan.active) return true;      // plan-only: assume the workspace exists
-        Workspace* ws = get_workspace(stream);
-        const size_t tiles = (size_t)units * mb;
-        if (!ws || tiles >= (size_t)ws->ncounters || tiles * ks * mt * 4096 > ws->slab_bytes) return false;
-        *slabs = ws->ring_slabs;
-        *counters = ws->counters;
-        return true;
-    };
-    if (g_variant >= QS_GEMM_RING_GEOMETRY_BASE && g_variant < QS_GEMM_RING_GEOMETRY_END) {       // tests: forced geometry
-        const int v = g_variant - QS_GEMM_RING_GEOMETRY_BASE, ks = v / 100 + 1, mt = (v % 100) / 10, wn = v % 10;
-        const int mb = ((M + 15) / 16 + mt - 1) / mt;
-        if (act && ks > 1) return QS_UNFUSED;
-        QS_REQUIRE((mt == 1 || mt == 2 || mt == 4 || mt == 8) && (wn == 1 || wn == 2 || (wn == 4 && mt == 4)) &&
-                       !(mt == 1 && wn == 2) && !(mt == 8 && wn != 2) &&
-                       N % (64 * wn) == 0 && (K / 64) % ks == 0 && (K / 64 / ks) % (8 / wn) == 0 && (ks == 1 || K / ks <= 32768),
-                   "w4a8 gemm: forced ring geometry mt=%d wn=%d ksplit=%d does not fit M=%d N=%d K=%d", mt, wn, ks, M, N,
-                   K);
-        int* slabs = nullptr;
-        unsigned* counters = nullptr;
-        QS_REQUIRE(ring_ws(mt, mb, ks, &slabs, &counters), "w4a8 gemm: no split-K workspace for the forced geometry");
-        return qs_launch_gemm_ring(MODE, outk, mt, wn, A, Wu, zeros, scales8, wscales, ascales, wszs, assums, out, M, N,
-                                   K, mb, ks, slabs, counters, stream);
+    if (variant >= QS_GEMM_RING_GEOMETRY_BASE && variant < QS_GEMM_RING_GEOMETRY_END) {       // tests: forced geometry
+        const int v = variant - QS_GEMM_RING_GEOMETRY_BASE, ks = v / 100 + 1, mt = (v % 100) / 10, wn = v % 10;
+        if (act && ks > 1) return {GEMM_NONE};
+        if (!((mt == 1 || mt == 2 || mt == 4 || mt == 8) && (wn == 1 || wn == 2 || (wn == 4 && mt == 4)) &&
+              !(mt == 1 && wn == 2) && !(mt == 8 && wn != 2) &&
+              N % (64 * wn) == 0 && (K / 64) % ks == 0 && (K / 64 / ks) % (8 / wn) == 0 && (ks == 1 || K / ks <= 32768))) {
+            qs_set_error("w4a8 gemm: forced ring geometry mt=%d wn=%d ksplit=%d does not fit M=%d N=%d K=%d", mt, wn, ks, M, N, K);
+            return {GEMM_INVALID};
+        }
+        return {GEMM_RING, {mt, wn, ((M + 15) / 16 + mt - 1) / mt, ks}};
     }
     // Geometry choice (measured: scripts/bench_gemm.py for the Llama-3-8B shapes, scripts/bench_gemm_shard.py for the
     // tensor-parallel shard shapes): a workgroup of (16 mt tokens) x (64 wn channels) streams K (16 mt + 32 wn) bytes
     // through its CU, one workgroup per CU at a time, and the per-CU fill rate (~47 GB/s) is what bounds these shapes -
     // so take the geometry with the fewest bytes per CU over all its rounds; ties go to the two-unit workgroups (the
     // activation tile is shared by two waves).  Short K (< 1024) at M <= 64 stays on the split-K kernel (fixed costs).
-    if (M <= 1024 && !(K < 1024 && M <= 64) && g_variant != QS_GEMM_RING_OFF && (g_variant < QS_GEMM_SPLITK_BASE || g_variant >= QS_GEMM_RING_OFF) &&
+    if (M <= 1024 && !(K < 1024 && M <= 64) && variant != QS_GEMM_RING_OFF && (variant < QS_GEMM_SPLITK_BASE || variant >= QS_GEMM_RING_OFF) &&
         (size_t)M * K < (1ull << 32) && (size_t)N * K / 2 < (1ull << 32)) {
         const int mt_all = (M + 15) / 16;
         // <8,2> = 128-token workgroups (round 5): PER-GROUP only, un-split, from 65 tokens on - one level-2 dequant of a weight byte
@@ -514,10 +489,10 @@ int dispatch(const int8_t* A, const int8_t* W, const int8_t* zeros, const int8_t
         };
         long best = -1;
         int bmt = 0, bwn = 0, bks = 1;
-        for (int ks = 1; ks <= (g_variant == QS_GEMM_RING_NO_KSLICES || act ? 1 : 4); ks *= 2)
+        for (int ks = 1; ks <= (variant == QS_GEMM_RING_NO_KSLICES || act ? 1 : 4); ks *= 2)
             for (int i = 0; i < 7; ++i) {
                 const int mt = geo[i][0], wn = geo[i][1];
-                if (mt == 8 && (MODE != 1 || ks > 1 || mt_all <= 4 || mt_all > 8 || g_variant == QS_GEMM_RING_NO_MT8)) continue;   // (65 .. 128 tokens)
+                if (mt == 8 && (mode != 1 || ks > 1 || mt_all <= 4 || mt_all > 8 || variant == QS_GEMM_RING_NO_MT8)) continue;   // (65 .. 128 tokens)
                 if (N % (64 * wn) != 0 || (K / 64) % ks != 0 || (K / 64 / ks) % (8 / wn) != 0) continue;
                 if (ks > 1 && K / ks > 32768) continue;        // the seam's sentinel must stay out of reach of a partial sum
                 const int mb = (mt_all + mt - 1) / mt;
@@ -525,7 +500,7 @@ int dispatch(const int8_t* A, const int8_t* W, const int8_t* zeros, const int8_t
                 if (ks > 1 && (long)mb * (N / (64 * wn)) > 256) continue;   // K slices are for under-filled grids only
                 // per-group: the level-2 dequant is VALU work per weight byte a workgroup streams (measured at M = 128, g128:
                 // qkv 16.0 us with (4,1) against 18.2 with the equal-bytes (2,2)) - charged as a quarter of the weight bytes
-                const long pg = MODE == 1 && g_variant != QS_GEMM_RING_NO_GROUP_TERM ? 8 * wn : 0;
+                const long pg = mode == 1 && variant != QS_GEMM_RING_NO_GROUP_TERM ? 8 * wn : 0;
                 const long cost = ((blocks + 255) / 256) * (16 * mt + 32 * wn + pg) * (long)(K / ks) * (ks > 1 ? 11 : 10) / 10 +
                                   seam(ks, mt);
                 if (best < 0 || cost < best) best = cost, bmt = mt, bwn = wn, bks = ks;
@@ -538,7 +513,7 @@ int dispatch(const int8_t* A, const int8_t* W, const int8_t* zeros, const int8_t
         // model puts the two 1 KB apart and cannot be tuned to separate them without flipping M = 32 (measured the other way).
         // (Inside the decode step the two are equal, 2.809 vs 2.813 ms: kept for the traffic - one slab per tile instead of three.)
         if (best >= 0 && bmt == 2 && bwn == 2 && bks == 4 && (mt_all + 1) / 2 == 2 && (long)2 * (N / 64) * 2 == 256 &&
-            (K / 64) % 2 == 0 && (K / 64 / 2) % 8 == 0 && g_variant != QS_GEMM_RING_NO_DOWN_OVERRIDE)
+            (K / 64) % 2 == 0 && (K / 64 / 2) % 8 == 0 && variant != QS_GEMM_RING_NO_DOWN_OVERRIDE)
             bwn = 1, bks = 2;
         // the older register-staged split-K kernel takes any K and cuts the tokens down to 16 per workgroup: same byte
         // model, ~20 % slower at equal bytes (measured) - it wins where K leaves the ring kernel only coarse geometries
@@ -554,33 +529,13 @@ int dispatch(const int8_t* A, const int8_t* W, const int8_t* zeros, const int8_t
             const long cost_o = ((blocks_o + 255) / 256) * (16 * mto + 32) * (long)K * 12 / 10;
             if (cost_o < best) best = -1;
         }
-        if (best >= 0) {
-            int mb = (mt_all + bmt - 1) / bmt;
-            int* slabs = nullptr;
-            unsigned* counters = nullptr;
-            if (!ring_ws(bmt, mb, bks, &slabs, &counters)) {   // no workspace (e.g. first call inside a capture): best un-split
-                best = -1;
-                bks = 1;
-                for (int i = 0; i < 6; ++i) {
-                    const int mt = geo[i][0], wn = geo[i][1];
-                    if (N % (64 * wn) != 0 || (K / 64) % (8 / wn) != 0) continue;
-                    const long blocks = (long)((mt_all + mt - 1) / mt) * (N / (64 * wn));
-                    const long cost = ((blocks + 255) / 256) * (16 * mt + 32 * wn);
-                    if (best < 0 || cost < best) best = cost, bmt = mt, bwn = wn;
-                }
-                mb = (mt_all + bmt - 1) / bmt;
-            }
-            if (best >= 0)
-                return qs_launch_gemm_ring(MODE, outk, bmt, bwn, A, Wu, zeros, scales8, wscales, ascales, wszs, assums, out,
-                                           M, N, K, mb, bks, slabs, counters, stream);
-        }
+        if (best >= 0) return {GEMM_RING, {bmt, bwn, (mt_all + bmt - 1) / bmt, bks}};
     }
-    if (act) return QS_UNFUSED;
+    if (act) return {GEMM_NONE};
     // many channels: LDS-shared activation tiles + LDS-DMA rings (gemm_w4a8_lds.hip); variant 2000 forces the
     // split-K kernel, 2001 forces the LDS kernel (A/B tests)
-    if ((((units >= 256 && M > 16) || M >= 384) && g_variant != QS_GEMM_PAIR_OFF || g_variant == QS_GEMM_PAIR_FORCED) && N % 128 == 0 && K >= 256)
-        return qs_launch_gemm_pair(MODE, OUTK, A, Wu, zeros, scales8, wscales, ascales, wszs, assums, out, M, N, K,
-                                   stream);
+    if ((((units >= 256 && M > 16) || M >= 384) && variant != QS_GEMM_PAIR_OFF || variant == QS_GEMM_PAIR_FORCED) && N % 128 == 0 && K >= 256)
+        return {GEMM_PAIR};
     int mtile = M <= 16 ? 1 : M <= 32 ? 2 : M <= 48 ? 3 : 4;
     bool xcd_map = false;
     if (units < 256 && units % 8 == 0 && M > 16) {
@@ -596,8 +551,8 @@ int dispatch(const int8_t* A, const int8_t* W, const int8_t* zeros, const int8_t
     }
     int NW = nsteps >= 16 && mtile <= 2 ? 8 : nsteps >= 4 ? 4 : (nsteps >= 2 ? 2 : 1);
     int S = 1;
-    if (g_variant >= QS_GEMM_SPLITK_BASE && g_variant < QS_GEMM_PAIR_OFF) {   // A/B: QS_GEMM_SPLITK_BASE + 100*mtile_override + 10*S + NW
-        const int v = g_variant - QS_GEMM_SPLITK_BASE;
+    if (variant >= QS_GEMM_SPLITK_BASE && variant < QS_GEMM_PAIR_OFF) {   // A/B: QS_GEMM_SPLITK_BASE + 100*mtile_override + 10*S + NW
+        const int v = variant - QS_GEMM_SPLITK_BASE;
         NW = v % 10;
         S = (v / 10) % 10;
         const int mo = v / 100;
@@ -614,13 +569,80 @@ int dispatch(const int8_t* A, const int8_t* W, const int8_t* zeros, const int8_t
         if (NW == 3 || NW == 5 || NW == 6 || NW == 7) NW = 4;
     }
     if (NW > nsteps) NW = 1;
+    return {GEMM_SPLITK, {mtile, NW, S, xcd_map ? 1 : 0}};
+}
+
+// The best un-split ring geometry: what a K-sliced ring plan runs as when there is no workspace (e.g. first call inside a
+// capture).  Always found: the K-sliced plan's own <mt, wn> fits un-split.
+GemmPlan ring_unsplit(int M, int N, int K) {
+    static const int geo[6][2] = {{4, 2}, {2, 2}, {4, 1}, {2, 1}, {1, 1}, {4, 4}};
+    const int mt_all = (M + 15) / 16;
+    long best = -1;
+    int bmt = 0, bwn = 0;
+    for (int i = 0; i < 6; ++i) {
+        const int mt = geo[i][0], wn = geo[i][1];
+        if (N % (64 * wn) != 0 || (K / 64) % (8 / wn) != 0) continue;
+        const long blocks = (long)((mt_all + mt - 1) / mt) * (N / (64 * wn));
+        const long cost = ((blocks + 255) / 256) * (16 * mt + 32 * wn);
+        if (best < 0 || cost < best) best = cost, bmt = mt, bwn = wn;
+    }
+    return {GEMM_RING, {bmt, bwn, (mt_all + bmt - 1) / bmt, 1}};
+}
+
+template <int MODE, int OUTK>
+int dispatch(const int8_t* A, const int8_t* W, const int8_t* zeros, const int8_t* scales8, const void* wscales,
+             const void* ascales, const void* wszs, const void* assums, void* out, int M, int N, int K,
+             qs_stream_t stream_, bool act = false) {
+    const int outk = act ? 2 : OUTK;
+    if (int rc = check_shape(M, N, K)) return rc;
+    if (M == 0) return QS_OK;   // empty batch: nothing to do (zero-size tensors carry null pointers)
+    QS_REQUIRE(A && W && out, "w4a8 gemm: null pointer");
+    if (OUTK == 0) QS_REQUIRE(wscales && ascales, "w4a8 gemm: null scale pointer");
+    if (MODE == 0 && OUTK == 0) QS_REQUIRE(wszs && assums, "w4a8 per-channel gemm: null w_szs / a_ssums");
+    if (MODE == 1) QS_REQUIRE(zeros && scales8, "w4a8 per-group gemm: null zeros / scales_i8");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const uint8_t* Wu = reinterpret_cast<const uint8_t*>(W);
+    const int variant = g_variant;
+    GemmPlan plan = plan_w4a8(MODE, act, M, N, K, variant);
+    if (plan.family == GEMM_INVALID) return QS_EINVAL;
+    const int* p = plan.p;
+    int* slabs = nullptr;
+    unsigned* counters = nullptr;
+    if (plan.family == GEMM_RING && p[3] > 1) {   // K slices need the slab / counter workspace: tiles * ksplit * (mt KiB * 4) bytes, one counter per tile
+        Workspace* ws = get_workspace(stream);
+        const size_t tiles = (size_t)(N / 64) * p[2];
+        if (ws && tiles < (size_t)ws->ncounters && tiles * p[3] * p[0] * 4096 <= ws->slab_bytes) {
+            slabs = ws->ring_slabs;
+            counters = ws->counters;
+        } else {   // no workspace (e.g. first call inside a capture)
+            QS_REQUIRE(variant < QS_GEMM_RING_GEOMETRY_BASE || variant >= QS_GEMM_RING_GEOMETRY_END,
+                       "w4a8 gemm: no split-K workspace for the forced geometry");
+            plan = ring_unsplit(M, N, K);
+        }
+    }
+    switch (plan.family) {
+    case GEMM_WIDE:
+        return qs_launch_gemm_wide(MODE, outk, A, Wu, zeros, scales8, wscales, ascales, wszs, assums, out, M, N, K,
+                                   g_tiled_order / 10, stream);
+    case GEMM_TILED:
+        return qs_launch_gemm_tiled(MODE, outk, A, Wu, zeros, scales8, wscales, ascales, wszs, assums, out, M, N, K, p[0],
+                                    stream);
+    case GEMM_RING:
+        return qs_launch_gemm_ring(MODE, outk, p[0], p[1], A, Wu, zeros, scales8, wscales, ascales, wszs, assums, out, M, N,
+                                   K, p[2], p[3], slabs, counters, stream);
+    case GEMM_PAIR:
+        return qs_launch_gemm_pair(MODE, OUTK, A, Wu, zeros, scales8, wscales, ascales, wszs, assums, out, M, N, K, stream);
+    case GEMM_SPLITK:
 #define QS_GO(MTV) \
-    return launch_splitk<MTV, MODE, OUTK, 2>(A, Wu, zeros, scales8, wscales, ascales, wszs, assums, out, M, N, K, NW, S, xcd_map, stream)
-    if (mtile == 1) QS_GO(1);
-    if (mtile == 2) QS_GO(2);
-    if (mtile == 3) QS_GO(3);
-    QS_GO(4);
+    return launch_splitk<MTV, MODE, OUTK, 2>(A, Wu, zeros, scales8, wscales, ascales, wszs, assums, out, M, N, K, p[1], p[2], p[3], stream)
+        if (p[0] == 1) QS_GO(1);
+        if (p[0] == 2) QS_GO(2);
+        if (p[0] == 3) QS_GO(3);
+        QS_GO(4);
 #undef QS_GO
+    default:
+        return QS_UNFUSED;
+    }
 }
 
 }  // namespace
@@ -678,15 +700,14 @@ extern "C" int qs_debug_gemm_clock_probe(void* buf, int workgroups) {
 
 extern "C" int qs_w4a8_gemm_plan(int per_group, int M, int N, int K, int* plan5) {
     QS_REQUIRE(plan5, "w4a8 gemm plan: null output");
-    const int8_t* d8 = reinterpret_cast<const int8_t*>(uintptr_t(256));   // never dereferenced in plan-only mode
-    void* dv = reinterpret_cast<void*>(uintptr_t(256));
-    g_qs_plan = {1, 0, {0, 0, 0, 0}};
-    const int rc = per_group ? dispatch<1, 0>(d8, d8, d8, d8, dv, dv, nullptr, nullptr, dv, M, N, K, nullptr)
-                             : dispatch<0, 0>(d8, d8, nullptr, nullptr, dv, dv, dv, dv, dv, M, N, K, nullptr);
-    plan5[0] = g_qs_plan.family;
-    for (int i = 0; i < 4; ++i) plan5[1 + i] = g_qs_plan.p[i];
-    g_qs_plan.active = 0;
-    return rc;
+    for (int i = 0; i < 5; ++i) plan5[i] = 0;
+    if (int rc = check_shape(M, N, K)) return rc;
+    if (M == 0) return QS_OK;
+    const GemmPlan plan = plan_w4a8(per_group ? 1 : 0, false, M, N, K, g_variant);
+    if (plan.family == GEMM_INVALID) return QS_EINVAL;
+    plan5[0] = plan.family;
+    for (int i = 0; i < 4; ++i) plan5[1 + i] = plan.p[i];
+    return QS_OK;
 }
 
 extern "C" int qs_w4a8_per_chn_gemm(const int8_t* in_feats, const int8_t* kernel, const void* wscales,
@@ -751,13 +772,13 @@ namespace {
 struct PlanesGeo {
     int mt, wn, ks, mb;
 };
-bool planes_geometry(int mode, int M, int N, int K, PlanesGeo& g) {
+bool planes_geometry(int mode, int M, int N, int K, int variant, PlanesGeo& g) {
     if (M < 1 || M > 1024 || N < 64 || N % 64 || K < 1024 || K % 128 || (size_t)M * K >= (1ull << 32) ||
         (size_t)N * K / 2 >= (1ull << 32))
         return false;
     const int mt_all = (M + 15) / 16;
     static const int geo[7][2] = {{4, 2}, {2, 2}, {4, 1}, {2, 1}, {1, 1}, {4, 4}, {8, 2}};   // <8,2>: forced only (tests)
-    const int force = g_variant >= QS_GEMM_PLANES_GEOMETRY_BASE && g_variant < QS_GEMM_PLANES_GEOMETRY_END ? g_variant - QS_GEMM_PLANES_GEOMETRY_BASE : -1;   // tests / A-B: 4600 + 100*(ks-1) + 10*mt + wn
+    const int force = variant >= QS_GEMM_PLANES_GEOMETRY_BASE && variant < QS_GEMM_PLANES_GEOMETRY_END ? variant - QS_GEMM_PLANES_GEOMETRY_BASE : -1;   // tests / A-B: 4600 + 100*(ks-1) + 10*mt + wn
     long best = -1;
     for (int ks = 1; ks <= 4; ks *= 2)
         for (int i = 0; i < 7; ++i) {
@@ -779,7 +800,7 @@ int gemm_planes(const int8_t* A, const int8_t* W, const int8_t* zeros, const int
                 int K, qs_stream_t stream) {
     QS_REQUIRE(A && W && planes && (MODE == 0 || (zeros && scales8)), "w4a8 gemm (planes): null pointer");
     PlanesGeo g;
-    if (!planes_geometry(MODE, M, N, K, g)) {
+    if (!planes_geometry(MODE, M, N, K, g_variant, g)) {
         qs_set_error("w4a8 gemm (planes): no ring geometry for M=%d N=%d K=%d (ask qs_w4a8_gemm_planes_plan first)", M, N, K);
         return QS_ENOSUP;
     }
@@ -791,7 +812,7 @@ int gemm_planes(const int8_t* A, const int8_t* W, const int8_t* zeros, const int
 extern "C" int qs_w4a8_gemm_planes_plan(int per_group, int M, int N, int K, int* plan4) {
     QS_REQUIRE(plan4, "w4a8 gemm planes plan: null output");
     PlanesGeo g = {0, 0, 0, 0};
-    if (!planes_geometry(per_group ? 1 : 0, M, N, K, g)) g = {0, 0, 0, 0};      // k_slices == 0: not available, run the pair
+    if (!planes_geometry(per_group ? 1 : 0, M, N, K, g_variant, g)) g = {0, 0, 0, 0};      // k_slices == 0: not available, run the pair
     plan4[0] = g.ks, plan4[1] = g.mt, plan4[2] = g.wn, plan4[3] = g.mb;
     return QS_OK;
 }

@@ -634,17 +634,13 @@ int launch_tiled(const int8_t* A, const uint8_t* W, const int8_t* zeros, const i
 }  // namespace
 
 // Entry used by the dispatcher in gemm_w4a8.hip.  Preconditions (checked there): N % 256 == 0, K % 128 == 0, K >= 256.
+// mtile = m-tiles per wave: 8 = 256-token tile, 4 = 128-token tile.
 int qs_launch_gemm_tiled(int mode, int outk, const int8_t* A, const uint8_t* W, const int8_t* zeros,
                          const int8_t* scales8, const void* wscales, const void* ascales, const void* wszs,
                          const void* assums, void* out, int M, int N, int K, int mtile, hipStream_t stream) {
-    if (g_qs_plan.active) {
-        g_qs_plan.family = 4;
-        g_qs_plan.p[0] = mtile == 0 ? (M > 128 ? 8 : 4) : mtile, g_qs_plan.p[1] = g_qs_plan.p[2] = g_qs_plan.p[3] = 0;
-        return QS_OK;
-    }
 #define QS_T(MTV, MODEV, OUTV) \
     return launch_tiled<MTV, MODEV, OUTV>(A, W, zeros, scales8, wscales, ascales, wszs, assums, out, M, N, K, stream)
-    const bool big = mtile == 0 ? M > 128 : mtile == 8;
+    const bool big = mtile == 8;
 #ifdef QS_TIMING   // timing experiments (results are wrong by design): not in the shipped library
     if (mode == 0 && outk == 0 && big && g_tiled_dbg) {
 #define QS_D(D) case D: return launch_tiled<8, 0, 0, D>(A, W, zeros, scales8, wscales, ascales, wszs, assums, out, M, N, K, stream)

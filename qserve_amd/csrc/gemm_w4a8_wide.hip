@@ -622,11 +622,6 @@ int launch_wide(const int8_t* A, const uint8_t* W, const int8_t* zeros, const in
 int qs_launch_gemm_wide(int mode, int outk, const int8_t* A, const uint8_t* W, const int8_t* zeros,
                         const int8_t* scales8, const void* wscales, const void* ascales, const void* wszs,
                         const void* assums, void* out, int M, int N, int K, int persist_mode, hipStream_t stream) {
-    if (g_qs_plan.active) {
-        g_qs_plan.family = 5;
-        g_qs_plan.p[0] = 8, g_qs_plan.p[1] = g_qs_plan.p[2] = g_qs_plan.p[3] = 0;
-        return QS_OK;
-    }
 #define QS_T(MODEV, OUTV) \
     return launch_wide<MODEV, OUTV>(A, W, zeros, scales8, wscales, ascales, wszs, assums, out, M, N, K, persist_mode, stream)
 #ifdef QS_TIMING   // timing experiments (results are wrong by design): not in the shipped library

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Which W4A8 GEMM problems of the reference's model zoo still dispatch to the two ROUND-1 decode kernels (family 1 = register-staged
 split-K, gemm_w4a8.hip; family 2 = LDS-pair, gemm_w4a8_lds.hip) instead of the ring (3) / tiled (4) / wide (5) kernels?  Plan only
-(qs_w4a8_gemm_plan runs the dispatcher without touching a device): works in the CPU container.  VERDICT r05 item 8.
+(qs_w4a8_gemm_plan asks the dispatcher's planning function, which touches no device): works in the CPU container.  VERDICT r05 item 8.
 
     python scripts/list_dispatch_families.py            -> table on stdout (committed as profiles/round6_dispatch_families.txt)
 """

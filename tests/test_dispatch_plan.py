@@ -2,6 +2,7 @@
 measured heuristics of DESIGN.md 5.1 - a change here must come with new measurements (scripts/bench_gemm_shard.py)."""
 import pytest
 
+from qserve_amd._lib import lib
 from qserve_amd.plan import attention_plan, gemm_plan
 
 
@@ -95,6 +96,24 @@ def test_rejected_shapes_raise():
         gemm_plan(64, 4096, 4000)       # K % 128
 
 
+def test_selection_hook_codes_are_decoded_by_the_planner():
+    """qs_set_gemm_variant codes (include/qserve_amd.h qs_gemm_variant_code) as the plan entry sees them."""
+    try:
+        lib.qs_set_gemm_variant(2001)                           # LDS-pair kernel forced
+        assert gemm_plan(64, 4096, 4096) == dict(family="pair")
+        lib.qs_set_gemm_variant(4000)                           # ring kernel off: the round-1 kernels serve decode shapes
+        assert gemm_plan(64, 4096, 4096)["family"] == "splitk"
+        assert gemm_plan(64, 4096, 4096, per_group=True)["family"] == "splitk"
+        lib.qs_set_gemm_variant(3003)                           # four-wave 256-token tile forced, per-channel too
+        assert gemm_plan(64, 4096, 4096) == dict(family="wide", tile_tokens=256)
+        lib.qs_set_gemm_variant(4121)                           # forced ring geometry <2,1>, no K slices
+        assert gemm_plan(64, 4096, 4096) == ring(2, 1, 2)
+        lib.qs_set_gemm_variant(4211)                           # forced ring geometry <1,1> x 2 K slices
+        assert gemm_plan(64, 4096, 4096) == ring(1, 1, 4, 2)
+    finally:
+        lib.qs_set_gemm_variant(-1)
+
+
 # ---- decode attention ----------------------------------------------------------------------------------------------
 def test_attention_headline_config_is_one_workgroup_per_sequence_and_kv_head():
     assert attention_plan(64, 32, 8, 24, 1536) == dict(family="mfma_kv4", kv_splits=1, waves=8)     # 512 workgroups
@@ -128,3 +147,14 @@ def test_attention_rejects_bad_head_counts():
         attention_plan(4, 30, 8, 24, 1000)          # heads not a multiple of kv heads
     with pytest.raises(RuntimeError):
         attention_plan(4, 72, 8, 24, 1000)          # group of 9 query heads
+
+
+def test_attention_selection_hook_codes_are_decoded_by_the_planner():
+    try:
+        lib.qs_set_attention_variant(1)                         # VALU kernels everywhere
+        assert attention_plan(8, 32, 8, 24, 1535) == dict(family="valu", kv_splits=1, waves=4)
+        lib.qs_set_attention_variant(103)                       # exactly 3 KV splits, KV4 and KV8
+        assert attention_plan(8, 32, 8, 24, 1535) == dict(family="mfma_kv4", kv_splits=3, waves=8)
+        assert attention_plan(8, 32, 8, 24, 1535, int4_kv_cache=False) == dict(family="mfma_kv8", kv_splits=3, waves=4)
+    finally:
+        lib.qs_set_attention_variant(0)
