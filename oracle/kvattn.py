@@ -113,6 +113,19 @@ def rope_neox(x, pos, base):
     return np.concatenate([ra, rb], axis=-1).astype(np.float16)
 
 
+def rope_neox_inv(x, pos, base):
+    """The inverse rotation of rope_neox (by -pos), same coefficients and roundings: rope_neox(rope_neox_inv(x, p), p)
+    equals x up to two fp16 roundings.  For building inputs whose ROTATED vectors are prescribed (tests/_attn_cases.py)."""
+    x = np.asarray(x, np.float16)
+    dim = x.shape[-1]
+    c, s = rope_coef(pos, dim, base)
+    a = x[..., : dim // 2].astype(np.float32)
+    b = x[..., dim // 2:].astype(np.float32)
+    ra = ((c * a).astype(np.float32) + (s * b).astype(np.float32)).astype(np.float32)
+    rb = ((c * b).astype(np.float32) - (s * a).astype(np.float32)).astype(np.float32)
+    return np.concatenate([ra, rb], axis=-1).astype(np.float16)
+
+
 def kv_scale_zero(x, int4):
     """Per-(token, head) asymmetric parameters, Template.hpp:1051-1082 / applyBias...h:288-331.
     x fp16 [..., dim] -> (scale f16, zero f16, inv_scale f32)."""

@@ -3,6 +3,24 @@ import numpy as np
 import torch
 
 
+class DevPools:
+    """One layer's K and V page pools on the device (uint8 [nblocks, page_bytes], the oracle's PagePool layout)."""
+
+    def __init__(self, nblocks, hkv, int4, device, fill=0xFF):
+        from oracle import kvattn
+        self.pb = kvattn.page_bytes(hkv, 128, int4)
+        self.k = torch.full((nblocks, self.pb), fill, dtype=torch.uint8, device=device)
+        self.v = torch.full((nblocks, self.pb), fill, dtype=torch.uint8, device=device)
+
+    def pointers(self, tables):
+        """block indices [B,2,mb] -> device addresses, as model_runner.py:396-414 builds them."""
+        t = torch.from_numpy(tables.copy())
+        p = torch.empty_like(t)
+        p[:, 0] = self.k.data_ptr() + t[:, 0] * self.pb
+        p[:, 1] = self.v.data_ptr() + t[:, 1] * self.pb
+        return p.to(self.k.device)
+
+
 def dev(x, device="cuda:0"):
     return torch.from_numpy(np.ascontiguousarray(x)).to(device)
 

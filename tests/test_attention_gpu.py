@@ -6,27 +6,12 @@ import numpy as np
 import pytest
 import torch
 
-from _helpers import dev, ulp_diff_f16
+from _helpers import DevPools, dev, ulp_diff_f16  # noqa: F401  (DevPools: also imported from here by other tests)
 from oracle import kvattn, synth
 
 pytestmark = pytest.mark.gpu
 ROPE = 5e5
 TOL = 1e-3   # north_star: "within 1e-3 on the fp16 attention output"
-
-
-class DevPools:
-    def __init__(self, nblocks, hkv, int4, device, fill=0xFF):
-        self.pb = kvattn.page_bytes(hkv, 128, int4)
-        self.k = torch.full((nblocks, self.pb), fill, dtype=torch.uint8, device=device)
-        self.v = torch.full((nblocks, self.pb), fill, dtype=torch.uint8, device=device)
-
-    def pointers(self, tables):
-        """block indices [B,2,mb] -> device addresses, as model_runner.py:396-414 builds them."""
-        t = torch.from_numpy(tables.copy())
-        p = torch.empty_like(t)
-        p[:, 0] = self.k.data_ptr() + t[:, 0] * self.pb
-        p[:, 1] = self.v.data_ptr() + t[:, 1] * self.pb
-        return p.to(self.k.device)
 
 
 def run_case(gpu, B, H, Hkv, lengths, int4, seed):
