@@ -428,6 +428,34 @@ int qs_debug_wave_reduce_selftest(const float* in, float* out, int n, qs_stream_
  * QS_EINVAL for any other value. */
 int qs_debug_flash_variant(int variant);
 
+/* Append attention (no reference counterpart): n >= 1 NEW tokens per sequence against a context that already sits in the quantised
+ * pages - chunked prefill, prefix reuse, verification of drafted tokens.  Sequence b has past_lens[b] tokens in its pages and
+ * n = cu_seqlens_q[b + 1] - cu_seqlens_q[b] new rows in the packed fp16 qkv buffer [T, (H + 2 Hkv) * 128] (n = 0 is legal);
+ * past + n <= 64 * max_blocks, past need not be a multiple of 64.  Device pointers: cu_seqlens_q int32 [batch + 1], past_lens
+ * int32 [batch], kv_pointers int64 [batch, 2, max_blocks] (page addresses, as for qs_single_query_attention).
+ *   qs_append_rope_update_kv_cache  new token i: q and k NeoX-rotated at position past + i in place in qkv; rotated K and raw V
+ *                      quantised per (token, KV head) into the page slot of position past + i - byte for byte what
+ *                      qs_apply_bias_rope_update_kv_cache stores for that position.
+ *   qs_append_attention  query row i attends to keys 0 .. past + i: positions < past de-quantised from the pages (the decode
+ *                      kernels' values), positions >= past in fp16 from the ALREADY ROTATED qkv (rotated k, raw v).  fp32 softmax,
+ *                      scale 1/sqrt(128), out fp16 [T, H, 128] with row stride out_stride0 (elements).  The two calls touch
+ *                      disjoint page slots: no ordering is needed between them.  past = 0 is the prefill attention, n = 1 the
+ *                      decode attention.  qkv and out 16-byte aligned, strides multiples of 8 elements.
+ *   qs_append_attention_plan  pure (no device access): plan3 = {tokens per query tile, query tiles per sequence at max_seqlen_q,
+ *                      waves per workgroup} of the launch the arguments would get; all zero for an empty launch.  One workgroup
+ *                      serves a query tile of ONE KV head with all H / Hkv query heads: rows = (token, head-in-group) pairs.
+ * QS_EINVAL: null pointers, bad sizes / head counts / strides;  QS_ENOSUP: head_dim != 128, tokens_per_block != 64, caches
+ * without zero points, H / Hkv > 8. */
+int qs_append_rope_update_kv_cache(void* qkv, const int32_t* cu_seqlens_q, const int32_t* past_lens,
+                                   const int64_t* kv_pointers, int num_tokens, int batch, int max_blocks, int head_num,
+                                   int kv_head_num, int tokens_per_block, int size_per_token, int rotary_embedding_dim,
+                                   float rotary_base, int int4_kv_cache, int kv_cache_with_zeros, qs_stream_t stream);
+int qs_append_attention(const void* qkv, void* out, const int32_t* cu_seqlens_q, const int32_t* past_lens,
+                        const int64_t* kv_pointers, int num_tokens, int batch, int max_seqlen_q, int max_blocks, int num_heads,
+                        int num_kv_heads, int head_dim, int64_t qkv_stride0, int64_t out_stride0, int tokens_per_block,
+                        int size_per_token, int int4_kv_cache, int kv_cache_with_zeros, qs_stream_t stream);
+int qs_append_attention_plan(int batch, int max_seqlen_q, int num_heads, int num_kv_heads, int* plan3);
+
 /* Timing tool (scripts/trace_attn.py): device-to-device copy of the first `bytes` of the split-KV workspace, where the
  * trace instantiation of the KV4 decode attention (qs_set_attention_variant(232)) leaves its s_memtime stamps.
  * (A library built with -DQS_RING_TRACE additionally exports qs_debug_ring_trace(void* buf) for scripts/trace_gemm.py;

@@ -71,6 +71,9 @@ SIGNATURES = {
     "qs_debug_flash_variant": (_i, [_i]),
     "qs_flash_attn_varlen_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i64, _i64, _i64, _i, _i, _f,
                                       _i, _vp]),
+    "qs_append_rope_update_kv_cache": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _vp]),
+    "qs_append_attention": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i64, _i64, _i, _i, _i, _i, _vp]),
+    "qs_append_attention_plan": (_i, [_i, _i, _i, _i, _vp]),
 }
 
 

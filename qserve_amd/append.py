@@ -1,0 +1,80 @@
+"""Append attention (extension; NOT part of the reference's `qserve_backend` surface): n >= 1 new tokens per sequence against a
+context that already sits in the quantised KV4 / KV8 pages - chunked prefill, prefix reuse, verification of drafted tokens.
+
+Sequence b has `past_lens[b]` tokens in its pages and `cu_seqlens_q[b + 1] - cu_seqlens_q[b]` new rows in the packed fp16
+`qkv` buffer [T, (H + 2 Hkv) * 128] (the layout the prefill writer takes; n = 0 is legal).  include/qserve_amd.h has the contract:
+
+    append_rope_update_kv_cache   new token i: q, k rotated at position past + i in place; K / V quantised into that position's slot
+    append_attention              row i attends to keys 0 .. past + i: < past de-quantised from the pages, >= past in fp16 from qkv
+    append                        the two, in that order -> out fp16 [T, H, 128]
+
+`past = 0` is the prefill pair (apply_bias_rope_update_kv_cache + flash_attn_varlen_func), `n = 1` is single_query_attention.
+Backed by qserve_amd/csrc/append_attention.hip and the offset-aware writer in attention.hip."""
+import torch
+
+from .backend._util import check, expect, guard, lib, ptr, stream
+
+
+def _check_common(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, size_per_token, int4_kv, what):
+    expect(qkv, torch.float16, "qkv")
+    expect(cu_seqlens_q, torch.int32, "cu_seqlens_q")
+    expect(past_lens, torch.int32, "past_lens")
+    expect(kv_pointers, torch.int64, "kv_pointers")
+    H, Hkv = int(num_heads), int(num_kv_heads)
+    if H <= 0 or Hkv <= 0 or H % Hkv != 0:
+        raise RuntimeError(f"{what}: bad head counts H={H} Hkv={Hkv}")
+    if H // Hkv > 8:
+        raise NotImplementedError(f"{what}: {H // Hkv} query heads per KV head (1..8 are provided, as for decode)")
+    if qkv.dim() != 2 or qkv.size(1) != (H + 2 * Hkv) * 128:
+        raise RuntimeError(f"{what}: qkv must be [tokens, (H + 2 Hkv) * 128] = [T, {(H + 2 * Hkv) * 128}], got {tuple(qkv.shape)}")
+    batch = past_lens.numel()
+    if cu_seqlens_q.dim() != 1 or past_lens.dim() != 1 or cu_seqlens_q.numel() != batch + 1:
+        raise RuntimeError(f"{what}: cu_seqlens_q must be [batch + 1] and past_lens [batch]")
+    if kv_pointers.dim() != 3 or kv_pointers.size(0) != batch or kv_pointers.size(1) != 2:
+        raise RuntimeError(f"{what}: kv_pointers must be [batch, 2, max_blocks], got {tuple(kv_pointers.shape)}")
+    if int(size_per_token) != Hkv * (64 if int4_kv else 128):
+        raise RuntimeError(f"{what}: size_per_token={size_per_token}, expected {Hkv * (64 if int4_kv else 128)}")
+    return batch
+
+
+def append_rope_update_kv_cache(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, size_per_token, rope_theta,
+                                int4_kv):
+    """In place on `qkv` (q and k heads rotated at positions past + i) and on the pages behind `kv_pointers`."""
+    what = "append.append_rope_update_kv_cache"
+    batch = _check_common(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, size_per_token, int4_kv, what)
+    with guard(qkv):
+        check(lib.qs_append_rope_update_kv_cache(ptr(qkv), ptr(cu_seqlens_q), ptr(past_lens), ptr(kv_pointers), qkv.size(0), batch,
+                                                 kv_pointers.size(-1), int(num_heads), int(num_kv_heads), 64, int(size_per_token),
+                                                 128, float(rope_theta), int(bool(int4_kv)), 1, stream()), what)
+
+
+def append_attention(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, size_per_token, int4_kv,
+                     max_seqlen_q=None, out=None):
+    """`qkv` ALREADY rotated (append_rope_update_kv_cache) -> out fp16 [T, H, 128].  `max_seqlen_q`: an upper bound of the new
+    tokens per sequence (sizes the launch; default: all T rows - correct, without a device read-back, but a larger grid)."""
+    what = "append.append_attention"
+    batch = _check_common(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, size_per_token, int4_kv, what)
+    T, H = qkv.size(0), int(num_heads)
+    if out is None:
+        out = torch.empty((T, H, 128), dtype=torch.float16, device=qkv.device)
+    else:
+        expect(out, torch.float16, "out", contiguous=False)
+        if tuple(out.shape) != (T, H, 128) or out.stride(2) != 1 or out.stride(1) != 128 or out.stride(0) % 8 != 0:
+            raise RuntimeError(f"{what}: out must be [T, H, 128] with contiguous heads and a row stride that is a multiple of 8")
+    msq = T if max_seqlen_q is None else int(max_seqlen_q)
+    if msq < 0:
+        raise RuntimeError(f"{what}: max_seqlen_q={msq}")
+    with guard(qkv):
+        check(lib.qs_append_attention(ptr(qkv), ptr(out), ptr(cu_seqlens_q), ptr(past_lens), ptr(kv_pointers), T, batch, min(msq, T),
+                                      kv_pointers.size(-1), H, int(num_kv_heads), 128, qkv.stride(0), out.stride(0), 64,
+                                      int(size_per_token), int(bool(int4_kv)), 1, stream()), what)
+    return out
+
+
+def append(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, size_per_token, rope_theta, int4_kv,
+           max_seqlen_q=None):
+    """Writer, then attention (the two touch disjoint page slots; the attention needs the writer's in-place rotation of qkv)."""
+    append_rope_update_kv_cache(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, size_per_token, rope_theta,
+                                int4_kv)
+    return append_attention(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, size_per_token, int4_kv,
+                            max_seqlen_q=max_seqlen_q)

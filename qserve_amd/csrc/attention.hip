@@ -484,29 +484,12 @@ __device__ __forceinline__ void group_quant_store(const h8& lo, const h8& hi, ui
     }
 }
 
+// one token's row: RoPE at `pos` in place on the q and k heads, quantised K / V into the page slot of `pos` of sequence b
 template <bool INT4>
-__global__ __launch_bounds__(TPB) void prefill_kv_vec_kernel(_Float16* __restrict__ qkv, const int* __restrict__ seq_lens,
-                                                             const int* __restrict__ padding_offset,
-                                                             const int64_t* __restrict__ kv_pointers, int num_tokens,
-                                                             int max_blocks, int head_num, int kv_head_num, int seq_len,
-                                                             const float2* __restrict__ rope_tab) {
+__device__ __forceinline__ void kv_vec_token(_Float16* row, const RopeCS (&cs)[8], int b, int pos, int dg, int slot0,
+                                             const int64_t* __restrict__ kv_pointers, int max_blocks, int head_num,
+                                             int kv_head_num) {
     constexpr int DHB = INT4 ? DH / 2 : DH;
-    const int t = blockIdx.x;
-    const int g = t + (padding_offset ? padding_offset[t] : 0);
-    const int b = g / seq_len, pos = g % seq_len;          // applyBias...h:186-194
-    if (pos >= seq_lens[b]) return;
-    const int dg = threadIdx.x & 7, slot0 = threadIdx.x >> 3;   // TPB / 8 head slots per pass
-    const int n = (head_num + 2 * kv_head_num) * DH;
-    _Float16* row = qkv + (size_t)t * n;
-    RopeCS cs[8];
-    {
-        const float4* tp = reinterpret_cast<const float4*>(rope_tab + (size_t)pos * 64 + 8 * dg);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float4 v = tp[j];
-            cs[2 * j].c = v.x, cs[2 * j].s = v.y, cs[2 * j + 1].c = v.z, cs[2 * j + 1].s = v.w;
-        }
-    }
     for (int job = slot0; job < head_num + kv_head_num; job += TPB / 8) {
         _Float16* hp = row + job * DH;                      // q heads, then k heads: contiguous in the row
         const h8 lo = *reinterpret_cast<const h8*>(hp + 8 * dg), hi = *reinterpret_cast<const h8*>(hp + 64 + 8 * dg);
@@ -536,6 +519,64 @@ __global__ __launch_bounds__(TPB) void prefill_kv_vec_kernel(_Float16* __restric
                                     vsc + kv_head_num * PAGE_TOK + hk * PAGE_TOK + slot, dg);
         }
     }
+}
+__device__ __forceinline__ void rope_cs_from_table(const float2* __restrict__ rope_tab, int pos, int dg, RopeCS (&cs)[8]) {
+    const float4* tp = reinterpret_cast<const float4*>(rope_tab + (size_t)pos * 64 + 8 * dg);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float4 v = tp[j];
+        cs[2 * j].c = v.x, cs[2 * j].s = v.y, cs[2 * j + 1].c = v.z, cs[2 * j + 1].s = v.w;
+    }
+}
+
+template <bool INT4>
+__global__ __launch_bounds__(TPB) void prefill_kv_vec_kernel(_Float16* __restrict__ qkv, const int* __restrict__ seq_lens,
+                                                             const int* __restrict__ padding_offset,
+                                                             const int64_t* __restrict__ kv_pointers, int num_tokens,
+                                                             int max_blocks, int head_num, int kv_head_num, int seq_len,
+                                                             const float2* __restrict__ rope_tab) {
+    const int t = blockIdx.x;
+    const int g = t + (padding_offset ? padding_offset[t] : 0);
+    const int b = g / seq_len, pos = g % seq_len;          // applyBias...h:186-194
+    if (pos >= seq_lens[b]) return;
+    const int dg = threadIdx.x & 7, slot0 = threadIdx.x >> 3;   // TPB / 8 head slots per pass
+    const int n = (head_num + 2 * kv_head_num) * DH;
+    RopeCS cs[8];
+    rope_cs_from_table(rope_tab, pos, dg, cs);
+    kv_vec_token<INT4>(qkv + (size_t)t * n, cs, b, pos, dg, slot0, kv_pointers, max_blocks, head_num, kv_head_num);
+}
+
+// The offset-aware writer of the append path (qs_append_rope_update_kv_cache; no reference counterpart): token t of the packed
+// buffer belongs to the sequence b with cu_q[b] <= t < cu_q[b + 1] and sits at position past_lens[b] + (t - cu_q[b]).  The same
+// arithmetic per element as the prefill writer (kv_vec_token); cos / sin from the library's table where it covers the position,
+// otherwise evaluated here (rope_coef: the same double-evaluated, float-rounded values).  Positions outside the pointer table
+// are skipped.
+template <bool INT4>
+__global__ __launch_bounds__(TPB) void append_kv_vec_kernel(_Float16* __restrict__ qkv, const int* __restrict__ cu_q,
+                                                            const int* __restrict__ past_lens,
+                                                            const int64_t* __restrict__ kv_pointers, int batch, int max_blocks,
+                                                            int head_num, int kv_head_num, const float2* __restrict__ rope_tab,
+                                                            int tab_len, float rope_base) {
+    const int t = blockIdx.x;
+    if (t < cu_q[0] || t >= cu_q[batch]) return;
+    int b = 0, hi_b = batch;                                // largest b with cu_q[b] <= t (empty sequences are stepped over)
+    while (b + 1 < hi_b) {
+        const int mid = (b + hi_b) >> 1;
+        if (cu_q[mid] <= t) b = mid;
+        else hi_b = mid;
+    }
+    const int pos = past_lens[b] + (t - cu_q[b]);
+    if (pos < 0 || pos >= max_blocks * PAGE_TOK) return;
+    const int dg = threadIdx.x & 7, slot0 = threadIdx.x >> 3;
+    const int n = (head_num + 2 * kv_head_num) * DH;
+    RopeCS cs[8];
+    if (rope_tab && pos < tab_len) {
+        rope_cs_from_table(rope_tab, pos, dg, cs);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) cs[j] = rope_coef(8 * dg + j, pos, rope_base, DH);
+    }
+    kv_vec_token<INT4>(qkv + (size_t)t * n, cs, b, pos, dg, slot0, kv_pointers, max_blocks, head_num, kv_head_num);
 }
 
 __global__ void padding_offsets_kernel(int* __restrict__ out, const int* __restrict__ cu, int max_seqlen) {
@@ -797,6 +838,41 @@ extern "C" int qs_apply_bias_rope_update_kv_cache(void* qkv, const int32_t* seq_
                            padding_offset, kv_pointers, num_tokens, max_blocks, head_num, kv_head_num, seq_len,
                            rotary_embedding_base);
     return qs_launch_status("apply_bias_rope_update_kv_cache");
+}
+
+// The prefill writer for tokens that CONTINUE a sequence (append attention, include/qserve_amd.h): new token i of sequence b is
+// rotated at position past_lens[b] + i and quantised into that position's page slot.
+extern "C" int qs_append_rope_update_kv_cache(void* qkv, const int32_t* cu_seqlens_q, const int32_t* past_lens,
+                                              const int64_t* kv_pointers, int num_tokens, int batch, int max_blocks,
+                                              int head_num, int kv_head_num, int tokens_per_block, int size_per_token,
+                                              int rotary_embedding_dim, float rotary_base, int int4_kv_cache,
+                                              int kv_cache_with_zeros, qs_stream_t stream) {
+    QS_REQUIRE(qkv && cu_seqlens_q && past_lens && kv_pointers, "append_rope_update_kv_cache: null pointer");
+    QS_REQUIRE(head_num > 0 && kv_head_num > 0 && batch >= 0 && num_tokens >= 0 && max_blocks > 0,
+               "append_rope_update_kv_cache: bad sizes");
+    if (rotary_embedding_dim != 128 || tokens_per_block != 64 || !kv_cache_with_zeros) {
+        qs_set_error("append_rope_update_kv_cache: only head_dim=128, tokens_per_block=64 and "
+                     "zero-point KV caches are supported");
+        return QS_ENOSUP;
+    }
+    const int dhb = int4_kv_cache ? 64 : 128;
+    QS_REQUIRE(size_per_token == kv_head_num * dhb, "append_rope_update_kv_cache: size_per_token=%d, expected %d", size_per_token,
+               kv_head_num * dhb);
+    if (num_tokens == 0 || batch == 0) return QS_OK;
+    hipStream_t st = (hipStream_t)stream;
+    // (table length: the pointer table's reach rounded up to a power of two >= 2048 - calls with growing tables share an entry
+    //  of the library's few table slots; positions a table does not cover are evaluated in the kernel)
+    int want = 2048, tab_len = 0;
+    while (want < max_blocks * PAGE_TOK && want < 32768) want *= 2;
+    const float2* tab = g_attn_variant == 2 ? nullptr : qs_rope_table(rotary_base, want, st, &tab_len);
+    if (!tab) tab_len = 0;
+    if (int4_kv_cache)
+        hipLaunchKernelGGL(append_kv_vec_kernel<true>, dim3(num_tokens), dim3(TPB), 0, st, (_Float16*)qkv, cu_seqlens_q, past_lens,
+                           kv_pointers, batch, max_blocks, head_num, kv_head_num, tab, tab_len, rotary_base);
+    else
+        hipLaunchKernelGGL(append_kv_vec_kernel<false>, dim3(num_tokens), dim3(TPB), 0, st, (_Float16*)qkv, cu_seqlens_q, past_lens,
+                           kv_pointers, batch, max_blocks, head_num, kv_head_num, tab, tab_len, rotary_base);
+    return qs_launch_status("append_rope_update_kv_cache");
 }
 
 extern "C" int qs_compute_padding_offsets(int32_t* padding_offsets, const int32_t* cu_seqlens, int batch,

@@ -284,33 +284,25 @@ class DecodeEngine:
         torch.cuda.synchronize()
 
     # ---- real prefill: the reference's is_prompt=True path (llama_w4a8_unpad.py:199-243, 330-361) -------------
-    def prefill(self, prompt_len, tokens=None):
-        """Run the prompt through the model: per layer  norm+quant -> qkv GEMM -> apply_bias_rope_update_kv_cache
-        (RoPE in place + quantised cache write) -> flash_attn_varlen_func (causal) -> quant -> o_proj -> residual+norm
-        -> gate_up -> silu_and_mul+quant -> down -> residual.  All sequences have `prompt_len` tokens.  Leaves the
-        cache filled, `hidden` = last-token states, `tokens` = first sampled token, lengths = prompt_len + 1."""
-        from .flash import flash_attn_varlen_func
-        cfg, B, dev = self.cfg, self.B, self.dev
-        assert self.with_lm_head and prompt_len + 1 <= self.max_len
-        T = B * prompt_len
-        f16, i8 = torch.float16, torch.int8
+    def _prompt_buffers(self, T):
+        """Activation buffers of the is_prompt path for T rows."""
+        f16, i8, dev = torch.float16, torch.int8, self.dev
+        return dict(
+            qa=torch.empty((T, self.hid), dtype=i8, device=dev), qo=torch.empty((T, self.H * 128), dtype=i8, device=dev),
+            q_mlp=torch.empty((T, self.inter), dtype=i8, device=dev), q_scale=torch.empty((T,), dtype=f16, device=dev),
+            q_sum=torch.empty((T,), dtype=f16, device=dev), qkv=torch.empty((T, self.qkv_n), dtype=f16, device=dev),
+            proj=torch.empty((T, self.hid), dtype=f16, device=dev),
+            gate_up=torch.empty((T, 2 * self.inter), dtype=f16, device=dev),
+            mlp_act=torch.empty((T, self.inter), dtype=f16, device=dev))
+
+    def _prompt_layers(self, h, bufs, attend):
+        """The layer stack of the is_prompt path, in place on h (fp16 [T, hid]); `bufs`: _prompt_buffers of >= T rows.
+        attend(li, qkv) -> fp16 [T, H * 128]: cache write + attention of layer li on its packed qkv rows (prefill: writer + flash
+        over the call's own k / v; prefill_chunked: append attention over the pages + the chunk)."""
+        cfg, T = self.cfg, h.size(0)
         fuse_sum, fuse = self.group_size == -1, self.fuse_pairs
-        if tokens is None:
-            tokens = torch.randint(0, cfg["vocab"], (T,), device=dev,
-                                   generator=torch.Generator(device=dev).manual_seed(7))
-        h = torch.index_select(self.embed, 0, tokens)
-        qa = torch.empty((T, self.hid), dtype=i8, device=dev)
-        qo = torch.empty((T, self.H * 128), dtype=i8, device=dev)
-        q_mlp = torch.empty((T, self.inter), dtype=i8, device=dev)
-        q_scale = torch.empty((T,), dtype=f16, device=dev)
-        q_sum = torch.empty((T,), dtype=f16, device=dev)
-        qkv = torch.empty((T, self.qkv_n), dtype=f16, device=dev)
-        proj = torch.empty((T, self.hid), dtype=f16, device=dev)
-        gate_up = torch.empty((T, 2 * self.inter), dtype=f16, device=dev)
-        mlp_act = torch.empty((T, self.inter), dtype=f16, device=dev)
-        seq = torch.full((B,), prompt_len, dtype=torch.int32, device=dev)
-        cu = torch.arange(0, B + 1, device=dev, dtype=torch.int32) * prompt_len
-        pad = fused_attention.compute_padding_offsets(cu, prompt_len, T)
+        qa, qo, q_mlp, q_scale, q_sum, qkv, proj, gate_up, mlp_act = (
+            bufs[k][:T] for k in ("qa", "qo", "q_mlp", "q_scale", "q_sum", "qkv", "proj", "gate_up", "mlp_act"))
         sums = q_sum if fuse_sum else None
 
         def norm_quant(x, w):
@@ -331,13 +323,7 @@ class DecodeEngine:
             if li == 0:
                 norm_quant(h, L["ln1"])
             L["qkv"](qa, q_scale, q_sum, qkv)
-            fused_attention.apply_bias_rope_update_kv_cache(
-                qkv, seq, pad, self.tables[li], self.H, self.Hkv, prompt_len, 64, self.size_per_token, 128,
-                cfg["rope_theta"], 8192, True, self.int4, True)
-            q, k, v = qkv.split([self.H * 128, self.Hkv * 128, self.Hkv * 128], dim=-1)
-            attn = flash_attn_varlen_func(q.reshape(T, self.H, 128), k.reshape(T, self.Hkv, 128),
-                                          v.reshape(T, self.Hkv, 128), cu, cu, prompt_len, prompt_len, dropout_p=0.0,
-                                          causal=True).reshape(T, -1)
+            attn = attend(li, qkv)
             if fuse_sum:
                 fused_kernels.invoke_quant_fuse_sum(qo, attn, q_sum, q_scale)
             else:
@@ -368,9 +354,11 @@ class DecodeEngine:
                 add_norm_quant(h, proj, self.layers[li + 1]["ln1"])
             else:
                 residual_add_(h, proj)
-        last = (cu[1:] - 1).to(torch.int64)
-        torch.index_select(h, 0, last, out=self.hidden)
-        layernorm_ops.rms_norm(self.final, self.hidden, self.norm_w, cfg["eps"])
+
+    def _prompt_head(self, last_rows, prompt_len):
+        """Last-token states -> `hidden`, first sampled token -> `tokens`, lengths = prompt_len + 1."""
+        self.hidden.copy_(last_rows)
+        layernorm_ops.rms_norm(self.final, self.hidden, self.norm_w, self.cfg["eps"])
         if self.vocab_parallel:
             tpmod.all_reduce_sum_(self._head_local())                # in place, through the process group
             self._head_finish(self.head_cand)
@@ -378,6 +366,66 @@ class DecodeEngine:
             logits = torch.matmul(self.final, self.lm_head.t())
             argmax_rows_(logits, self.tokens)
         self.lengths.fill_(prompt_len + 1)
+
+    def prefill(self, prompt_len, tokens=None):
+        """Run the prompt through the model: per layer  norm+quant -> qkv GEMM -> apply_bias_rope_update_kv_cache
+        (RoPE in place + quantised cache write) -> flash_attn_varlen_func (causal) -> quant -> o_proj -> residual+norm
+        -> gate_up -> silu_and_mul+quant -> down -> residual.  All sequences have `prompt_len` tokens.  Leaves the
+        cache filled, `hidden` = last-token states, `tokens` = first sampled token, lengths = prompt_len + 1."""
+        from .flash import flash_attn_varlen_func
+        cfg, B, dev = self.cfg, self.B, self.dev
+        assert self.with_lm_head and prompt_len + 1 <= self.max_len
+        T = B * prompt_len
+        if tokens is None:
+            tokens = torch.randint(0, cfg["vocab"], (T,), device=dev,
+                                   generator=torch.Generator(device=dev).manual_seed(7))
+        h = torch.index_select(self.embed, 0, tokens)
+        bufs = self._prompt_buffers(T)
+        seq = torch.full((B,), prompt_len, dtype=torch.int32, device=dev)
+        cu = torch.arange(0, B + 1, device=dev, dtype=torch.int32) * prompt_len
+        pad = fused_attention.compute_padding_offsets(cu, prompt_len, T)
+
+        def attend(li, qkv):
+            fused_attention.apply_bias_rope_update_kv_cache(
+                qkv, seq, pad, self.tables[li], self.H, self.Hkv, prompt_len, 64, self.size_per_token, 128,
+                cfg["rope_theta"], 8192, True, self.int4, True)
+            q, k, v = qkv.split([self.H * 128, self.Hkv * 128, self.Hkv * 128], dim=-1)
+            return flash_attn_varlen_func(q.reshape(T, self.H, 128), k.reshape(T, self.Hkv, 128),
+                                          v.reshape(T, self.Hkv, 128), cu, cu, prompt_len, prompt_len, dropout_p=0.0,
+                                          causal=True).reshape(T, -1)
+
+        self._prompt_layers(h, bufs, attend)
+        last = (cu[1:] - 1).to(torch.int64)
+        self._prompt_head(torch.index_select(h, 0, last), prompt_len)
+
+    def prefill_chunked(self, prompt_len, chunk, tokens=None):
+        """`prefill` in chunks of `chunk` tokens per sequence (the last one may be shorter): the same op sequence per chunk on
+        B * chunk rows - the activations never hold more -, attention through qserve_amd.append.append with past = c * chunk
+        (the chunk's K / V go into the pages, its queries attend to the pages of the earlier chunks and, in fp16, to the chunk
+        itself); lm_head and sampling once, after the last chunk.  Ends in the state `prefill` ends in.  `tokens`: as for
+        `prefill`, [B * prompt_len], sequence-major."""
+        from . import append as appendmod      # (looked up per call: `appendmod.append` is the seam tests wrap)
+        cfg, B, dev = self.cfg, self.B, self.dev
+        assert self.with_lm_head and prompt_len + 1 <= self.max_len and chunk >= 1
+        if tokens is None:
+            tokens = torch.randint(0, cfg["vocab"], (B * prompt_len,), device=dev,
+                                   generator=torch.Generator(device=dev).manual_seed(7))
+        tokens = tokens.view(B, prompt_len)
+        chunk = min(chunk, prompt_len)
+        bufs = self._prompt_buffers(B * chunk)
+        h = None
+        for c0 in range(0, prompt_len, chunk):
+            n = min(chunk, prompt_len - c0)
+            h = torch.index_select(self.embed, 0, tokens[:, c0:c0 + n].reshape(-1))
+            cu = torch.arange(0, B + 1, device=dev, dtype=torch.int32) * n
+            past = torch.full((B,), c0, dtype=torch.int32, device=dev)
+
+            def attend(li, qkv):
+                return appendmod.append(qkv, cu, past, self.tables[li], self.H, self.Hkv, self.size_per_token,
+                                        cfg["rope_theta"], self.int4, max_seqlen_q=n).reshape(B * n, -1)
+
+            self._prompt_layers(h, bufs, attend)
+        self._prompt_head(h.view(B, -1, self.hid)[:, -1], prompt_len)
 
     # ---- one decode step (llama_w4a8_unpad.py:330-361 per layer) --------------------------------------------
     def _segments(self):

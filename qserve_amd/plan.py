@@ -30,3 +30,12 @@ def attention_plan(batch, num_heads, num_kv_heads, max_blocks, timestep, int4_kv
     check(lib.qs_attention_plan(batch, num_heads, num_kv_heads, max_blocks, timestep, int(bool(int4_kv_cache)),
                                 C.cast(buf, C.c_void_p)), "attention plan")
     return dict(family=ATTN_FAMILIES.get(buf[0], "none"), kv_splits=buf[1], waves=buf[2])
+
+
+def append_attention_plan(batch, max_seqlen_q, num_heads, num_kv_heads):
+    """-> dict(tile_tokens, q_tiles, waves): the append attention launcher's geometry (`qs_append_attention_plan`).  One
+    workgroup serves `tile_tokens` new tokens of one KV head with all its query heads; all zero for an empty launch."""
+    buf = (C.c_int * 3)()
+    check(lib.qs_append_attention_plan(batch, max_seqlen_q, num_heads, num_kv_heads, C.cast(buf, C.c_void_p)),
+          "append attention plan")
+    return dict(tile_tokens=buf[0], q_tiles=buf[1], waves=buf[2])
