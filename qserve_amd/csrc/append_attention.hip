@@ -7,9 +7,10 @@
 // to fp16), keys >= past are the rotated k / raw v of this call, read in fp16 from the packed qkv buffer.  fp32 softmax, scale
 // 1/sqrt(128), fp16 output.  past = 0 is the prefill attention, n = 1 the decode attention.
 //
-// Mapping: the key loop is the prefill provider's (flash_prefill.hip: swapped products S^T = K Q^T / O^T = V^T P^T on
-// v_mfma_f32_32x32x16_f16, 64-key tiles in LDS - K with a 16-byte XOR swizzle, V transposed on read by ds_read_b64_tr_b16 -, lazy
-// running maximum, O out through LDS as whole rows); what differs is WHO the 128 rows of a workgroup are and WHERE a tile comes from:
+// Mapping: the key loop is the prefill provider's, by construction - both kernels are built on the tile core of flash_tile.h (swapped
+// products S^T = K Q^T / O^T = V^T P^T on v_mfma_f32_32x32x16_f16, 64-key tiles in LDS - K with a 16-byte XOR swizzle, V transposed on
+// read by ds_read_b64_tr_b16 -, lazy running maximum, O out through LDS as whole rows); what differs from flash_prefill.hip is WHO the
+// 128 rows of a workgroup are and WHERE a tile comes from:
 //   * workgroup = (sequence, KV head, query tile); its rows are (token, head-in-group) pairs, row r = G * token + g, so the G query
 //     heads of a KV group share every staged tile: a cached byte is fetched once per (sequence, KV head, query tile) - the decode
 //     kernels' rule, because with a long `past` and a short n this op is bound by the cache bytes as decode is.  The causal limit
@@ -23,37 +24,13 @@
 //   * phase 2, the new tokens' fp16 k / v rows from qkv by LDS-DMA in 64-key tiles with the causal mask, exactly as in the prefill
 //     provider.
 // One barrier per tile, two LDS buffers, online softmax across both phases.  No split-KV: a workgroup walks the whole past.
-#include "common.h"
-#include <type_traits>
-#include <utility>
+#include "flash_tile.h"
 
 namespace {
 
-typedef float v16f __attribute__((ext_vector_type(16)));
-typedef u32 v2u __attribute__((ext_vector_type(2)));
+using namespace qs_flash;
 
-constexpr int DH = 128;
-constexpr int NWV = 4;            // waves per workgroup (32 rows each)
-constexpr int BM = 32 * NWV;      // (token, head) rows per workgroup
-constexpr int PPW = 16 / NWV;     // 1 KiB DMA pieces of a K (and of a V) tile per wave
-constexpr int BN = 64;            // keys per tile = tokens per page
-constexpr int KS_BYTES = BN * DH * 2;
-constexpr int VT_BYTES = BN * DH * 2;
 constexpr int MAX_G = 8;          // query heads per KV head (the decode kernels' range)
-
-__device__ __forceinline__ u32 pack_h2(float a, float b) {
-    const h2 v = {(_Float16)a, (_Float16)b};
-    return __builtin_bit_cast(u32, v);
-}
-
-template <class F, int... I>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
 
 // exact uint4 -> fp16 for the 8 nibbles of x, in the order (e0,e4),(e1,e5),(e2,e6),(e3,e7) (the decode kernels' form, attention.hip)
 __device__ __forceinline__ void nib8_to_h2(u32 x, h2 (&o)[4]) {
@@ -122,8 +99,8 @@ __global__ __launch_bounds__(64 * NWV, 2) void append_attention_kernel(const _Fl
     constexpr int DHB = INT4 ? DH / 2 : DH;        // bytes per cached token and head
     constexpr int NQ = INT4 ? 1 : 2;               // 16-byte loads per thread, page and tensor
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    uint8_t (*s_k)[KS_BYTES] = reinterpret_cast<uint8_t (*)[KS_BYTES]>(smem);                    // [2][16 KiB]
-    uint8_t (*s_vt)[VT_BYTES] = reinterpret_cast<uint8_t (*)[VT_BYTES]>(smem + 2 * KS_BYTES);    // [2][16 KiB]
+    uint8_t* const s_k = smem;                           // [2][16 KiB]  } the tile images of flash_tile.h
+    uint8_t* const s_vt = smem + 2 * KS_BYTES;           // [2][16 KiB]  }
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -153,45 +130,12 @@ __global__ __launch_bounds__(64 * NWV, 2) void append_attention_kernel(const _Fl
         for (int s = 0; s < 8; ++s) qf[s] = *reinterpret_cast<const h8*>(qp + 16 * s);
     }
 
-    // ---- phase 2 staging by LDS-DMA (the prefill provider's): a 1 KiB piece = 4 keys x 256 B, wave w copies K pieces 4w .. 4w+3
-    // and the same V pieces; the XOR swizzles of the images are applied to the per-lane SOURCE chunk; keys beyond the sequence
-    // are clamped to its last row (finite data; their scores are masked)
+    // ---- phase 2 staging by LDS-DMA (stage_fp16_tile): the new tokens' k / v rows of this KV head in the packed qkv buffer
     const _Float16* kg = qkv + (size_t)q_start * qkv_stride0 + (size_t)(num_heads + hkv) * DH;
-    const _Float16* vg = kg + (size_t)num_kv_heads * DH;
-    typedef __attribute__((address_space(3))) void* lptr_t;
-    const u32 lds_k = (u32)(size_t)(lptr_t)smem, lds_v = lds_k + 2 * KS_BYTES;
-    auto dma16 = [&](u32 voff, const void* sbase, u32 lds_addr) {
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_addr) : "memory");
-    };
-    static_assert(PPW == 4, "the per-piece offsets below are derived for four pieces per wave");
-    const int l4 = lane >> 4, pos = lane & 15;
-    const u32 koff0 = (u32)l4 * (u32)qkv_stride0 * 2u + (u32)((pos ^ l4) * 16);
-    const u32 voff0 = (u32)l4 * (u32)qkv_stride0 * 2u + (u32)((pos ^ (l4 << 2)) * 16);
-    auto load_new = [&](int j, int buf) {
-        const _Float16* kb_ = kg + ((size_t)j * BN + 4 * PPW * wave) * qkv_stride0;   // first key of this wave's pieces
-        const _Float16* vb_ = vg + ((size_t)j * BN + 4 * PPW * wave) * qkv_stride0;
-        const bool ragged = j * BN + BN > n;            // wave-uniform: only the last tile of a sequence
-#pragma unroll
-        for (int i = 0; i < PPW; ++i) {
-            if (ragged) {                                 // clamp the row to the sequence's last key (offsets from the TILE's base)
-                // (from a lane id of its own: derived from `lane`, the per-piece offsets of this once-per-workgroup path are loop
-                //  invariants the compiler keeps in - and spills from - registers across the key loop)
-                const int fl = (int)fresh_lane_id(), l4r = fl >> 4, posr = fl & 15;
-                const int key = 4 * (PPW * wave + i) + l4r;
-                int kc = n - 1 - j * BN;
-                kc = key < kc ? key : kc;
-                const u32 ko = (u32)kc * (u32)qkv_stride0 * 2u + (u32)((posr ^ (key & 15)) * 16);
-                const u32 vo = (u32)kc * (u32)qkv_stride0 * 2u + (u32)((posr ^ ((key & 3) << 2)) * 16);
-                dma16(ko, kg + (size_t)j * BN * qkv_stride0, lds_k + buf * KS_BYTES + (PPW * wave + i) * 1024);
-                dma16(vo, vg + (size_t)j * BN * qkv_stride0, lds_v + buf * VT_BYTES + (PPW * wave + i) * 1024);
-            } else {
-                u32 ko = koff0;
-                if (i > 0) asm volatile("v_xor_b32 %0, %1, %2" : "=v"(ko) : "n"(64 * i), "v"(koff0));
-                dma16(ko, kb_ + (size_t)(4 * i) * qkv_stride0, lds_k + buf * KS_BYTES + (PPW * wave + i) * 1024);
-                dma16(voff0, vb_ + (size_t)(4 * i) * qkv_stride0, lds_v + buf * VT_BYTES + (PPW * wave + i) * 1024);
-            }
-        }
-    };
+    const TileRows ksrc = k_rows(kg, qkv_stride0, lane);
+    const TileRows vsrc = v_rows(kg + (size_t)num_kv_heads * DH, qkv_stride0, lane);
+    const u32 lds_k = lds_address(smem), lds_v = lds_k + 2 * KS_BYTES;
+    auto load_new = [&](int j, int buf) { stage_fp16_tile(j, buf, n, wave, lds_k, ksrc, vsrc); };
 
     // ---- phase 1 staging: this head's [64 tokens][DHB bytes] slice of a page is contiguous.  Wave w owns tokens 16w .. 16w+15 of the
     // page - thread (token 16w + (lane >> 2), quarter lane & 3) de-quantises dims 32 quarter .. + 31 of K and of V - and the tile rows
@@ -232,8 +176,8 @@ __global__ __launch_bounds__(64 * NWV, 2) void append_attention_kernel(const _Fl
     auto commit_page = [&](int p, int buf) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's own pieces are in LDS
         const int fl = (int)fresh_lane_id(), ptl = fl >> 2, pc4 = fl & 3;   // token within the wave's 16, quarter
-        uint8_t* const wk = &s_k[buf][wave * 4096];
-        uint8_t* const wv = &s_vt[buf][wave * 4096];
+        uint8_t* const wk = s_k + buf * KS_BYTES + wave * 4096;
+        uint8_t* const wv = s_vt + buf * VT_BYTES + wave * 4096;
         v4u rk[NQ], rv[NQ];
 #pragma unroll
         for (int i = 0; i < NQ; ++i) {
@@ -260,10 +204,6 @@ __global__ __launch_bounds__(64 * NWV, 2) void append_attention_kernel(const _Fl
             *reinterpret_cast<h8*>(wk + ptl * 256 + ((chunk ^ (ptok & 15)) * 16)) = kd[m];
             *reinterpret_cast<h8*>(wv + ptl * 256 + ((chunk ^ ((ptok & 3) << 2)) * 16)) = vd[m];
         }
-    };
-    auto tiles_landed = [&]() {                       // every wave's pieces: own queue drained, then the barrier
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
     };
     // tile t + 1 on its way while tile t is computed: a page's raw bytes (issue) that become its fp16 image behind the compute
     // (commit), or a tile of new keys straight into the other buffers
@@ -301,130 +241,20 @@ __global__ __launch_bounds__(64 * NWV, 2) void append_attention_kernel(const _Fl
         constexpr int buf = decltype(bufc)::value;
         issue_next(t, buf ^ 1);                       // lands in the other buffers during this tile
 
-        // ---------------- S^T = K Q^T : two blocks of 32 keys, operand reads one group of 4 MFMAs ahead ----------------
-        v16f sacc[2];
-        {
-            h8 ka[2][4];
-            auto read_k = [&](int g, h8 (&dst)[4]) {       // group g = (kb = g >> 1, s = 4 (g & 1) .. +3)
-                const int key = 32 * (g >> 1) + li;
-                const uint8_t* krow = &s_k[buf][key * 256];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int sl = 4 * (g & 1) + j;
-                    dst[j] = *reinterpret_cast<const h8*>(krow + (((2 * sl + hi) ^ (key & 15)) * 16));
-                }
-            };
-            read_k(0, ka[0]);
-            read_k(1, ka[1]);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const v16f zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                    const bool first = (g & 1) == 0 && j == 0;
-                    sacc[g >> 1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ka[g & 1][j], qf[4 * (g & 1) + j], first ? zero16 : sacc[g >> 1], 0, 0, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                if (g + 2 < 4) read_k(g + 2, ka[g & 1]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        // A operands of O^T += V^T P^T by the LDS transpose read (flash_prefill.hip): a 16-lane group reads the [4 keys][16 dims]
-        // block of the row-major tile and lane c receives column c = (dim c, keys 0..3), its four k-slots of the PV MFMA
-        const int ta = lane & 15, g1 = (lane >> 4) & 1;
-        const int tkey = 4 * hi + (ta >> 2);
+        v16f sacc[NKB];
+        qk_tile(smem, bufc, lane, qf, sacc);
         h8 va[2][4];
-        auto read_v = [&](int d, h8 (&dst)[4]) {
-            const int chunk = (4 * d + 2 * g1 + ((ta & 3) >> 1)) ^ ((ta >> 2) << 2);   // V image swizzle: chunk ^ 4 (key & 3)
-            const uint8_t* vrow = &s_vt[buf][tkey * 256 + chunk * 16 + (ta & 1) * 8];
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int m = 0; m < 2; ++m) {
-                    const int kofs = (32 * kb + 16 * m) * 256;
-                    typedef short s4 __attribute__((ext_vector_type(4)));
-                    typedef __attribute__((address_space(3))) s4* lds_s4;
-                    const s4 t0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)(vrow + kofs));             // keys +0..3
-                    const s4 t1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)(vrow + kofs + 8 * 256));   // keys +8..11
-                    const v2u lo = __builtin_bit_cast(v2u, t0), hi2 = __builtin_bit_cast(v2u, t1);
-                    dst[2 * kb + m] = __builtin_bit_cast(h8, (v4u){lo.x, lo.y, hi2.x, hi2.y});
-                }
-        };
-        read_v(0, va[0]);
+        read_v(smem, bufc, lane, 0, va[0]);           // group 0 of the P.V operands, requested under the softmax
         __builtin_amdgcn_sched_barrier(0);
-        // sacc[kb][r] = score of (this lane's row, key 32kb + (r&3) + 8(r>>2) + 4hi of the tile).  A page is masked where it holds
-        // slots >= past (its last one only), a tile of new keys where it touches the diagonal of a row of this wave or the end of the
-        // new tokens (wave-uniform tests); `limit` = the last key of the tile this lane's row may see
+        // A page is masked where it holds slots >= past (its last one only), a tile of new keys where it touches the diagonal of a row
+        // of this wave or the end of the new tokens (wave-uniform tests); `limit` = the last key of the tile this lane's row may see
         const bool page = t < np;
         const int j0 = (t - np) * BN;
         const bool need_mask = page ? t * BN + BN > past : j0 + BN - 1 > tok_first || j0 + BN > n;
-        float mx = -INFINITY;
-        if (need_mask) {
-            const int limit = page ? past - 1 - t * BN : tok_ld - j0;
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int key = 32 * kb + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                    const float sv = key <= limit ? sacc[kb][r] : -INFINITY;
-                    sacc[kb][r] = sv;
-                    mx = fmaxf(mx, sv);
-                }
-        } else {
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sacc[kb][r]);
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64)) * scale_log2;      // scale > 0: max commutes with it
-        // lazy reference maximum: it moves only when a tile exceeds it by more than 2^8 (probabilities stay <= 256 in fp16, sums in
-        // fp32: the same softmax), so the rescale of O is rare
-        const float m_new = mx > m_run + 8.0f ? mx : m_run;
-        const float m_use = m_new == -INFINITY ? 0.f : m_new;     // fully masked so far: keep exp2 arguments finite
-        const float alpha = __builtin_amdgcn_exp2f(m_run - m_use);
-        m_run = m_new;
-        typedef float v2f __attribute__((ext_vector_type(2)));
-        const v2f sc2 = {scale_log2, scale_log2}, nm2 = {-m_use, -m_use};
-        v2f psum2 = {0.f, 0.f};
-        u32 pb[2][2][4];                                           // [kb][m]: 8 probabilities in B-operand order
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const v2f sv = {sacc[kb][8 * m + 2 * j], sacc[kb][8 * m + 2 * j + 1]};
-                    v2f pp = __builtin_elementwise_fma(sv, sc2, nm2);
-                    pp[0] = __builtin_amdgcn_exp2f(pp[0]);          // -inf stays -inf -> 0
-                    pp[1] = __builtin_amdgcn_exp2f(pp[1]);
-                    psum2 += pp;
-                    pb[kb][m][j] = pack_h2(pp[0], pp[1]);
-                }
-        l_run = l_run * alpha + (psum2[0] + psum2[1]);
-        if (__builtin_expect(__any(alpha != 1.0f), 0)) {           // the reference maximum moved for some row of this wave
-#pragma unroll
-            for (int d = 0; d < 4; ++d)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) oacc[d][r] *= alpha;
-        }
-
-        // ---------------- O^T += V^T P^T ----------------
-        read_v(1, va[1]);
-        __builtin_amdgcn_sched_barrier(0);
-        static_for<4>([&](auto dc) {
-            constexpr int d = decltype(dc)::value;
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int m = 0; m < 2; ++m) {
-                    const h8 pbv = __builtin_bit_cast(h8, (v4u){pb[kb][m][0], pb[kb][m][1], pb[kb][m][2], pb[kb][m][3]});
-                    oacc[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(va[d & 1][2 * kb + m], pbv, oacc[d], 0, 0, 0);
-                }
-            __builtin_amdgcn_sched_barrier(0);
-            if (d + 2 < 4) read_v(d + 2, va[d & 1]);
-            __builtin_amdgcn_sched_barrier(0);
-        });
+        auto limit = [&] { return page ? past - 1 - t * BN : tok_ld - j0; };
+        u32 pb[NKB][2][4];
+        softmax_tile<true>(sacc, need_mask, limit, lane, scale_log2, m_run, l_run, oacc, pb);
+        pv_tile(smem, bufc, lane, va, pb, oacc);
         commit_next(t, buf ^ 1);
         tiles_landed();
     };
@@ -452,33 +282,17 @@ __global__ __launch_bounds__(64 * NWV, 2) void append_attention_kernel(const _Fl
     }
     if (!wave_rows) return;                              // (behind the last barrier)
 
-    // ---- epilogue: normalise, fp16, out through LDS as whole 256-byte rows (flash_prefill.hip).  A wave writes its 32 x 128 block
-    // into its own 8.5 KiB of the (dead) tile buffers - every wave has passed the last tile's barrier - and reads it back 16 bytes
-    // per lane, 16 lanes per row; row r of the workgroup goes to (token tok0 + r / G, head hkv G + r % G).
+    // ---- epilogue: normalise, fp16, out through LDS as whole 256-byte rows (store_rows_through_lds); row r of the workgroup goes
+    // to (token tok0 + r / G, head hkv G + r % G)
+    // (the two lines of the normaliser stay in the kernel: as a helper of flash_tile.h they cost this kernel ~50 registers and spills)
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     const float inv = l_tot > 0.f ? 1.0f / l_tot : 0.f;
-    constexpr int OST = 272;
-    uint8_t* const so = smem + wave * (32 * OST);
-    const int li_e = (int)(fresh_lane_id() & 31u), hi_e = (int)(fresh_lane_id() >> 5);
-    static_for<4>([&](auto dc) {
-        constexpr int d = decltype(dc)::value;
-        static_for<4>([&](auto rc) {
-            constexpr int rq = decltype(rc)::value;
-            h4 o;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) o[j] = (_Float16)(oacc[d][4 * rq + j] * inv);
-            *reinterpret_cast<h4*>(so + li_e * OST + (32 * d + 8 * rq + 4 * hi_e) * 2) = o;
-        });
-    });
-    const int lid = (int)fresh_lane_id(), rr = lid >> 4, cc = lid & 15;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int rl = 4 * j + rr, r = wave * 32 + rl;
+    store_rows_through_lds(smem, wave, oacc, inv, [&](int rl, int cc, const v4u& x) {
+        const int r = wave * 32 + rl;
         const int tok = tok0 + r / G;
-        const v4u x = *reinterpret_cast<const v4u*>(so + rl * OST + cc * 16);
         if (r < tq * G && tok < n)
             *reinterpret_cast<v4u*>(out + (size_t)(q_start + tok) * o_stride0 + (size_t)(hkv * G + r % G) * DH + cc * 8) = x;
-    }
+    });
 }
 
 }  // namespace
@@ -524,19 +338,11 @@ extern "C" int qs_append_attention(const void* qkv, void* out, const int32_t* cu
     if (rc != QS_OK) return rc;
     if (batch == 0 || max_seqlen_q == 0 || num_tokens == 0) return QS_OK;
     constexpr int SMEM = 2 * KS_BYTES + 2 * VT_BYTES;
-    static bool configured_dev[QS_MAX_DEVICES] = {};   // the attribute belongs to the (kernel, device) pair
-    bool& configured = configured_dev[qs_device_slot()];
-    if (!configured) {
-        hipError_t e1 = hipSuccess;
-        for (const void* fn : {reinterpret_cast<const void*>(append_attention_kernel<true>), reinterpret_cast<const void*>(append_attention_kernel<false>)}) {
-            const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-            if (e != hipSuccess) e1 = e;
-        }
-        if (e1 != hipSuccess) {
-            qs_set_error("append_attention: cannot reserve %d bytes of LDS", SMEM);
-            return (int)e1;
-        }
-        configured = true;
+    static bool lds_reserved[QS_MAX_DEVICES] = {};
+    if (const hipError_t e = qs_reserve_lds({reinterpret_cast<const void*>(append_attention_kernel<true>), reinterpret_cast<const void*>(append_attention_kernel<false>)},
+                                            SMEM, lds_reserved); e != hipSuccess) {
+        qs_set_error("append_attention: cannot reserve %d bytes of LDS", SMEM);
+        return (int)e;
     }
     const float scale_log2 = 0.08838834764831845f * 1.4426950408889634f;   // 1/sqrt(128) * log2(e)
     const dim3 grid(num_kv_heads, plan3[1], batch), block(64 * plan3[2]);

@@ -46,7 +46,6 @@ constexpr int UT = 32;         // tokens per pipeline unit (half a page)
 constexpr int USB = UT * DHB;  // bytes of K (or V) data per unit and KV head
 constexpr int NW = QS_ATTN_WAVES_KV4;   // waves per workgroup; all of them may own units
 constexpr int NWT = NW;
-typedef u32 v2u __attribute__((ext_vector_type(2)));
 constexpr int QS_ATTNQ_CAP = 4096;   // sequences the attention + quant fusion can hand over (larger batches run the pair)
 constexpr int QS_ATTNQ_ROW = 4096;   // values per row at most (H x 128 <= 4096: quant_kernel's 256-thread mapping)
 constexpr int SVC = NW - 1;    // the service wave (RoPE, operand build, new token) - the wave that owns the fewest units
@@ -74,10 +73,6 @@ __device__ __forceinline__ void wave_quant_store4(_Float16 v0, _Float16 v1, uint
     }
 }
 
-__device__ __forceinline__ u32 pack_h2(float a, float b) {
-    const h2 v = {(_Float16)a, (_Float16)b};
-    return __builtin_bit_cast(u32, v);
-}
 // (x & m) | c as ONE v_and_or_b32: m and c live in VGPRs (VOP3 takes no 32-bit literals, which is why the compiler
 // otherwise emits v_and + v_or with literal operands)
 __device__ __forceinline__ u32 and_or(u32 x, u32 m, u32 c) {

@@ -38,11 +38,6 @@ __device__ __forceinline__ void wave_quant_store8(_Float16 v0, _Float16 v1, uint
     }
 }
 
-__device__ __forceinline__ u32 pack_h2(float a, float b) {
-    const h2 v = {(_Float16)a, (_Float16)b};
-    return __builtin_bit_cast(u32, v);
-}
-
 // cache policy of the page DMA: non-temporal (aux bit 1) - every KV byte is read exactly once per step (measured on the
 // KV4 twin: -4 % at L = 1033 ... -12 % at L = 4096); QS_KV8_NT=0 at build time restores the default policy for A/B
 #ifndef QS_KV8_NT
@@ -50,7 +45,6 @@ __device__ __forceinline__ u32 pack_h2(float a, float b) {
 #endif
 constexpr int NT_AUX = QS_KV8_NT ? 2 : 0;
 typedef __attribute__((address_space(3))) const uint8_t* lds_u8;   // 32-bit LDS address (keeps ds_read, not flat_load)
-typedef u32 v2u __attribute__((ext_vector_type(2)));
 #define LDS_AT(T, p) (*(const __attribute__((address_space(3))) T*)(p))
 
 template <int G>

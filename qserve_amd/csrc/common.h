@@ -6,6 +6,9 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <initializer_list>
+#include <type_traits>
+#include <utility>
 
 #include "../../include/qserve_amd.h"
 
@@ -16,6 +19,23 @@ typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32;
 typedef unsigned int v4u __attribute__((ext_vector_type(4)));
+typedef u32 v2u __attribute__((ext_vector_type(2)));
+
+// two floats -> one register of two fp16 (round to nearest even)
+__device__ __forceinline__ u32 pack_h2(float a, float b) {
+    const h2 v = {(_Float16)a, (_Float16)b};
+    return __builtin_bit_cast(u32, v);
+}
+
+// compile-time loop: f(std::integral_constant<int, 0>{}), ..., f(<N-1>)
+template <class F, int... I>
+__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
+    (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+    static_for_impl(f, std::make_integer_sequence<int, N>{});
+}
 
 void qs_set_error(const char* fmt, ...);
 
@@ -42,6 +62,21 @@ static inline int qs_device_slot() {
     int d = 0;
     if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= QS_MAX_DEVICES) d = 0;
     return d;
+}
+
+// Reserve `bytes` of dynamic LDS for each of `kernels`, once per device: the attribute belongs to the (kernel, device) pair, so
+// `done` is the launcher's own static flag array (one per kernel set, or per launcher instantiation).  Returns the last failure -
+// the launcher words its own error text - and leaves the flag clear so that the next launch tries again.
+static inline hipError_t qs_reserve_lds(std::initializer_list<const void*> kernels, int bytes, bool (&done)[QS_MAX_DEVICES]) {
+    bool& configured = done[qs_device_slot()];
+    if (configured) return hipSuccess;
+    hipError_t e1 = hipSuccess;
+    for (const void* fn : kernels) {
+        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (e != hipSuccess) e1 = e;
+    }
+    configured = e1 == hipSuccess;
+    return e1;
 }
 
 // silu(x) rounded to fp16 with the hardware exp2 / rcp forms (what the reference's --use_fast_math build computes; see

@@ -5,63 +5,19 @@
 //   max_seqlen_k, causal=True)            (qserve/modeling/models/llama_w4a8_unpad.py:30,232-242)
 // flash-attn v2 semantics: softmax(scale * Q K^T) V per sequence and head, fp32 softmax, causal mask aligned to the
 // bottom-right corner when the query and key lengths differ.  The algorithm is the published FlashAttention-2 forward
-// (online softmax over key tiles, no S x S matrix); the mapping below is written for CDNA4:
+// (online softmax over key tiles, no S x S matrix).  The mapping onto CDNA4 - 64-key tiles of K and V in LDS, swapped products on
+// v_mfma_f32_32x32x16_f16, register-only softmax, O out through LDS as whole rows - is the tile core of flash_tile.h, shared with
+// append_attention.hip; what this file adds is WHO the rows are and the tile schedule:
 //   * workgroup = 4 wave64 = 128 query rows of one (sequence, head); wave w owns 32 rows and keeps their Q fragments
 //     (8 x 16 dims) in registers for the whole key loop;
-//   * key/value tiles of 64 keys are staged through LDS once per workgroup (shared by the 4 waves; the G query heads
-//     of a GQA group are separate workgroups that re-read the tiles from L2): K row-major with a 16-byte XOR swizzle,
-//     V row-major too (16-byte chunk ^ 4 (key & 3): the 32 lanes of a transpose read then hit 32 distinct 8-byte slots;
-//     chunk ^ 2 (key & 3), the round-1 form, left them two-way conflicted - SQ_LDS_BANK_CONFLICT was a third of the LDS cycles) and TRANSPOSED ON READ by ds_read_b64_tr_b16, both tiles
-//     double-buffered, one barrier per tile;
-//   * "swapped" products on v_mfma_f32_32x32x16_f16:  S^T = K Q^T  (A = K rows, B = Q rows, both plain 16-byte reads)
-//     leaves every lane holding 16 of the 32 scores of ITS OWN query row, so the softmax is register-only (one
-//     cross-lane max with lane ^ 32) and the probabilities already sit in B-operand order for
-//     O^T = V^T P^T  (A = V^T fragments, two transpose reads each; k-slot <-> key mapping chosen to match the S^T layout);
-//   * exp2 with the scale folded into one fp32 multiply; rescaling of O only through the running max.
-#include "common.h"
-#include <type_traits>
-#include <utility>
+//   * the tiles are the fp16 k / v rows of the sequence, staged once per workgroup (the G query heads of a GQA group are separate
+//     workgroups that re-read the tiles from L2), up to the causal diagonal of the workgroup's last row.
+#include "flash_tile.h"
 
 namespace {
 
-typedef float v16f __attribute__((ext_vector_type(16)));
-typedef u32 v2u __attribute__((ext_vector_type(2)));
+using namespace qs_flash;
 
-#ifndef QS_FLASH_DBG
-#define QS_FLASH_DBG 0            // timing experiments (scripts/bench_flash.py; results wrong): 1 no exp2, 2 no P.V, 4 no Q.K^T, 8 no tile loads, 16 no key loop, 32 no output stores, 64 no Q loads
-#endif
-constexpr int DH = 128;
-#ifndef QS_FLASH_NW
-#define QS_FLASH_NW 4
-#endif
-constexpr int NWV = QS_FLASH_NW;  // waves per workgroup (32 query rows each)
-constexpr int BM = 32 * NWV;      // query rows per workgroup
-constexpr int PPW = 16 / NWV;     // 1 KiB DMA pieces of a K (and of a V) tile per wave
-#ifndef QS_FLASH_NKB
-#define QS_FLASH_NKB 2
-#endif
-#ifndef QS_FLASH_OCC
-#define QS_FLASH_OCC 2
-#endif
-constexpr int NKB = QS_FLASH_NKB;  // 32-key blocks per tile
-constexpr int BN = 32 * NKB;      // keys per tile
-constexpr int KS_BYTES = BN * DH * 2;             // 16 KiB
-constexpr int VT_BYTES = BN * DH * 2;             // 16 KiB (row-major like K; transposed on read)
-
-__device__ __forceinline__ u32 pack_h2(float a, float b) {
-    const h2 v = {(_Float16)a, (_Float16)b};
-    return __builtin_bit_cast(u32, v);
-}
-
-// compile-time loop: f(std::integral_constant<int, 0>{}), ..., f(<N-1>)
-template <class F, int... I>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
 #ifdef QS_FLASH_TRACE
 // timing builds only (scripts/trace_flash.py): cycles per phase of the key loop, summed per wave
 __device__ unsigned long long* g_flash_trace = nullptr;
@@ -87,7 +43,7 @@ __device__ unsigned long long* g_flash_trace = nullptr;
 //  (5) O leaves through LDS as whole rows (see the epilogue).
 // In-run A/B (profiles/round6_flash_ab7.txt): 64 x 1 024 tokens 0.233 -> 0.277 of the dense fp16 MFMA peak, 4 x 8 192: 0.345 -> 0.397.
 template <bool CAUSAL, int VAR>
-__global__ __launch_bounds__(64 * NWV, QS_FLASH_OCC) void flash_fwd_kernel(const _Float16* __restrict__ q, const _Float16* __restrict__ k,
+__global__ __launch_bounds__(64 * NWV, 2) void flash_fwd_kernel(const _Float16* __restrict__ q, const _Float16* __restrict__ k,
                                                           const _Float16* __restrict__ v, _Float16* __restrict__ out,
                                                           const int* __restrict__ cu_q, const int* __restrict__ cu_k,
                                                           int num_heads, int num_kv_heads, int64_t q_stride0,
@@ -95,8 +51,6 @@ __global__ __launch_bounds__(64 * NWV, QS_FLASH_OCC) void flash_fwd_kernel(const
                                                           float scale_log2) {
     constexpr bool R6 = VAR != 0;      // VAR: 0 = the kernel of rounds 2-5 (A/B: qs_debug_flash_variant(1)), 1 = round 6 (default)
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    uint8_t (*s_k)[KS_BYTES] = reinterpret_cast<uint8_t (*)[KS_BYTES]>(smem);                    // [2][16 KiB]
-    uint8_t (*s_vt)[VT_BYTES] = reinterpret_cast<uint8_t (*)[VT_BYTES]>(smem + 2 * KS_BYTES);    // [2][16 KiB]
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -123,10 +77,7 @@ __global__ __launch_bounds__(64 * NWV, QS_FLASH_OCC) void flash_fwd_kernel(const
     {
         const _Float16* qp = q + (size_t)(q_start + row_ld) * q_stride0 + (size_t)h * DH + 8 * hi;
 #pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            if (QS_FLASH_DBG & 64) qf[s] = (h8){(_Float16)(0.01f * lane), 1, 2, 3, 4, 5, 6, (_Float16)s};
-            else qf[s] = *reinterpret_cast<const h8*>(qp + 16 * s);
-        }
+        for (int s = 0; s < 8; ++s) qf[s] = *reinterpret_cast<const h8*>(qp + 16 * s);
     }
 
     // ---- key range ----------------------------------------------------------------------------------------------------
@@ -135,57 +86,13 @@ __global__ __launch_bounds__(64 * NWV, QS_FLASH_OCC) void flash_fwd_kernel(const
         const int last = qt * BM + BM - 1 + shift;     // largest key any row of this workgroup may see
         kv_end = last + 1 < len_k ? last + 1 : len_k;
     }
-    const int ntiles = (QS_FLASH_DBG & 16) ? 0 : kv_end > 0 ? (kv_end + BN - 1) / BN : 0;   // (DBG 16: prologue + epilogue only)
+    const int ntiles = kv_end > 0 ? (kv_end + BN - 1) / BN : 0;
 
-    // ---- tile staging by LDS-DMA: a 1 KiB piece = 4 keys x 256 B; wave w copies K pieces 4w .. 4w+3 and the same V pieces.
-    // The DMA writes lane-linear (lane l -> key l >> 4 of the piece, 16-byte position l & 15), so the XOR swizzles of the
-    // images are applied to the per-lane SOURCE chunk.  No staging registers, no ds_write pass; keys beyond the sequence
-    // are clamped to its last row (finite data; their scores are masked, their probabilities are 0).
-    const _Float16* kg = k + (size_t)k_start * k_stride0 + (size_t)hkv * DH;
-    const _Float16* vg = v + (size_t)k_start * v_stride0 + (size_t)hkv * DH;
-    typedef __attribute__((address_space(3))) void* lptr_t;
-    const u32 lds_k = (u32)(size_t)(lptr_t)smem, lds_v = lds_k + 2 * KS_BYTES;
-    // scalar base (advances by one tile) + per-lane 32-bit byte offset (constant): no per-lane 64-bit arithmetic per piece
-    auto dma16 = [&](u32 voff, const void* sbase, u32 lds_addr) {
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_addr) : "memory");
-    };
-    static_assert(NKB == 2, "the DMA staging below is written for 64-key tiles");
-    // Per-lane source offsets: ONE register each for K and V (round 6; were PPW each).  Piece i of a wave covers keys
-    // 4 (PPW wave + i) + (lane >> 4): the rows of piece i are 4 i keys further on - a wave-uniform distance that goes into the scalar
-    // base -, the V swizzle depends on key & 3 = (lane >> 4) & 3 only, and the K swizzle pos ^ (key & 15) differs between the pieces
-    // by an XOR with 4 i on the 16-byte position (PPW = 4: key & 15 = 4 i + (lane >> 4)), i.e. by `^ 64 i` on the byte offset.
-    static_assert(PPW == 4, "the per-piece offsets below are derived for four pieces per wave");
-    const int l4 = lane >> 4, pos = lane & 15;
-    const u32 koff0 = (u32)l4 * (u32)k_stride0 * 2u + (u32)((pos ^ l4) * 16);
-    const u32 voff0 = (u32)l4 * (u32)v_stride0 * 2u + (u32)((pos ^ (l4 << 2)) * 16);
-    auto load_tile = [&](int t, int buf) {
-        const _Float16* kb_ = kg + ((size_t)t * BN + 4 * PPW * wave) * k_stride0;   // first key of this wave's pieces
-        const _Float16* vb_ = vg + ((size_t)t * BN + 4 * PPW * wave) * v_stride0;
-        const bool ragged = t * BN + BN > len_k;        // wave-uniform: only the last tile of a sequence
-#pragma unroll
-        for (int i = 0; i < PPW; ++i) {
-            if (ragged) {                                 // clamp the row to the sequence's last key (offsets from the TILE's base)
-                const int key = 4 * (PPW * wave + i) + l4;
-                int kc = len_k - 1 - t * BN;
-                kc = key < kc ? key : kc;
-                const u32 ko = (u32)kc * (u32)k_stride0 * 2u + (u32)((pos ^ (key & 15)) * 16);
-                const u32 vo = (u32)kc * (u32)v_stride0 * 2u + (u32)((pos ^ ((key & 3) << 2)) * 16);
-                dma16(ko, kg + (size_t)t * BN * k_stride0, lds_k + buf * KS_BYTES + (PPW * wave + i) * 1024);
-                dma16(vo, vg + (size_t)t * BN * v_stride0, lds_v + buf * VT_BYTES + (PPW * wave + i) * 1024);
-            } else {
-                // (the XOR is re-done per tile by an opaque statement: hoisted out of the loop - as the compiler does with the plain
-                //  expression - the three extra offsets are exactly what it spills to scratch once O is pinned)
-                u32 ko = koff0;
-                if (i > 0) asm volatile("v_xor_b32 %0, %1, %2" : "=v"(ko) : "n"(64 * i), "v"(koff0));
-                dma16(ko, kb_ + (size_t)(4 * i) * k_stride0, lds_k + buf * KS_BYTES + (PPW * wave + i) * 1024);
-                dma16(voff0, vb_ + (size_t)(4 * i) * v_stride0, lds_v + buf * VT_BYTES + (PPW * wave + i) * 1024);
-            }
-        }
-    };
-    auto tiles_landed = [&]() {                       // every wave's pieces: own queue drained, then the barrier
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-    };
+    // ---- tile staging by LDS-DMA (stage_fp16_tile): the k / v rows of this sequence and KV head
+    const TileRows ksrc = k_rows(k + (size_t)k_start * k_stride0 + (size_t)hkv * DH, k_stride0, lane);
+    const TileRows vsrc = v_rows(v + (size_t)k_start * v_stride0 + (size_t)hkv * DH, v_stride0, lane);
+    const u32 lds_k = lds_address(smem);
+    auto load_tile = [&](int t, int buf) { stage_fp16_tile(t, buf, len_k, wave, lds_k, ksrc, vsrc); };
 
     v16f oacc[4];
 #pragma unroll
@@ -208,12 +115,6 @@ __global__ __launch_bounds__(64 * NWV, QS_FLASH_OCC) void flash_fwd_kernel(const
         for (int s = 0; s < 8; ++s) asm volatile("" : "+v"(qf[s]));
     }
     tiles_landed();
-#ifdef QS_FLASH_STAGGER
-    // experiment: the two workgroups of a CU run identical code with identical timing and can settle in lockstep (both in
-    // their MFMA phase, then both in their VALU phase); delay every other workgroup by about half a tile
-    if ((blockIdx.x ^ blockIdx.y ^ blockIdx.z) & 1)
-        for (int i = 0; i < QS_FLASH_STAGGER; ++i) __builtin_amdgcn_s_sleep(16);
-#endif
 
 #ifdef QS_FLASH_TRACE
     unsigned ft[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -226,7 +127,7 @@ __global__ __launch_bounds__(64 * NWV, QS_FLASH_OCC) void flash_fwd_kernel(const
         // (round 6, measured and dropped: the pieces of tile t + 1 requested LATER - K behind Q.K^T, V behind the exponentials, where an
         //  LDS-DMA instruction should cost the wave fewer issue cycles than next to 16 ds_read_b128: equal at 64 x 1 024 tokens, -0.8 %
         //  at 4 x 8 192, profiles/round6_flash_ab6.txt)
-        if (!(QS_FLASH_DBG & 8) && t + 1 < ntiles) load_tile(t + 1, buf ^ 1);   // lands in the other buffers during this tile
+        if (t + 1 < ntiles) load_tile(t + 1, buf ^ 1);   // lands in the other buffers during this tile
         // causal: the workgroup's key range ends at its LAST row's diagonal; a wave whose 32 rows all lie before this tile
         // has nothing to add (every score masked) - it only takes part in the staging and the barrier
         // (R6: such tiles never reach this body - see the loops below)
@@ -235,154 +136,21 @@ __global__ __launch_bounds__(64 * NWV, QS_FLASH_OCC) void flash_fwd_kernel(const
             return;
         }
 
-        // ---------------- S^T = K Q^T : two blocks of 32 keys ----------------
-        // operand reads run one group of 4 MFMAs ahead of the matrix pipe (two register sets): issued as written, they
-        // leave the compiler no choice but counted lgkmcnt waits - with read-then-use in one loop body every MFMA sat behind
-        // a full LDS round trip
         v16f sacc[NKB];
-        if (!(QS_FLASH_DBG & 4)) {
-            h8 ka[2][4];
-            auto read_k = [&](int g, h8 (&dst)[4]) {       // group g = (kb = g >> 1, s = 4 (g & 1) .. +3)
-                const int key = 32 * (g >> 1) + li;
-                const uint8_t* krow = &s_k[buf][key * 256];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int sl = 4 * (g & 1) + j;
-                    dst[j] = *reinterpret_cast<const h8*>(krow + (((2 * sl + hi) ^ (key & 15)) * 16));
-                }
-            };
-            read_k(0, ka[0]);
-            read_k(1, ka[1]);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    // the first MFMA of a 32-key block starts from C = 0 (an inline constant operand: no 16-register zero
-                    // fill per block and tile)
-                    const v16f zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                    const bool first = (g & 1) == 0 && j == 0;
-                    sacc[g >> 1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ka[g & 1][j], qf[4 * (g & 1) + j], first ? zero16 : sacc[g >> 1], 0, 0, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                if (g + 2 < 4) read_k(g + 2, ka[g & 1]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        } else {
-#pragma unroll
-            for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) sacc[kb][r] = 0.f;
-            sacc[0][0] = (float)qf[0][0];
-        }
-        // A operands of O^T += V^T P^T by the LDS transpose read: a 16-lane group (16 consecutive dims, one lane half) reads
-        // the [4 keys][16 dims] block of the row-major tile - lane a supplies the 8-byte piece (key a>>2, dims 4(a&3)..+3) -
-        // and lane c receives column c = (dim c, keys 0..3), i.e. exactly its four k-slots of the PV MFMA.  Group d = the
-        // four MFMAs of output dims 32d .. 32d+31; group 0 is requested here, under the softmax.
-        const int ta = lane & 15, g1 = (lane >> 4) & 1;
-        const int tkey = 4 * hi + (ta >> 2);                       // key within a 16-key block; tkey & 3 == ta >> 2
-        h8 va[2][4];
-        auto read_v = [&](int d, h8 (&dst)[4]) {
-            const int chunk = (4 * d + 2 * g1 + ((ta & 3) >> 1)) ^ ((ta >> 2) << 2);   // V image swizzle: chunk ^ 4 (key & 3)
-            const uint8_t* vrow = &s_vt[buf][tkey * 256 + chunk * 16 + (ta & 1) * 8];
-#pragma unroll
-            for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-                for (int m = 0; m < 2; ++m) {
-                    const int kofs = (32 * kb + 16 * m) * 256;
-                    typedef short s4 __attribute__((ext_vector_type(4)));
-                    typedef __attribute__((address_space(3))) s4* lds_s4;
-                    const s4 t0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)(vrow + kofs));             // keys +0..3
-                    const s4 t1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)(vrow + kofs + 8 * 256));   // keys +8..11
-                    const v2u lo = __builtin_bit_cast(v2u, t0), hi2 = __builtin_bit_cast(v2u, t1);
-                    dst[2 * kb + m] = __builtin_bit_cast(h8, (v4u){lo.x, lo.y, hi2.x, hi2.y});
-                }
-        };
+        qk_tile(smem, bufc, lane, qf, sacc);
         QS_FT(1);                                                  // DMA issue + Q.K^T
-        if (!(QS_FLASH_DBG & 2)) read_v(0, va[0]);
+        h8 va[2][4];
+        read_v(smem, bufc, lane, 0, va[0]);                        // group 0 of the P.V operands, requested under the softmax
         __builtin_amdgcn_sched_barrier(0);
-        // sacc[kb][r] = score of (this lane's row, key t*64 + 32kb + (r&3) + 8(r>>2) + 4hi)
-        // masking only where the tile touches the diagonal or the end of the keys (wave-uniform test); raw scores
-        // stay unscaled, the scale is folded into the exponent's fma
+        // masking only where the tile touches the diagonal or the end of the keys (wave-uniform test); `limit` = the last key of
+        // the tile this lane's row may see
         const int tile_last = t * BN + BN - 1;
         const bool need_mask = tile_last >= len_k || (CAUSAL && tile_last > qt * BM + wave * 32 + shift);
-        float mx = -INFINITY;
-        if (need_mask) {
-#pragma unroll
-            for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int key = t * BN + 32 * kb + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                    const bool ok = key < len_k && (!CAUSAL || key <= row + shift);
-                    const float sv = ok ? sacc[kb][r] : -INFINITY;
-                    sacc[kb][r] = sv;
-                    mx = fmaxf(mx, sv);
-                }
-        } else {
-#pragma unroll
-            for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sacc[kb][r]);
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64)) * scale_log2;      // scale > 0: max commutes with it
-        // R6: lazy reference maximum (see the kernel's header)
-        const float m_new = R6 ? (mx > m_run + 8.0f ? mx : m_run) : fmaxf(m_run, mx);
-        const float m_use = m_new == -INFINITY ? 0.f : m_new;     // fully masked so far: keep exp2 arguments finite
-        const float alpha = __builtin_amdgcn_exp2f(m_run - m_use);                  // m_run = -inf -> 0
-        m_run = m_new;
-        // two scores per instruction where the ISA has a packed form (v_pk_fma_f32, v_pk_add_f32; the exponential has none):
-        // round 5, the key loop is as VALU-bound as it is MFMA-bound (HISTORY 5.5)
-        typedef float v2f __attribute__((ext_vector_type(2)));
-        const v2f sc2 = {scale_log2, scale_log2}, nm2 = {-m_use, -m_use};
-        v2f psum2 = {0.f, 0.f};
-        u32 pb[NKB][2][4];                                           // [kb][m]: 8 probabilities in B-operand order
-#pragma unroll
-        for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const v2f sv = {sacc[kb][8 * m + 2 * j], sacc[kb][8 * m + 2 * j + 1]};
-                    v2f pp = __builtin_elementwise_fma(sv, sc2, nm2);
-                    if (!(QS_FLASH_DBG & 1)) {
-                        pp[0] = __builtin_amdgcn_exp2f(pp[0]);      // -inf stays -inf
-                        pp[1] = __builtin_amdgcn_exp2f(pp[1]);
-                    }
-                    psum2 += pp;
-                    pb[kb][m][j] = pack_h2(pp[0], pp[1]);
-                }
-        const float psum = psum2[0] + psum2[1];
-        l_run = l_run * alpha + psum;
-        // (R6: marked unlikely - with the lazy maximum it is the first tile and jumps of more than 2^8.  The not-taken path must not
-        //  carry register copies of the 64 accumulators: see the loop structure below)
-        if (R6 ? __builtin_expect(__any(alpha != 1.0f), 0) : __any(alpha != 1.0f)) {   // the running max moved for some row of this wave
-#pragma unroll
-            for (int d = 0; d < 4; ++d)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) oacc[d][r] *= alpha;
-        }
-
+        auto limit = [&] { return (CAUSAL && row + shift < len_k - 1 ? row + shift : len_k - 1) - t * BN; };
+        u32 pb[NKB][2][4];
+        softmax_tile<R6>(sacc, need_mask, limit, lane, scale_log2, m_run, l_run, oacc, pb);   // R6: lazy reference maximum (see the kernel's header)
         QS_FT(2);                                                  // mask + softmax + O rescale
-        // ---------------- O^T += V^T P^T ----------------
-        if (QS_FLASH_DBG & 2) {
-            oacc[0][0] += __builtin_bit_cast(float, pb[0][0][0] ^ pb[NKB - 1][1][3]);
-        } else {
-            read_v(1, va[1]);
-            __builtin_amdgcn_sched_barrier(0);
-            static_for<4>([&](auto dc) {
-                constexpr int d = decltype(dc)::value;
-#pragma unroll
-                for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-                    for (int m = 0; m < 2; ++m) {
-                        const h8 pbv = __builtin_bit_cast(h8, (v4u){pb[kb][m][0], pb[kb][m][1], pb[kb][m][2], pb[kb][m][3]});
-                        oacc[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(va[d & 1][2 * kb + m], pbv, oacc[d], 0, 0, 0);
-                    }
-                __builtin_amdgcn_sched_barrier(0);
-                if (d + 2 < 4) read_v(d + 2, va[d & 1]);
-                __builtin_amdgcn_sched_barrier(0);
-            });
-        }
+        pv_tile(smem, bufc, lane, va, pb, oacc);
         QS_FT(3);                                                  // P.V
         tiles_landed();
         QS_FT(4);                                                  // wait for the next tile + barrier
@@ -407,7 +175,7 @@ __global__ __launch_bounds__(64 * NWV, QS_FLASH_OCC) void flash_fwd_kernel(const
             ++t;
         }
         for (; t < ntiles; ++t) {
-            if (!(QS_FLASH_DBG & 8) && t + 1 < ntiles) load_tile(t + 1, (t + 1) & 1);
+            if (t + 1 < ntiles) load_tile(t + 1, (t + 1) & 1);
             tiles_landed();
         }
     } else {
@@ -421,7 +189,7 @@ __global__ __launch_bounds__(64 * NWV, QS_FLASH_OCC) void flash_fwd_kernel(const
     }
 #endif
 
-    // ---- epilogue: normalise, fp16, 8-byte stores (4 consecutive dims per accumulator quad) ---------------------------
+    // ---- epilogue: normalise, fp16 ----------------------------------------------------------------------------------------
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     const float inv = l_tot > 0.f ? 1.0f / l_tot : 0.f;
     // (the row index is re-derived from a lane id the compiler cannot merge with the one above: kept alive across the key loop
@@ -430,37 +198,14 @@ __global__ __launch_bounds__(64 * NWV, QS_FLASH_OCC) void flash_fwd_kernel(const
     // whole-row stores need 16-byte alignment of every row (wave-uniform)
     const bool rows16 = R6 && (o_stride0 % 8 == 0) && ((reinterpret_cast<uintptr_t>(out) & 15) == 0);
     if (rows16) {
-        // Round 6: O goes through LDS and leaves as WHOLE ROWS.  In the accumulator layout a lane owns one query row, so the direct
-        // form below is 16 stores of 8 bytes per lane at a row stride (o_stride0, 8 KiB for 32 heads): every store instruction touches
-        // 64 different cache lines, and the store tail of a workgroup lasts ~2 key tiles (MI355X_MICROARCH.md: "attention epilogue
-        // store tail ... store-ISSUE-bound").  Here a wave writes its 32 x 128 fp16 block into its own 8.5 KiB of the (dead) K / V
-        // buffers - row stride 272 B: the rows of a half-wave fall on banks 4 li, two-way conflicts at most - and reads it back 16
-        // bytes per lane, 16 lanes per row: 8 stores per lane, each instruction 4 complete 256-byte rows.  No barrier: every wave has
-        // passed the last tile's barrier (all reads of the buffers are over) and touches only its own block; the LDS serves a wave's
-        // accesses in order.
-        constexpr int OST = 272;
-        uint8_t* const so = smem + wave * (32 * OST);
-        const int li_e = (int)(fresh_lane_id() & 31u), hi_e = (int)(fresh_lane_id() >> 5);
-        static_for<4>([&](auto dc) {
-            constexpr int d = decltype(dc)::value;
-            static_for<4>([&](auto rc) {
-                constexpr int rq = decltype(rc)::value;
-                h4 o;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) o[j] = (_Float16)(oacc[d][4 * rq + j] * inv);
-                *reinterpret_cast<h4*>(so + li_e * OST + (32 * d + 8 * rq + 4 * hi_e) * 2) = o;
-            });
-        });
-        const int lid = (int)fresh_lane_id(), rr = lid >> 4, cc = lid & 15;
+        // out through LDS as whole 256-byte rows (store_rows_through_lds): row r of this wave is query row row0 + r of head h
         const int row0 = qt * BM + wave * 32;
-        _Float16* const ob = out + (size_t)(q_start + row0) * o_stride0 + (size_t)h * DH + cc * 8;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int r = 4 * j + rr;
-            const v4u x = *reinterpret_cast<const v4u*>(so + r * OST + cc * 16);
-            if (row0 + r < len_q && (!(QS_FLASH_DBG & 32) || x.x == 0x12345678u)) *reinterpret_cast<v4u*>(ob + (size_t)r * o_stride0) = x;
-        }
+        _Float16* const ob = out + (size_t)(q_start + row0) * o_stride0 + (size_t)h * DH;
+        store_rows_through_lds(smem, wave, oacc, inv, [&](int r, int cc, const v4u& x) {
+            if (row0 + r < len_q) *reinterpret_cast<v4u*>(ob + (size_t)r * o_stride0 + cc * 8) = x;
+        });
     } else if (row_e < len_q) {
+        // 8-byte stores (4 consecutive dims per accumulator quad)
         _Float16* op = out + (size_t)(q_start + row_e) * o_stride0 + (size_t)h * DH;
         static_for<4>([&](auto dc) {
             constexpr int d = decltype(dc)::value;
@@ -512,24 +257,13 @@ extern "C" int qs_flash_attn_varlen_fwd(const void* q, const void* k, const void
     if (batch == 0 || max_seqlen_q == 0) return QS_OK;
     const float scale_log2 = softmax_scale * 1.4426950408889634f;
     dim3 grid(num_heads, (max_seqlen_q + BM - 1) / BM, batch);
-#ifndef QS_FLASH_LDSPAD
-#define QS_FLASH_LDSPAD 0
-#endif
-    constexpr int SMEM = 2 * KS_BYTES + 2 * VT_BYTES + QS_FLASH_LDSPAD;   // (pad: occupancy experiments)
-    static bool configured_dev[QS_MAX_DEVICES] = {};   // the attribute belongs to the (kernel, device) pair
-    bool& configured = configured_dev[qs_device_slot()];
-    if (!configured) {
-        hipError_t e1 = hipSuccess;
-        for (const void* fn : {reinterpret_cast<const void*>(flash_fwd_kernel<true, 0>), reinterpret_cast<const void*>(flash_fwd_kernel<true, 1>),
-                               reinterpret_cast<const void*>(flash_fwd_kernel<false, 0>), reinterpret_cast<const void*>(flash_fwd_kernel<false, 1>)}) {
-            const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-            if (e != hipSuccess) e1 = e;
-        }
-        if (e1 != hipSuccess) {
-            qs_set_error("flash_attn_varlen: cannot reserve %d bytes of LDS", SMEM);
-            return (int)e1;
-        }
-        configured = true;
+    constexpr int SMEM = 2 * KS_BYTES + 2 * VT_BYTES;   // dynamic LDS: K [2][16 KiB], then V [2][16 KiB] (flash_tile.h)
+    static bool lds_reserved[QS_MAX_DEVICES] = {};
+    if (const hipError_t e = qs_reserve_lds({reinterpret_cast<const void*>(flash_fwd_kernel<true, 0>), reinterpret_cast<const void*>(flash_fwd_kernel<true, 1>),
+                                             reinterpret_cast<const void*>(flash_fwd_kernel<false, 0>), reinterpret_cast<const void*>(flash_fwd_kernel<false, 1>)},
+                                            SMEM, lds_reserved); e != hipSuccess) {
+        qs_set_error("flash_attn_varlen: cannot reserve %d bytes of LDS", SMEM);
+        return (int)e;
     }
 #define QS_FL(C, P)                                                                                                    \
     hipLaunchKernelGGL((flash_fwd_kernel<C, P>), grid, dim3(64 * NWV), SMEM, (hipStream_t)stream, (const _Float16*)q,   \

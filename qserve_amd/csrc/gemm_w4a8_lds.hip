@@ -275,16 +275,10 @@ int launch_pair(const int8_t* A, const uint8_t* W, const int8_t* zeros, const in
                 hipStream_t stream) {
     auto kern = w4a8_gemm_pair<MT, MODE, OUTK, DBG>;
     const size_t smem = (size_t)2 * NS * (16 * MT * 128) + 4 * NS * WBYTES + 4 * NS * 256;
-    static bool configured_dev[QS_MAX_DEVICES] = {};   // the attribute belongs to the (kernel, device) pair
-    bool& configured = configured_dev[qs_device_slot()];
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) {
-            qs_set_error("w4a8 gemm (lds): cannot reserve %zu bytes of LDS: %s", smem, hipGetErrorString(e));
-            return (int)e;
-        }
-        configured = true;
+    static bool lds_reserved[QS_MAX_DEVICES] = {};   // per instantiation (= kernel) and device
+    if (const hipError_t e = qs_reserve_lds({reinterpret_cast<const void*>(kern)}, (int)smem, lds_reserved); e != hipSuccess) {
+        qs_set_error("w4a8 gemm (lds): cannot reserve %zu bytes of LDS: %s", smem, hipGetErrorString(e));
+        return (int)e;
     }
     dim3 grid(N / 128, (M + 16 * MT - 1) / (16 * MT));
     hipLaunchKernelGGL(kern, grid, dim3(256), smem, stream, A, W, zeros, scales8,

@@ -47,7 +47,6 @@ constexpr int SC_OFF = 160 * 1024 - SC_BYTES;
 
 
 typedef __attribute__((address_space(3))) void* lptr_t;
-typedef u32 v2u __attribute__((ext_vector_type(2)));
 
 // QS_RING_TRACE builds (scripts/trace_gemm.py; never the shipped library): per-wave timeline into a caller buffer
 #ifdef QS_RING_TRACE

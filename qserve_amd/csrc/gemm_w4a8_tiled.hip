@@ -35,7 +35,6 @@ constexpr int WSTAGE = BN * 32;            // packed weight bytes per stage = 8 
 
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
-typedef u32 v2u __attribute__((ext_vector_type(2)));
 
 template <int N>
 __device__ __forceinline__ void wait_vm() {
@@ -607,16 +606,10 @@ int launch_tiled(const int8_t* A, const uint8_t* W, const int8_t* zeros, const i
     auto kern = w4a8_gemm_tiled<MT, MODE, OUTK, DBG>;
     constexpr int BM = 32 * MT;
     const size_t smem = (size_t)NS * (BM * 64 + WSTAGE + 512) + 3072;   // rings + the staged epilogue operands (the epilogue's 18 KiB of staging rows alias the rings)
-    static bool configured_dev[QS_MAX_DEVICES] = {};   // the attribute belongs to the (kernel, device) pair
-    bool& configured = configured_dev[qs_device_slot()];
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) {
-            qs_set_error("w4a8 gemm (tiled): cannot reserve %zu bytes of LDS: %s", smem, hipGetErrorString(e));
-            return (int)e;
-        }
-        configured = true;
+    static bool lds_reserved[QS_MAX_DEVICES] = {};   // per instantiation (= kernel) and device
+    if (const hipError_t e = qs_reserve_lds({reinterpret_cast<const void*>(kern)}, (int)smem, lds_reserved); e != hipSuccess) {
+        qs_set_error("w4a8 gemm (tiled): cannot reserve %zu bytes of LDS: %s", smem, hipGetErrorString(e));
+        return (int)e;
     }
     const int nbm = (M + BM - 1) / BM;
     const int ntiles = nbm * (N / BN);

@@ -39,7 +39,6 @@ constexpr int APAIR = BM * 128;            // activation bytes per stage pair (1
 constexpr int NA2 = APAIR / 4096;          // 4 KiB all-thread DMA instructions per activation pair
 
 typedef __attribute__((address_space(3))) void* lptr_t;
-typedef u32 v2u __attribute__((ext_vector_type(2)));
 
 template <int N>
 __device__ __forceinline__ void wait_vm() {
@@ -61,17 +60,7 @@ __device__ __forceinline__ void raw_barrier() {
 }
 #define QS_PIN() __builtin_amdgcn_sched_barrier(0)
 
-// compile-time loop: f(std::integral_constant<int, 0>{}), ..., f(<N-1>) - the accumulator register numbers of the asm MFMAs
-// must be immediates
-template <class F, int... I>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
-
+// (static_for of common.h below: the accumulator register numbers of the asm MFMAs must be immediates)
 // acc(mt, cl) = a[(4 mt + cl) 4 .. + 3].  FIRST: the tile's first stage writes A x B + 0 (no zero-fill of 256 registers).
 // No hazard padding is needed inside: the operands are LDS read results or were built a whole stage earlier (the disassembly
 // contract in tests/test_kernel_contracts.py checks that no VALU write of a source precedes an MFMA by fewer than two
@@ -590,16 +579,10 @@ int launch_wide(const int8_t* A, const uint8_t* W, const int8_t* zeros, const in
                 hipStream_t stream) {
     auto kern = w4a8_gemm_wide<MODE, OUTK, DBG>;
     const size_t smem = (size_t)NS * (BM * 64 + WSTAGE + 512);   // (the epilogue's staging rows alias activation pair slot 2)
-    static bool configured_dev[QS_MAX_DEVICES] = {};   // the attribute belongs to the (kernel, device) pair
-    bool& configured = configured_dev[qs_device_slot()];
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) {
-            qs_set_error("w4a8 gemm (wide): cannot reserve %zu bytes of LDS: %s", smem, hipGetErrorString(e));
-            return (int)e;
-        }
-        configured = true;
+    static bool lds_reserved[QS_MAX_DEVICES] = {};   // per instantiation (= kernel) and device
+    if (const hipError_t e = qs_reserve_lds({reinterpret_cast<const void*>(kern)}, (int)smem, lds_reserved); e != hipSuccess) {
+        qs_set_error("w4a8 gemm (wide): cannot reserve %zu bytes of LDS: %s", smem, hipGetErrorString(e));
+        return (int)e;
     }
     const int nbm = (M + BM - 1) / BM;
     const int ntiles = nbm * (N / BN);

@@ -25,7 +25,8 @@ pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not ava
 def asm(tmp_path_factory):
     out = {}
     d = tmp_path_factory.mktemp("asm")
-    for name in ("attention_mfma", "attention_mfma8", "gemm_w4a8_ring", "gemm_w4a8_tiled", "gemm_w4a8_wide", "flash_prefill"):
+    for name in ("attention_mfma", "attention_mfma8", "gemm_w4a8_ring", "gemm_w4a8_tiled", "gemm_w4a8_wide", "flash_prefill",
+                 "append_attention"):
         dst = d / (name + ".s")
         r = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-S", "--cuda-device-only", "-o", str(dst),
                             os.path.join(CSRC, name + ".hip")], capture_output=True, text=True)
@@ -103,7 +104,34 @@ def test_flash_prefill_key_loop_waits_and_copies(asm):
         assert not [1 for mn, _, _ in ins if mn.startswith("scratch_")]
 
 
-@pytest.mark.parametrize("unit", ["attention_mfma", "attention_mfma8", "gemm_w4a8_ring", "gemm_w4a8_tiled", "gemm_w4a8_wide", "flash_prefill"])
+def test_append_attention_key_loop_and_occupancy(asm):
+    """Append attention runs the tile core of the prefill provider (flash_tile.h) and rests on the same properties: the key loop
+    unrolled over the two LDS buffers holds the 32 MFMAs of each of its two tiles, no register copies of the O accumulators and
+    no scratch access, and both instantiations (KV4, KV8) fit two workgroups per CU.  The loop has a mid-loop exit (an odd tile
+    count leaves from the middle), so it is located as the smallest label .. backward-branch span that holds 64 MFMAs."""
+    text = asm["append_attention"]
+    ks = {n: b for n, b in kernels(text).items() if "append_attention_kernel" in n}
+    assert len(ks) == 2
+    for name, body in ks.items():
+        lines = body.splitlines()
+        labels = {m.group(1): i for i, l in enumerate(lines) for m in [re.match(r"\s*(\.LBB\d+_\d+):", l)] if m}
+        spans = []
+        for i, l in enumerate(lines):
+            m = re.search(r"s_c?branch\w*\s+(\.LBB\d+_\d+)\b", l)
+            if m and labels.get(m.group(1), i) < i:
+                ins = _instructions("\n".join(lines[labels[m.group(1)]:i + 1]))
+                if sum(1 for mn, _, _ in ins if mn.startswith("v_mfma")) >= 64:
+                    spans.append(ins)
+        assert spans, f"{name}: no loop with the MFMAs of two tiles"
+        ins = min(spans, key=len)
+        assert sum(1 for mn, _, _ in ins if mn.startswith("v_mfma_f32_32x32x16_f16")) == 64, name
+        assert not [1 for mn, _, _ in ins if mn.startswith("v_mov_b64")], f"{name}: accumulator copies inside the key loop"
+        assert "scratch_" not in body, f"{name}: scratch access"
+        assert meta(text, name, "ScratchSize") == 0 and meta(text, name, "Occupancy") == 2, name
+
+
+@pytest.mark.parametrize("unit", ["attention_mfma", "attention_mfma8", "gemm_w4a8_ring", "gemm_w4a8_tiled", "gemm_w4a8_wide", "flash_prefill",
+                                  "append_attention"])
 def test_hot_path_kernels_do_not_spill(asm, unit):
     text = asm[unit]
     names = re.findall(r"^\s*\.amdhsa_kernel (\S+)", text, re.M)
