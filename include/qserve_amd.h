@@ -236,6 +236,9 @@ int qs_w4a8_gemm_plan(int per_group, int M, int N, int K, int* plan5);
  *                     length_per_sample[bi]-1 : timestep), every sequence has `timestep` CACHED tokens and the new token
  *                     is written at position `timestep`
  *   out half [B,H,Dh] contiguous (the reference returns torch::empty_like(q))
+ * Layout contract (QS_EINVAL otherwise, checked before any device call): q, k, v and out 16-byte aligned; q_stride0 and
+ * kv_stride0 multiples of 8 elements, q_stride0 >= H*Dh, kv_stride0 >= Hkv*Dh.  Any such stride is served (padded rows, views
+ * into wider buffers, k and v in buffers of their own) - but k and v share ONE token stride.
  * Page layout (kvCacheUtils.h:47-126): [Hkv][tokens_per_block][Dh'] data, then half scale[Hkv][tpb], then
  * half zero[Hkv][tpb]; Dh' = size_per_token / Hkv bytes.
  * Side effect: quantises the new token's rotated K and V into the page of position length-1.
@@ -350,6 +353,14 @@ int qs_silu_and_mul_quant(int8_t* out, const void* input, void* input_sum, void*
  *   out half [total_q, H, 128]   token stride o_stride0
  *   cu_seqlens_q / cu_seqlens_k int32 [batch+1] (device).  causal: bottom-right aligned when lengths differ (v2.1+).
  * head_dim must be 128; dropout, ALiBi, sliding windows and returning probabilities are not provided.
+ * Layout contract (QS_EINVAL otherwise, checked before any device call): heads contiguous (element strides (stride0, 128, 1));
+ *   q, k, v   16-byte aligned; q_stride0, k_stride0, v_stride0 multiples of 8 elements, >= the token's heads (H*128 resp.
+ *             Hkv*128) and < 2^24.  q, k and v may live in three buffers with three strides.  Every such stride is served with the
+ *             same bits; K strides that are multiples of 128 elements (whole heads per token: packed qkv, contiguous k) take the
+ *             one-register tile offsets of the key loop, all others its general per-piece offsets;
+ *   out       8-byte aligned, o_stride0 a multiple of 4 elements, >= H*128 and < 2^24; rows are written 16 bytes at a time where
+ *             out is 16-byte aligned and o_stride0 a multiple of 8, 8 bytes at a time otherwise.  Nothing outside the rows'
+ *             H*128 elements is written.
  * ---------------------------------------------------------------------------------------------------------- */
 int qs_flash_attn_varlen_fwd(const void* q, const void* k, const void* v, void* out, const int32_t* cu_seqlens_q,
                              const int32_t* cu_seqlens_k, int batch, int num_heads, int num_kv_heads, int head_dim,
@@ -440,7 +451,10 @@ int qs_debug_flash_variant(int variant);
  *                      kernels' values), positions >= past in fp16 from the ALREADY ROTATED qkv (rotated k, raw v).  fp32 softmax,
  *                      scale 1/sqrt(128), out fp16 [T, H, 128] with row stride out_stride0 (elements).  The two calls touch
  *                      disjoint page slots: no ordering is needed between them.  past = 0 is the prefill attention, n = 1 the
- *                      decode attention.  qkv and out 16-byte aligned, strides multiples of 8 elements.
+ *                      decode attention.  Layout contract (QS_EINVAL otherwise, checked before any device call): qkv and out
+ *                      16-byte aligned; qkv_stride0 a multiple of 8 elements, >= (H + 2 Hkv) * 128 and < 2^24; out_stride0 a
+ *                      multiple of 8, >= H * 128.  Every such stride is served with the same bits (padded rows, views into
+ *                      wider buffers); nothing outside the rows' H * 128 elements is written.
  *   qs_append_attention_plan  pure (no device access): plan3 = {tokens per query tile, query tiles per sequence at max_seqlen_q,
  *                      waves per workgroup} of the launch the arguments would get; all zero for an empty launch.  One workgroup
  *                      serves a query tile of ONE KV head with all H / Hkv query heads: rows = (token, head-in-group) pairs.

@@ -20,6 +20,9 @@ def single_query_attention(q, k, v, kv_pointers, length_per_sample, alibi_slopes
         raise RuntimeError("k and v must have stride(2) == 1 and stride(1) == head_dim")
     if not (q.stride(2) == 1 and q.stride(1) == headdim):
         raise RuntimeError("q must have stride(2) == 1 and stride(1) == head_dim")
+    if k.stride(0) != v.stride(0):
+        # (the C entry takes ONE kv_stride0 - include/qserve_amd.h; the reference passes views of one packed qkv buffer)
+        raise RuntimeError("k and v must have the same token stride (views of one qkv buffer, or equally padded buffers)")
     if length_per_sample is not None:
         expect(length_per_sample, torch.int32, "length_per_sample")
         if tuple(length_per_sample.shape) != (batch,):

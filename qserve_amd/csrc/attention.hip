@@ -713,6 +713,13 @@ int single_query_attention(const void* q, const void* k, const void* v, const in
     QS_REQUIRE(size_per_token == num_kv_heads * dhb, "single_query_attention: size_per_token=%d, expected %d",
                size_per_token, num_kv_heads * dhb);
     QS_REQUIRE(max_blocks > 0 && memory_max_seqlen > 0, "single_query_attention: bad max_blocks / memory_max_seqlen");
+    // the layouts the kernels serve (include/qserve_amd.h): the new token's rows are fetched in 4-byte pieces by LDS-DMA, the fused
+    // quantiser stores `out` 16 bytes at a time - one rule for every kernel family, checked in front of every device call
+    QS_REQUIRE(q_stride0 % 8 == 0 && kv_stride0 % 8 == 0 && q_stride0 >= (int64_t)num_heads * 128 && kv_stride0 >= (int64_t)num_kv_heads * 128,
+               "single_query_attention: token strides must hold the token's heads and keep 16-byte alignment");
+    QS_REQUIRE(((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v) |
+                 reinterpret_cast<uintptr_t>(out)) & 15) == 0,
+               "single_query_attention: q, k, v and out must be 16-byte aligned");
     if (batch == 0) return QS_OK;
     const AttnPlan plan = plan_attention(batch, num_heads, num_kv_heads, max_blocks, timestep, int4_kv_cache, quant != nullptr,
                                          g_attn_variant);

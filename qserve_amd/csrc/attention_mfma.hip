@@ -925,8 +925,12 @@ __global__ __launch_bounds__(NWT * 64, 4) void decode_attention_mfma_kernel(
                 if (!p0 && i0 < hidden) raw[0] = reinterpret_cast<const v4u*>(&s_meta[0][0][0])[(i0 - own_lo) >> 3];
                 if (!p1 && i1 < hidden) raw[1] = reinterpret_cast<const v4u*>(&s_meta[0][0][0])[(i1 - own_lo) >> 3];
             }
-            float* const sm = reinterpret_cast<float*>(&s_kv[0]);                // 2 x 4 floats (the rings are dead)
-            float amax = 0.f, sum = 0.f;
+            // The statistics in quant_kernel's order (row_ops.h quant_row<2, 4, 4> / reduce_max_blocksum): the row sum is DEFINED block by
+            // block - chunk set c of wave w is the 512-element block 4 c + w: one sequential chain per chunk, the wave butterfly per
+            // block, then one more butterfly over the (at most 8) block sums, lane b = block b, -0.0 beyond the row.  (Until round 6 one
+            // chain ran over both chunks and the waves were added left to right: the same bits for rows of up to 2 blocks only.)
+            float* const sm = reinterpret_cast<float*>(&s_kv[0]);                // 4 + 2 x 4 floats (the rings are dead)
+            float amax = 0.f, sum[2] = {0.f, 0.f};                               // (a chunk beyond the row adds +0 to its block)
             if (tid2 < 256) {
 #pragma unroll
                 for (int c = 0; c < 2; ++c) {
@@ -936,26 +940,30 @@ __global__ __launch_bounds__(NWT * 64, 4) void decode_attention_mfma_kernel(
 #pragma unroll
                         for (int j = 0; j < 8; ++j) {
                             const float f = (float)vv[j];
-                            sum += f;
+                            sum[c] += f;
+                            QS_SEQ(sum[c]);
                             amax = fmaxf(amax, fabsf(f));
                         }
                     }
                 }
                 amax = wave_max(amax);
-                if (qrowsum) sum = wave_sum(sum);
+                if (qrowsum) {
+                    sum[0] = wave_sum(sum[0]);
+                    sum[1] = wave_sum(sum[1]);
+                }
                 if ((tid2 & 63) == 0) {
                     sm[tid2 >> 6] = amax;
-                    sm[4 + (tid2 >> 6)] = sum;
+                    sm[4 + (tid2 >> 6)] = sum[0];
+                    sm[8 + (tid2 >> 6)] = sum[1];
                 }
             }
             __syncthreads();
             if (tid2 < 256) {
-                float r = sm[0], s2 = qrowsum ? sm[4] : 0.f;
+                float r = sm[0];
 #pragma unroll
-                for (int w = 1; w < 4; ++w) {
-                    r = fmaxf(r, sm[w]);
-                    if (qrowsum) s2 = s2 + sm[4 + w];
-                }
+                for (int w = 1; w < 4; ++w) r = fmaxf(r, sm[w]);
+                float s2 = 0.f;
+                if (qrowsum && tid2 < 64) s2 = wave_sum(tid2 < (hidden + 511) / 512 ? sm[4 + tid2] : -0.0f);   // (wave 0: wave-uniform)
                 if (tid2 == 0) {
                     qscale[b] = __float2half_rn(r / 127.0f);                     // fused_kernels.cu:72
                     if (qrowsum) qrowsum[b] = __float2half_rn(s2);                     // :121

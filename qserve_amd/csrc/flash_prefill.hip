@@ -250,8 +250,19 @@ extern "C" int qs_flash_attn_varlen_fwd(const void* q, const void* k, const void
         qs_set_error("flash_attn_varlen: head_dim=%d, only 128 is supported (the reference's models)", head_dim);
         return QS_ENOSUP;
     }
+    // The layouts the kernels serve (include/qserve_amd.h) - everything else is refused HERE, in front of every device call:
+    // q / k / v rows are read 16 bytes at a time (k / v by LDS-DMA with 32-bit lane offsets of up to 64 rows), out is written 16 bytes
+    // at a time where its base and stride allow it and 8 bytes at a time otherwise.
     QS_REQUIRE(q_stride0 % 8 == 0 && k_stride0 % 8 == 0 && v_stride0 % 8 == 0 && o_stride0 % 4 == 0,
                "flash_attn_varlen: token strides must keep 16-byte alignment");
+    QS_REQUIRE(q_stride0 >= (int64_t)num_heads * DH && o_stride0 >= (int64_t)num_heads * DH && k_stride0 >= (int64_t)num_kv_heads * DH &&
+                   v_stride0 >= (int64_t)num_kv_heads * DH,
+               "flash_attn_varlen: a token stride is shorter than the token's heads");
+    QS_REQUIRE(q_stride0 < (1 << 24) && k_stride0 < (1 << 24) && v_stride0 < (1 << 24) && o_stride0 < (1 << 24),
+               "flash_attn_varlen: token strides must be below 2^24 elements");
+    QS_REQUIRE(((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v)) & 15) == 0 &&
+                   (reinterpret_cast<uintptr_t>(out) & 7) == 0,
+               "flash_attn_varlen: q, k, v must be 16-byte aligned and out 8-byte aligned");
     QS_REQUIRE(max_seqlen_q >= 0 && max_seqlen_k >= 0, "flash_attn_varlen: negative max_seqlen");
     QS_REQUIRE(softmax_scale > 0.f, "flash_attn_varlen: softmax_scale must be positive");
     if (batch == 0 || max_seqlen_q == 0) return QS_OK;

@@ -58,7 +58,10 @@ __device__ __forceinline__ void tiles_landed() {      // every wave's pieces: ow
 // and V (round 6; were PPW each).  Piece i of a wave covers keys 4 (PPW wave + i) + (lane >> 4): the rows of piece i are 4 i keys
 // further on - a wave-uniform distance that goes into the scalar base -, the V swizzle depends on key & 3 = (lane >> 4) & 3 only,
 // and the K swizzle pos ^ (key & 15) differs between the pieces by an XOR with 4 i on the 16-byte position (PPW = 4:
-// key & 15 = 4 i + (lane >> 4)), i.e. by `^ 64 i` on the byte offset.
+// key & 15 = 4 i + (lane >> 4)), i.e. by `^ 64 i` on the byte offset - ON THE SUMMED OFFSET only where the row part
+// (lane >> 4) * stride * 2 leaves the low 8 bits alone, i.e. for stride % 128 == 0 (whole heads per token: every layout of the
+// engine).  Any other K stride (a padded row, a view into a wider buffer) takes the per-piece offsets of stage_fp16_tile's general
+// path.  V has no per-piece term: any stride.
 struct TileRows {
     const _Float16* base;
     int64_t stride;
@@ -77,10 +80,11 @@ __device__ __forceinline__ void stage_fp16_tile(int t, int buf, int len_k, int w
     const u32 lds_v = lds_k + 2 * KS_BYTES;
     const _Float16* kb_ = ks.base + ((size_t)t * BN + 4 * PPW * wave) * ks.stride;   // first key of this wave's pieces
     const _Float16* vb_ = vs.base + ((size_t)t * BN + 4 * PPW * wave) * vs.stride;
-    const bool ragged = t * BN + BN > len_k;        // wave-uniform: only the last tile of a sequence
+    // wave-uniform: the last tile of a sequence, or K rows whose stride the one-register form of k_rows cannot serve (scalar test)
+    const bool ragged = t * BN + BN > len_k || (ks.stride & 127) != 0;
 #pragma unroll
     for (int i = 0; i < PPW; ++i) {
-        if (ragged) {                                 // clamp the row to the sequence's last key (offsets from the TILE's base)
+        if (ragged) {                                 // general per-piece offsets, the row clamped to the sequence's last key (from the TILE's base)
             // (from a lane id of its own: derived from the caller's `lane`, the per-piece offsets of this once-per-workgroup path
             //  are loop invariants the compiler keeps in - and spills from - registers across the key loop)
             const int fl = (int)fresh_lane_id(), l4r = fl >> 4, posr = fl & 15;

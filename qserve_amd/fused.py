@@ -100,6 +100,8 @@ def single_query_attention_quant(q, k, v, kv_pointers, length_per_sample, quant_
         raise RuntimeError("k and v must have stride(2) == 1 and stride(1) == head_dim")
     if not (q.stride(2) == 1 and q.stride(1) == headdim):
         raise RuntimeError("q must have stride(2) == 1 and stride(1) == head_dim")
+    if k.stride(0) != v.stride(0):
+        raise RuntimeError("k and v must have the same token stride (views of one qkv buffer, or equally padded buffers)")
     if length_per_sample is not None:
         expect(length_per_sample, torch.int32, "length_per_sample")
     if quant_out.numel() != q.size(0) * nheads * headdim:

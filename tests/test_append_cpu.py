@@ -89,7 +89,7 @@ def test_plan_is_pure_and_mirrored(built_lib):
     buf = (C.c_int * 3)()
     for batch in (0, 1, 4, 64):
         for n in (0, 1, 4, 31, 32, 33, 128, 129, 512, 8192):
-            for H, Hkv in ((32, 8), (8, 2), (4, 4), (8, 1), (6, 2), (28, 4), (64, 8)):
+            for H, Hkv in ((32, 8), (8, 2), (4, 4), (8, 1), (6, 2), (12, 4), (5, 1), (7, 1), (16, 8), (28, 4), (64, 8)):
                 assert lib.qs_append_attention_plan(batch, n, H, Hkv, C.cast(buf, C.c_void_p)) == 0
                 got = dict(tile_tokens=buf[0], q_tiles=buf[1], waves=buf[2])
                 assert got == append_attention_plan(batch, n, H, Hkv)
@@ -101,6 +101,7 @@ def test_plan_is_pure_and_mirrored(built_lib):
                 assert got["tile_tokens"] >= 1 and got["tile_tokens"] * G <= rows
                 assert got["tile_tokens"] == rows // G                   # no row of the workgroup idle that a token could use
                 assert (got["q_tiles"] - 1) * got["tile_tokens"] < n <= got["q_tiles"] * got["tile_tokens"]
+                assert got == dict(tile_tokens=128 // G, q_tiles=-(-n // (128 // G)), waves=4)   # every group size 1 .. 8, stated outright
     assert lib.qs_append_attention_plan(1, 4, 8, 3, C.cast(buf, C.c_void_p)) == -1 and list(buf) == [0, 0, 0]
     assert lib.qs_append_attention_plan(1, 4, 18, 2, C.cast(buf, C.c_void_p)) == -2
     assert lib.qs_append_attention_plan(1, 4, 8, 2, None) == -1

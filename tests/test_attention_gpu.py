@@ -356,18 +356,44 @@ def test_decode_valu_kernel_still_correct(gpu, int4):
 
 
 
-@pytest.mark.parametrize("int4", [True, False], ids=["kv4", "kv8"])
-@pytest.mark.parametrize("with_sum", [True, False])
-@pytest.mark.parametrize("B,H,Hkv,L", [(64, 32, 8, 1033), (5, 8, 2, 300), (3, 8, 8, 130), (2, 16, 2, 70), (8, 32, 8, 4000),
-                                      (4100, 8, 2, 70)])   # (more sequences than the hand-over workspace holds: the pair runs)
-def test_attention_quant_fusion_is_bit_identical_to_the_pair(gpu, B, H, Hkv, L, with_sum, int4):
-    """qserve_amd.fused.single_query_attention_quant == single_query_attention ; invoke_quant(_fuse_sum): the fp16
-    output, the int8 row, the fp16 scale (and row sum) and every cache byte, bit for bit - in-kernel fusion (KV4, no KV
-    split: the workgroup of the last KV head finishes the row from the others' tagged granules), split-KV launches (B=8,
-    L=4000), batches beyond the hand-over workspace (4100 sequences) and the KV8 / other fall-back paths alike."""
-    import qserve_backend.fused_attention as fa
-    import qserve_backend.fused_kernels as fk
-    from qserve_amd import fused
+# Rows of 3 or more 512-element blocks through the PAYLOAD finisher of the KV4 kernel (group sizes other than 4 and 8, and any group
+# size under qs_set_attention_variant(7)): from 3 blocks on, the block order of invoke_quant_fuse_sum's row sum (row_ops.h
+# reduce_max_blocksum) and the single chain over both chunks the finisher ran until round 6 are different fp32 sums.
+FUSION_BLOCK_SHAPES = [(4, 12, 12, 130), (4, 32, 32, 130), (4, 16, 8, 200), (3, 24, 12, 300)]     # G = 1, 1, 2, 2: 3, 8, 4, 6 blocks
+FUSION_VARIANT7_SHAPES = [(64, 32, 8, 1033), (2, 16, 2, 70)]
+# The two orders differ by a few fp32 ulps and the row sum is stored in fp16: on random inputs the stored sums differ for about one
+# row in 2^12 (and not at all where every partial sum is exact in fp32).  So that the with_sum KV4 cases of the lists above have
+# POWER - fail on a finisher that sums in the old order - their rows are PLANTED (`_planted_v`): q = k = 16 everywhere makes the new
+# token's own score (2 896 after scaling) beat every cached key by > 1 000, its probability is 1 and the others underflow to 0, so the
+# attention output of every head IS the new token's raw v of its KV head; and v is made of values whose fp32 partial sums round
+# differently in the two orders.  The test re-derives that on the host, from the pair's own output, before it compares anything
+# (`_orders_differ`).  KV4 only: the KV8 kernel has no finisher, the fused entry issues the pair there.
+# (B, H, Hkv, L) -> (seed, cancel), found by search on the CPU
+FUSION_POWER = {(4, 12, 12, 130): (12008, True), (4, 32, 32, 130): (32000, True), (4, 16, 8, 200): (16007, True),
+                (3, 24, 12, 300): (24004, True), (64, 32, 8, 1033): (32000, True), (2, 16, 2, 70): (859, False)}
+
+
+def _planted_v(B, Hkv, seed, cancel):
+    """fp16 [B, Hkv, 128].  cancel: nine elements in ten come in pairs (x, -x) at random places of the token's Hkv * 128 values,
+    |x| = 2^U(0, 10) - large partial sums in every summation order, an exact total of 0 - and the others are small values of their
+    own: the row sum is theirs (a few units, fp16 ulp ~2^-9), and what the fp32 partial sums round away on the way depends on the
+    order.  not cancel (rows whose blocks repeat one another - G = 8 - add such pairs up exactly): signs and magnitudes 2^U(-8, 8)."""
+    r = np.random.default_rng(seed)
+    if not cancel:
+        return (r.choice([-1.0, 1.0], (B, Hkv, 128)) * 2.0 ** r.uniform(-8, 8, (B, Hkv, 128))).astype(np.float16)
+    n = Hkv * 128
+    v = np.zeros((B, n), np.float16)
+    for b in range(B):
+        perm = r.permutation(n)
+        npair = (n * 9 // 10) // 2
+        x = (r.choice([-1.0, 1.0], npair) * 2.0 ** r.uniform(0, 10, npair)).astype(np.float16)
+        v[b, perm[:npair]] = x
+        v[b, perm[npair:2 * npair]] = -x
+        v[b, perm[2 * npair:]] = r.uniform(-1, 1, n - 2 * npair).astype(np.float16)
+    return v.reshape(B, Hkv, 128)
+
+
+def _fusion_inputs(gpu, B, H, Hkv, L, int4, planted=None):
     g = torch.Generator(device=gpu).manual_seed(B + H + L)
     mb = (L + 63) // 64 + 1
     dhb = 64 if int4 else 128
@@ -386,9 +412,31 @@ def test_attention_quant_fusion_is_bit_identical_to_the_pair(gpu, B, H, Hkv, L, 
     new = torch.randn((B, (H + 2 * Hkv) * 128), generator=g, device=gpu, dtype=torch.float16)
     q, k, v = new.split([H * 128, Hkv * 128, Hkv * 128], dim=-1)
     q, k, v = q.reshape(B, H, 128), k.reshape(B, Hkv, 128), v.reshape(B, Hkv, 128)
+    if planted is not None:
+        new[:, : (H + Hkv) * 128] = 16.0
+        v.copy_(dev(_planted_v(B, Hkv, *planted), gpu))
     lens = torch.randint(max(1, L - 200), L + 1, (B,), generator=torch.Generator().manual_seed(3)).to(torch.int32).to(gpu)
     lens[0] = L
     args = (None, 8192, 64, Hkv * dhb, L, 128, ROPE, True, int4, True)
+    return fresh, tables, (q, k, v), lens, args
+
+
+def _orders_differ(out1):
+    """Rows of the pair's fp16 output [B, H, 128] whose row sum, rounded to fp16, differs between the payload finisher's order up
+    to round 6 (oracle.fused.hip_order_row_sum: per thread ONE 8-element chain over chunks c = 0, 1, the 64-lane butterfly, the 4
+    waves left to right) and the order invoke_quant_fuse_sum defines (oracle.fused.block_order_row_sum)."""
+    from oracle import fused as ofused
+    x = out1.detach().cpu().numpy().reshape(out1.shape[0], -1).astype(np.float32)
+    with np.errstate(over="ignore"):
+        old, blk = ofused.hip_order_row_sum(x).astype(np.float16), ofused.block_order_row_sum(x).astype(np.float16)
+    return np.nonzero(old.view(np.uint16) != blk.view(np.uint16))[0]
+
+
+def _fusion_case(gpu, B, H, Hkv, L, with_sum, int4, power=False):
+    import qserve_backend.fused_attention as fa
+    import qserve_backend.fused_kernels as fk
+    from qserve_amd import fused
+    fresh, tables, (q, k, v), lens, args = _fusion_inputs(gpu, B, H, Hkv, L, int4, FUSION_POWER[(B, H, Hkv, L)] if power else None)
     # the pair
     p1 = fresh()
     ptr1 = p1.pointers(tables)
@@ -400,6 +448,11 @@ def test_attention_quant_fusion_is_bit_identical_to_the_pair(gpu, B, H, Hkv, L, 
         fk.invoke_quant_fuse_sum(q1, out1.reshape(B, -1), m1, s1)
     else:
         fk.invoke_quant(q1, out1.reshape(B, -1), s1)
+    if power:
+        rows = _orders_differ(out1)
+        print(f"B={B} H={H} Hkv={Hkv} L={L} int4={int4}: the old and the block order of the row sum differ in fp16 in rows {rows.tolist()}")
+        assert len(rows) >= 1, "no row tells the two orders of the row sum apart: the case has no power (re-pick its seed)"
+        assert torch.equal(out1, v[:, :, None, :].expand(B, Hkv, H // Hkv, 128).reshape(B, H, 128)), "the planted rows are not the output"
     # the fused call, twice (the second launch hands over under the next generation tag)
     for rep in range(2):
         p2 = fresh()
@@ -414,6 +467,35 @@ def test_attention_quant_fusion_is_bit_identical_to_the_pair(gpu, B, H, Hkv, L, 
         assert torch.equal(q2, q1), "int8 row differs"
         assert torch.equal(m2.view(torch.int16), m1.view(torch.int16)), "row sum differs (or was touched without being asked for)"
         assert torch.equal(p2.k, p1.k) and torch.equal(p2.v, p1.v), "cache pages differ"
+
+
+@pytest.mark.parametrize("int4", [True, False], ids=["kv4", "kv8"])
+@pytest.mark.parametrize("with_sum", [True, False])
+@pytest.mark.parametrize("B,H,Hkv,L", [(64, 32, 8, 1033), (5, 8, 2, 300), (3, 8, 8, 130), (2, 16, 2, 70), (8, 32, 8, 4000),
+                                      (4100, 8, 2, 70)]    # (more sequences than the hand-over workspace holds: the pair runs)
+                         + FUSION_BLOCK_SHAPES)
+def test_attention_quant_fusion_is_bit_identical_to_the_pair(gpu, B, H, Hkv, L, with_sum, int4):
+    """qserve_amd.fused.single_query_attention_quant == single_query_attention ; invoke_quant(_fuse_sum): the fp16
+    output, the int8 row, the fp16 scale (and row sum) and every cache byte, bit for bit - in-kernel fusion (KV4, no KV
+    split: the workgroup of the last KV head finishes the row from the others' tagged granules), split-KV launches (B=8,
+    L=4000), batches beyond the hand-over workspace (4100 sequences) and the KV8 / other fall-back paths alike; rows of 3 to 8
+    blocks through the payload finisher (FUSION_BLOCK_SHAPES: with a row sum, on q / k / v for which the finisher's old summation
+    order provably gives another fp16 sum)."""
+    _fusion_case(gpu, B, H, Hkv, L, with_sum, int4, power=with_sum and int4 and (B, H, Hkv, L) in FUSION_BLOCK_SHAPES)
+
+
+@pytest.mark.parametrize("int4", [True, False], ids=["kv4", "kv8"])
+@pytest.mark.parametrize("with_sum", [True, False])
+@pytest.mark.parametrize("B,H,Hkv,L", FUSION_VARIANT7_SHAPES)
+def test_attention_quant_fusion_payload_form_is_bit_identical_to_the_pair(gpu, B, H, Hkv, L, with_sum, int4):
+    """qs_set_attention_variant(7): the payload hand-over also for the group sizes that otherwise gather the row statistics (4, 8) -
+    'same bits' (include/qserve_amd.h), rows of 8 and 4 blocks."""
+    from qserve_amd._lib import lib
+    lib.qs_set_attention_variant(7)
+    try:
+        _fusion_case(gpu, B, H, Hkv, L, with_sum, int4, power=with_sum and int4)
+    finally:
+        lib.qs_set_attention_variant(0)
 
 
 def test_attention_quant_fusion_equals_the_pair_under_the_reference_sum_order(gpu):
