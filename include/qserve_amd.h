@@ -458,6 +458,20 @@ int qs_debug_flash_variant(int variant);
  *   qs_append_attention_plan  pure (no device access): plan3 = {tokens per query tile, query tiles per sequence at max_seqlen_q,
  *                      waves per workgroup} of the launch the arguments would get; all zero for an empty launch.  One workgroup
  *                      serves a query tile of ONE KV head with all H / Hkv query heads: rows = (token, head-in-group) pairs.
+ *   qs_append_attention_split  the same attention (same arguments, layout contract and validation, checked before any device
+ *                      call) with the past of every sequence cut into up to num_splits contiguous page ranges that run as workgroups
+ *                      of their own - for long contexts at small batch, where the un-split launch leaves most of the chip idle.  Two
+ *                      launches on `stream`: the split kernel leaves per-row partial records (un-normalised fp32 O[128], running
+ *                      maximum, sum) in the library's split-KV workspace, a merge kernel combines them in fp32 and stores fp16 through
+ *                      out_stride0; nothing outside the rows' H * 128 elements is written.  The ranges are computed on the device
+ *                      from past_lens: max_past is an upper-bound HINT for the planner only (negative = 64 * max_blocks), never
+ *                      something a result depends on.  num_splits = 0 asks qs_append_attention_split_plan with max_past;
+ *                      num_splits >= 1 forces that count (tests, sweeps), clamped to 64 and to what the workspace holds;
+ *                      num_splits < 0 is QS_EINVAL.  An effective count of 1 - and a call that cannot have the workspace (too
+ *                      large, or its first use falls inside a stream capture) - runs qs_append_attention's launch: bit-identical to it.
+ *   qs_append_attention_split_plan  pure (no device access, deterministic in its arguments): plan5 = {tokens per query tile, query
+ *                      tiles, waves per workgroup [the three of qs_append_attention_plan], splits >= 1, KiB of workspace the partial
+ *                      records take (0 with one split)}; all zero for an empty launch.  max_past < 0 is QS_EINVAL.
  * QS_EINVAL: null pointers, bad sizes / head counts / strides;  QS_ENOSUP: head_dim != 128, tokens_per_block != 64, caches
  * without zero points, H / Hkv > 8. */
 int qs_append_rope_update_kv_cache(void* qkv, const int32_t* cu_seqlens_q, const int32_t* past_lens,
@@ -469,6 +483,13 @@ int qs_append_attention(const void* qkv, void* out, const int32_t* cu_seqlens_q,
                         int num_kv_heads, int head_dim, int64_t qkv_stride0, int64_t out_stride0, int tokens_per_block,
                         int size_per_token, int int4_kv_cache, int kv_cache_with_zeros, qs_stream_t stream);
 int qs_append_attention_plan(int batch, int max_seqlen_q, int num_heads, int num_kv_heads, int* plan3);
+int qs_append_attention_split(const void* qkv, void* out, const int32_t* cu_seqlens_q, const int32_t* past_lens,
+                              const int64_t* kv_pointers, int num_tokens, int batch, int max_seqlen_q, int max_blocks, int num_heads,
+                              int num_kv_heads, int head_dim, int64_t qkv_stride0, int64_t out_stride0, int tokens_per_block,
+                              int size_per_token, int int4_kv_cache, int kv_cache_with_zeros, int max_past, int num_splits,
+                              qs_stream_t stream);
+int qs_append_attention_split_plan(int batch, int max_seqlen_q, int max_past, int num_heads, int num_kv_heads, int int4_kv_cache,
+                                   int* plan5);
 
 /* Timing tool (scripts/trace_attn.py): device-to-device copy of the first `bytes` of the split-KV workspace, where the
  * trace instantiation of the KV4 decode attention (qs_set_attention_variant(232)) leaves its s_memtime stamps.

@@ -8,8 +8,13 @@ Sequence b has `past_lens[b]` tokens in its pages and `cu_seqlens_q[b + 1] - cu_
     append_attention              row i attends to keys 0 .. past + i: < past de-quantised from the pages, >= past in fp16 from qkv
     append                        the two, in that order -> out fp16 [T, H, 128]
 
+`max_past` / `num_splits` (append_attention, append): split-KV for long contexts at small batch.  With both None the call is the
+un-split `qs_append_attention`; otherwise `qs_append_attention_split` cuts every sequence's past into page ranges that run as
+workgroups of their own and merges their partial results - `num_splits` ranges when given, else what the planner
+(`qserve_amd.plan.append_attention_split_plan`) picks for the upper-bound hint `max_past`.
+
 `past = 0` is the prefill pair (apply_bias_rope_update_kv_cache + flash_attn_varlen_func), `n = 1` is single_query_attention.
-Backed by qserve_amd/csrc/append_attention.hip and the offset-aware writer in attention.hip."""
+Backed by qserve_amd/csrc/append_attention.hip, append_attention_split.hip and the offset-aware writer in attention.hip."""
 import torch
 
 from .backend._util import check, expect, guard, lib, ptr, stream
@@ -49,9 +54,11 @@ def append_rope_update_kv_cache(qkv, cu_seqlens_q, past_lens, kv_pointers, num_h
 
 
 def append_attention(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, size_per_token, int4_kv,
-                     max_seqlen_q=None, out=None):
+                     max_seqlen_q=None, out=None, max_past=None, num_splits=None):
     """`qkv` ALREADY rotated (append_rope_update_kv_cache) -> out fp16 [T, H, 128].  `max_seqlen_q`: an upper bound of the new
-    tokens per sequence (sizes the launch; default: all T rows - correct, without a device read-back, but a larger grid)."""
+    tokens per sequence (sizes the launch; default: all T rows - correct, without a device read-back, but a larger grid).
+    `max_past`: an upper bound of `past_lens` known on the host - a hint the split-KV planner sizes the launch with, never
+    something the result depends on; `num_splits` >= 1 forces that many page ranges per sequence.  Both None: the un-split call."""
     what = "append.append_attention"
     batch = _check_common(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, size_per_token, int4_kv, what)
     T, H = qkv.size(0), int(num_heads)
@@ -64,17 +71,23 @@ def append_attention(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_k
     msq = T if max_seqlen_q is None else int(max_seqlen_q)
     if msq < 0:
         raise RuntimeError(f"{what}: max_seqlen_q={msq}")
+    if num_splits is not None and int(num_splits) < 1:
+        raise RuntimeError(f"{what}: num_splits={num_splits} (None, or a forced count >= 1)")
+    args = (ptr(qkv), ptr(out), ptr(cu_seqlens_q), ptr(past_lens), ptr(kv_pointers), T, batch, min(msq, T), kv_pointers.size(-1), H,
+            int(num_kv_heads), 128, qkv.stride(0), out.stride(0), 64, int(size_per_token), int(bool(int4_kv)), 1)
     with guard(qkv):
-        check(lib.qs_append_attention(ptr(qkv), ptr(out), ptr(cu_seqlens_q), ptr(past_lens), ptr(kv_pointers), T, batch, min(msq, T),
-                                      kv_pointers.size(-1), H, int(num_kv_heads), 128, qkv.stride(0), out.stride(0), 64,
-                                      int(size_per_token), int(bool(int4_kv)), 1, stream()), what)
+        if max_past is None and num_splits is None:
+            check(lib.qs_append_attention(*args, stream()), what)
+        else:
+            hint = -1 if max_past is None else min(max(int(max_past), 0), 2 ** 31 - 1)
+            check(lib.qs_append_attention_split(*args, hint, 0 if num_splits is None else int(num_splits), stream()), what)
     return out
 
 
 def append(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, size_per_token, rope_theta, int4_kv,
-           max_seqlen_q=None):
+           max_seqlen_q=None, max_past=None, num_splits=None):
     """Writer, then attention (the two touch disjoint page slots; the attention needs the writer's in-place rotation of qkv)."""
     append_rope_update_kv_cache(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, size_per_token, rope_theta,
                                 int4_kv)
     return append_attention(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, size_per_token, int4_kv,
-                            max_seqlen_q=max_seqlen_q)
+                            max_seqlen_q=max_seqlen_q, max_past=max_past, num_splits=num_splits)

@@ -405,6 +405,7 @@ class DecodeEngine:
         itself); lm_head and sampling once, after the last chunk.  Ends in the state `prefill` ends in.  `tokens`: as for
         `prefill`, [B * prompt_len], sequence-major."""
         from . import append as appendmod      # (looked up per call: `appendmod.append` is the seam tests wrap)
+        # (max_past = c0, known on the host: a long past at a small batch is cut into page ranges - append_attention_split.hip)
         cfg, B, dev = self.cfg, self.B, self.dev
         assert self.with_lm_head and prompt_len + 1 <= self.max_len and chunk >= 1
         if tokens is None:
@@ -422,7 +423,7 @@ class DecodeEngine:
 
             def attend(li, qkv):
                 return appendmod.append(qkv, cu, past, self.tables[li], self.H, self.Hkv, self.size_per_token,
-                                        cfg["rope_theta"], self.int4, max_seqlen_q=n).reshape(B * n, -1)
+                                        cfg["rope_theta"], self.int4, max_seqlen_q=n, max_past=c0).reshape(B * n, -1)
 
             self._prompt_layers(h, bufs, attend)
         self._prompt_head(h.view(B, -1, self.hid)[:, -1], prompt_len)

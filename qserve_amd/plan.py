@@ -39,3 +39,13 @@ def append_attention_plan(batch, max_seqlen_q, num_heads, num_kv_heads):
     check(lib.qs_append_attention_plan(batch, max_seqlen_q, num_heads, num_kv_heads, C.cast(buf, C.c_void_p)),
           "append attention plan")
     return dict(tile_tokens=buf[0], q_tiles=buf[1], waves=buf[2])
+
+
+def append_attention_split_plan(batch, max_seqlen_q, max_past, num_heads, num_kv_heads, int4_kv_cache=True):
+    """-> dict(tile_tokens, q_tiles, waves, splits, workspace_bytes): what `qs_append_attention_split` launches when it is asked
+    to choose (`qs_append_attention_split_plan`).  The first three are `append_attention_plan`'s; `splits` page ranges per
+    sequence (1 = the un-split launch, which takes no workspace); all zero for an empty launch."""
+    buf = (C.c_int * 5)()
+    check(lib.qs_append_attention_split_plan(batch, max_seqlen_q, max_past, num_heads, num_kv_heads, int(bool(int4_kv_cache)),
+                                             C.cast(buf, C.c_void_p)), "append attention split plan")
+    return dict(tile_tokens=buf[0], q_tiles=buf[1], waves=buf[2], splits=buf[3], workspace_bytes=buf[4] * 1024)
