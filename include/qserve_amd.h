@@ -473,7 +473,30 @@ int qs_debug_flash_variant(int variant);
  *                      tiles, waves per workgroup [the three of qs_append_attention_plan], splits >= 1, KiB of workspace the partial
  *                      records take (0 with one split)}; all zero for an empty launch.  max_past < 0 is QS_EINVAL.
  * QS_EINVAL: null pointers, bad sizes / head counts / strides;  QS_ENOSUP: head_dim != 128, tokens_per_block != 64, caches
- * without zero points, H / Hkv > 8. */
+ * without zero points, H / Hkv > 8.
+ *
+ * Tree-draft verification (Medusa / EAGLE / SpecInfer style: several candidates per position, verified in one pass).  The n <= 64 new
+ * rows of a sequence are the NODES OF A TREE IN TOPOLOGICAL ORDER (a parent's index is below its child's).  tree_mask: device uint64
+ * [T], 8-byte aligned, one word per row of qkv; bit j of node i's word = "node i sees new token j of its own sequence", bits >= n are
+ * ignored.  A well-formed word is ancestor-closed and has its own bit set (a chain: (2 << i) - 1); the depth of a node is
+ * popcount(word) - 1 - the one source of truth, there is no depth array.
+ *   qs_append_tree_rope_update_kv_cache  qs_append_rope_update_kv_cache with two positions per node: q and k are NeoX-rotated at
+ *                      position past + depth (an empty word: depth 0), the rotated K and raw V are quantised into the slot of
+ *                      position past + i.  Same arithmetic per element, same cos / sin, slots beyond the pointer table are skipped;
+ *                      with chain words it leaves qs_append_rope_update_kv_cache's bytes.  qkv 16-byte aligned.
+ *   qs_append_tree_attention  qs_append_attention_split (same arguments - max_past and num_splits included -, layout contract,
+ *                      validation, workspace, merge and fall-back rules; num_splits = 1 runs un-split) with another rule among the new
+ *                      tokens: row i sees every cached key < past, and new key j iff j < n and bit j of its word is set.  Nothing else
+ *                      is assumed - no j <= i, no closure.  A row that sees no key is exactly 0.  Softmax, scale and de-quantised
+ *                      values are unchanged: with chain words the result is bit-identical to the linear entries.  max_seqlen_q > 64
+ *                      is QS_EINVAL before any device call.
+ *   qs_kv_cache_commit_path  after acceptance: for k < accept_lens[b], slot past + k of sequence b receives the bytes (data, fp16
+ *                      scale, fp16 zero; K and V, every KV head) of slot past + accept_idx[b, k].  accept_idx int32 [batch, max_accept]
+ *                      with strictly increasing rows (hence accept_idx[b, k] >= k) of node indices 0 .. 63, accept_lens int32 [batch],
+ *                      max_accept <= 64 (QS_EINVAL otherwise).  Every source is read before any destination is written (a source may
+ *                      be another move's destination; moves cross page boundaries); identity moves are skipped; no other byte of any
+ *                      page changes.  Slots >= past + accept_lens[b] KEEP WHAT THEY HOLD - the rejected nodes' stale K / V -, which every
+ *                      reader masks by the sequence length and the next writer overwrites.  The caller advances its lengths. */
 int qs_append_rope_update_kv_cache(void* qkv, const int32_t* cu_seqlens_q, const int32_t* past_lens,
                                    const int64_t* kv_pointers, int num_tokens, int batch, int max_blocks, int head_num,
                                    int kv_head_num, int tokens_per_block, int size_per_token, int rotary_embedding_dim,
@@ -490,6 +513,19 @@ int qs_append_attention_split(const void* qkv, void* out, const int32_t* cu_seql
                               qs_stream_t stream);
 int qs_append_attention_split_plan(int batch, int max_seqlen_q, int max_past, int num_heads, int num_kv_heads, int int4_kv_cache,
                                    int* plan5);
+int qs_append_tree_rope_update_kv_cache(void* qkv, const int32_t* cu_seqlens_q, const int32_t* past_lens,
+                                        const int64_t* kv_pointers, const uint64_t* tree_mask, int num_tokens, int batch,
+                                        int max_blocks, int head_num, int kv_head_num, int tokens_per_block, int size_per_token,
+                                        int rotary_embedding_dim, float rotary_base, int int4_kv_cache, int kv_cache_with_zeros,
+                                        qs_stream_t stream);
+int qs_append_tree_attention(const void* qkv, void* out, const int32_t* cu_seqlens_q, const int32_t* past_lens,
+                             const int64_t* kv_pointers, const uint64_t* tree_mask, int num_tokens, int batch, int max_seqlen_q,
+                             int max_blocks, int num_heads, int num_kv_heads, int head_dim, int64_t qkv_stride0, int64_t out_stride0,
+                             int tokens_per_block, int size_per_token, int int4_kv_cache, int kv_cache_with_zeros, int max_past,
+                             int num_splits, qs_stream_t stream);
+int qs_kv_cache_commit_path(const int64_t* kv_pointers, const int32_t* past_lens, const int32_t* accept_idx,
+                            const int32_t* accept_lens, int batch, int max_accept, int max_blocks, int kv_head_num,
+                            int tokens_per_block, int size_per_token, int int4_kv_cache, int kv_cache_with_zeros, qs_stream_t stream);
 
 /* Timing tool (scripts/trace_attn.py): device-to-device copy of the first `bytes` of the split-KV workspace, where the
  * trace instantiation of the KV4 decode attention (qs_set_attention_variant(232)) leaves its s_memtime stamps.

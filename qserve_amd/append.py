@@ -14,7 +14,19 @@ workgroups of their own and merges their partial results - `num_splits` ranges w
 (`qserve_amd.plan.append_attention_split_plan`) picks for the upper-bound hint `max_past`.
 
 `past = 0` is the prefill pair (apply_bias_rope_update_kv_cache + flash_attn_varlen_func), `n = 1` is single_query_attention.
-Backed by qserve_amd/csrc/append_attention.hip, append_attention_split.hip and the offset-aware writer in attention.hip."""
+
+Tree-draft verification (several drafted candidates per position, verified in one pass): the n <= 64 new rows of a sequence are the
+nodes of a tree in topological order, `tree_mask` int64 [T] holds one 64-bit word per row (bit j of node i's word: "node i sees new
+token j of its own sequence"; `tree_masks_from_parents` builds ancestor-closed words):
+
+    append_tree_rope_update_kv_cache   node i: q, k rotated at position past + depth (depth = popcount(word) - 1), K / V into slot past + i
+    append_tree_attention              row i attends to every cached key < past and to the new keys its word names - nothing else
+    append_tree                        the two, in that order
+    commit_path                        after acceptance: slots past .. past + m - 1 receive the accepted path's K / V; the slots behind
+                                       them keep the rejected nodes' stale bytes, which every reader masks by the sequence length
+
+Backed by qserve_amd/csrc/append_attention.hip, append_attention_split.hip, append_tree.hip and the offset-aware writers in
+attention.hip."""
 import torch
 
 from .backend._util import check, expect, guard, lib, ptr, stream
@@ -91,3 +103,112 @@ def append(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, s
                                 int4_kv)
     return append_attention(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, size_per_token, int4_kv,
                             max_seqlen_q=max_seqlen_q, max_past=max_past, num_splits=num_splits)
+
+
+# ---- tree-draft verification ------------------------------------------------------------------------------------------------
+MAX_TREE = 64      # nodes per sequence: one 64-bit word per row
+
+
+def tree_masks_from_parents(parents, cu_seqlens_q):
+    """Ancestor masks of draft trees -> int64 [T] (CPU; the bit pattern of the library's uint64 words).  `parents[t]` is the parent
+    of row t as an index INTO ITS OWN SEQUENCE, -1 for a node that hangs off the context; nodes are in topological order, so a
+    parent's index is below its child's (anything else raises).  Word of node i = word of its parent | bit i: ancestor-closed, own
+    bit set; a chain gives (2 << i) - 1."""
+    par = [int(x) for x in (parents.tolist() if hasattr(parents, "tolist") else parents)]
+    cu = [int(x) for x in (cu_seqlens_q.tolist() if hasattr(cu_seqlens_q, "tolist") else cu_seqlens_q)]
+    if not cu or cu[0] != 0 or cu[-1] != len(par) or any(b < a for a, b in zip(cu, cu[1:])):
+        raise RuntimeError(f"tree_masks_from_parents: cu_seqlens_q {cu} does not partition {len(par)} rows")
+    words = []
+    for s, e in zip(cu, cu[1:]):
+        if e - s > MAX_TREE:
+            raise RuntimeError(f"tree_masks_from_parents: {e - s} nodes in one sequence (at most {MAX_TREE})")
+        for i in range(e - s):
+            p = par[s + i]
+            if p < -1 or p >= i:
+                raise RuntimeError(f"tree_masks_from_parents: node {i} has parent {p}: a parent is -1 or an EARLIER node "
+                                   "(topological order)")
+            words.append((words[s + p] if p >= 0 else 0) | (1 << i))
+    return torch.tensor([w - (1 << 64) if w >= (1 << 63) else w for w in words], dtype=torch.int64)
+
+
+def _check_tree(tree_mask, qkv, max_seqlen_q, what):
+    expect(tree_mask, torch.int64, "tree_mask")
+    if tree_mask.dim() != 1 or tree_mask.numel() != qkv.size(0):
+        raise RuntimeError(f"{what}: tree_mask must be int64 [T] = [{qkv.size(0)}], one word per row of qkv, got {tuple(tree_mask.shape)}")
+    if max_seqlen_q is not None and int(max_seqlen_q) > MAX_TREE:
+        raise RuntimeError(f"{what}: max_seqlen_q={max_seqlen_q}: a tree has at most {MAX_TREE} nodes per sequence")
+
+
+def append_tree_rope_update_kv_cache(qkv, cu_seqlens_q, past_lens, kv_pointers, tree_mask, num_heads, num_kv_heads, size_per_token,
+                                     rope_theta, int4_kv):
+    """In place on `qkv` (q and k heads of node i rotated at position past + depth) and on the pages (slot past + i)."""
+    what = "append.append_tree_rope_update_kv_cache"
+    batch = _check_common(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, size_per_token, int4_kv, what)
+    _check_tree(tree_mask, qkv, None, what)
+    with guard(qkv):
+        check(lib.qs_append_tree_rope_update_kv_cache(ptr(qkv), ptr(cu_seqlens_q), ptr(past_lens), ptr(kv_pointers), ptr(tree_mask),
+                                                      qkv.size(0), batch, kv_pointers.size(-1), int(num_heads), int(num_kv_heads), 64,
+                                                      int(size_per_token), 128, float(rope_theta), int(bool(int4_kv)), 1, stream()), what)
+
+
+def append_tree_attention(qkv, cu_seqlens_q, past_lens, kv_pointers, tree_mask, num_heads, num_kv_heads, size_per_token, int4_kv,
+                          max_seqlen_q=None, out=None, max_past=None, num_splits=None):
+    """`qkv` ALREADY rotated (append_tree_rope_update_kv_cache) -> out fp16 [T, H, 128].  `max_seqlen_q` (<= 64; default: min(T, 64)),
+    `max_past`, `num_splits` as for append_attention; with both None the launch is un-split."""
+    what = "append.append_tree_attention"
+    batch = _check_common(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, size_per_token, int4_kv, what)
+    _check_tree(tree_mask, qkv, max_seqlen_q, what)
+    T, H = qkv.size(0), int(num_heads)
+    if out is None:
+        out = torch.empty((T, H, 128), dtype=torch.float16, device=qkv.device)
+    else:
+        expect(out, torch.float16, "out", contiguous=False)
+        if tuple(out.shape) != (T, H, 128) or out.stride(2) != 1 or out.stride(1) != 128 or out.stride(0) % 8 != 0:
+            raise RuntimeError(f"{what}: out must be [T, H, 128] with contiguous heads and a row stride that is a multiple of 8")
+    msq = min(T, MAX_TREE) if max_seqlen_q is None else int(max_seqlen_q)
+    if msq < 0:
+        raise RuntimeError(f"{what}: max_seqlen_q={msq}")
+    if num_splits is not None and int(num_splits) < 1:
+        raise RuntimeError(f"{what}: num_splits={num_splits} (None, or a forced count >= 1)")
+    hint = -1 if max_past is None else min(max(int(max_past), 0), 2 ** 31 - 1)
+    splits = (1 if max_past is None else 0) if num_splits is None else int(num_splits)
+    with guard(qkv):
+        check(lib.qs_append_tree_attention(ptr(qkv), ptr(out), ptr(cu_seqlens_q), ptr(past_lens), ptr(kv_pointers), ptr(tree_mask), T, batch,
+                                           min(msq, T), kv_pointers.size(-1), H, int(num_kv_heads), 128, qkv.stride(0), out.stride(0), 64,
+                                           int(size_per_token), int(bool(int4_kv)), 1, hint, splits, stream()), what)
+    return out
+
+
+def append_tree(qkv, cu_seqlens_q, past_lens, kv_pointers, tree_mask, num_heads, num_kv_heads, size_per_token, rope_theta, int4_kv,
+                max_seqlen_q=None, max_past=None, num_splits=None):
+    """Tree writer, then tree attention (the attention needs the writer's in-place rotation of qkv)."""
+    if max_seqlen_q is not None and int(max_seqlen_q) > MAX_TREE:      # (before the writer touches anything)
+        raise RuntimeError(f"append.append_tree: max_seqlen_q={max_seqlen_q}: a tree has at most {MAX_TREE} nodes per sequence")
+    append_tree_rope_update_kv_cache(qkv, cu_seqlens_q, past_lens, kv_pointers, tree_mask, num_heads, num_kv_heads, size_per_token,
+                                     rope_theta, int4_kv)
+    return append_tree_attention(qkv, cu_seqlens_q, past_lens, kv_pointers, tree_mask, num_heads, num_kv_heads, size_per_token, int4_kv,
+                                 max_seqlen_q=max_seqlen_q, max_past=max_past, num_splits=num_splits)
+
+
+def commit_path(kv_pointers, past_lens, accept_idx, accept_lens, num_kv_heads, size_per_token, int4_kv):
+    """In place on the pages: for k < accept_lens[b], slot past + k of sequence b receives the bytes of slot past + accept_idx[b, k]
+    (K and V, every KV head; data, scale, zero).  accept_idx int32 [batch, max_accept <= 64], rows strictly increasing; accept_lens
+    int32 [batch].  The slots behind the path keep the rejected nodes' bytes; the caller advances its lengths."""
+    what = "append.commit_path"
+    expect(kv_pointers, torch.int64, "kv_pointers")
+    expect(past_lens, torch.int32, "past_lens")
+    expect(accept_idx, torch.int32, "accept_idx")
+    expect(accept_lens, torch.int32, "accept_lens")
+    batch = past_lens.numel()
+    if kv_pointers.dim() != 3 or kv_pointers.size(0) != batch or kv_pointers.size(1) != 2:
+        raise RuntimeError(f"{what}: kv_pointers must be [batch, 2, max_blocks], got {tuple(kv_pointers.shape)}")
+    if accept_idx.dim() != 2 or accept_idx.size(0) != batch or accept_lens.dim() != 1 or accept_lens.numel() != batch:
+        raise RuntimeError(f"{what}: accept_idx must be [batch, max_accept] and accept_lens [batch]")
+    if accept_idx.size(1) > MAX_TREE:
+        raise RuntimeError(f"{what}: max_accept={accept_idx.size(1)}: a path has at most {MAX_TREE} nodes")
+    Hkv = int(num_kv_heads)
+    if Hkv <= 0 or int(size_per_token) != Hkv * (64 if int4_kv else 128):
+        raise RuntimeError(f"{what}: size_per_token={size_per_token}, expected {Hkv * (64 if int4_kv else 128)}")
+    with guard(kv_pointers):
+        check(lib.qs_kv_cache_commit_path(ptr(kv_pointers), ptr(past_lens), ptr(accept_idx), ptr(accept_lens), batch, accept_idx.size(1),
+                                          kv_pointers.size(-1), Hkv, 64, int(size_per_token), int(bool(int4_kv)), 1, stream()), what)

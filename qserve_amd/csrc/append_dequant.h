@@ -1,7 +1,7 @@
-// append_dequant.h -- the leaves both append attention kernels (append_attention.hip, append_attention_split.hip) share: the exact
-// KV4 / KV8 -> fp16 de-quantisation of 8 consecutive dims of a cached token (the decode kernels' values), the scalar form of a
-// page address for the LDS-DMA's base operand, and the launch geometry.  The page staging itself (LDS-DMA of a page's raw bytes into
-// the tile images, in-place de-quantisation behind the P.V products) captures its kernel's state and stays in each kernel.
+// append_dequant.h -- the leaves the append attention kernels (append_attention.hip, append_attention_split.hip, append_tree.hip)
+// share: the exact KV4 / KV8 -> fp16 de-quantisation of 8 consecutive dims of a cached token (the decode kernels' values), the scalar
+// form of a page address for the LDS-DMA's base operand, the launch geometry and the argument checks.  The page staging and the key
+// loop built from these leaves are append_walk.h.
 #pragma once
 #include "flash_tile.h"
 

@@ -484,9 +484,11 @@ __device__ __forceinline__ void group_quant_store(const h8& lo, const h8& hi, ui
     }
 }
 
-// one token's row: RoPE at `pos` in place on the q and k heads, quantised K / V into the page slot of `pos` of sequence b
+// one token's row: RoPE in place on the q and k heads with the coefficients `cs` (the ROPE POSITION is the caller's: it chose them),
+// quantised K / V into the page slot of position `slot_pos` of sequence b.  The two are the same position for a linear sequence
+// (the prefill and the append writer); a draft-tree node is rotated at its depth and parked in the slot of its index (the tree writer).
 template <bool INT4>
-__device__ __forceinline__ void kv_vec_token(_Float16* row, const RopeCS (&cs)[8], int b, int pos, int dg, int slot0,
+__device__ __forceinline__ void kv_vec_token(_Float16* row, const RopeCS (&cs)[8], int b, int slot_pos, int dg, int slot0,
                                              const int64_t* __restrict__ kv_pointers, int max_blocks, int head_num,
                                              int kv_head_num) {
     constexpr int DHB = INT4 ? DH / 2 : DH;
@@ -507,7 +509,7 @@ __device__ __forceinline__ void kv_vec_token(_Float16* row, const RopeCS (&cs)[8
             const int hk = job - head_num;
             const _Float16* vh = row + (head_num + kv_head_num) * DH + hk * DH;
             const h8 vl = *reinterpret_cast<const h8*>(vh + 8 * dg), vhh = *reinterpret_cast<const h8*>(vh + 64 + 8 * dg);
-            const int blk = pos >> 6, slot = pos & 63;
+            const int blk = slot_pos >> 6, slot = slot_pos & 63;
             const int64_t* tab = kv_pointers + (size_t)b * 2 * max_blocks;
             uint8_t* kp = reinterpret_cast<uint8_t*>(tab[blk]);
             uint8_t* vp = reinterpret_cast<uint8_t*>(tab[max_blocks + blk]);
@@ -546,6 +548,28 @@ __global__ __launch_bounds__(TPB) void prefill_kv_vec_kernel(_Float16* __restric
     kv_vec_token<INT4>(qkv + (size_t)t * n, cs, b, pos, dg, slot0, kv_pointers, max_blocks, head_num, kv_head_num);
 }
 
+// cos / sin of position `pos` for this lane's 8 dims: from the library's table where it covers the position, otherwise evaluated
+// here (rope_coef: the same double-evaluated, float-rounded values)
+__device__ __forceinline__ void rope_cs_at(const float2* __restrict__ rope_tab, int tab_len, float rope_base, int pos, int dg, RopeCS (&cs)[8]) {
+    if (rope_tab && pos < tab_len) {
+        rope_cs_from_table(rope_tab, pos, dg, cs);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) cs[j] = rope_coef(8 * dg + j, pos, rope_base, DH);
+    }
+}
+// the sequence of row t of a packed buffer: the largest b with cu_q[b] <= t (empty sequences are stepped over); -1 for a row of nobody
+__device__ __forceinline__ int sequence_of_row(const int* __restrict__ cu_q, int batch, int t) {
+    if (t < cu_q[0] || t >= cu_q[batch]) return -1;
+    int b = 0, hi_b = batch;
+    while (b + 1 < hi_b) {
+        const int mid = (b + hi_b) >> 1;
+        if (cu_q[mid] <= t) b = mid;
+        else hi_b = mid;
+    }
+    return b;
+}
+
 // The offset-aware writer of the append path (qs_append_rope_update_kv_cache; no reference counterpart): token t of the packed
 // buffer belongs to the sequence b with cu_q[b] <= t < cu_q[b + 1] and sits at position past_lens[b] + (t - cu_q[b]).  The same
 // arithmetic per element as the prefill writer (kv_vec_token); cos / sin from the library's table where it covers the position,
@@ -558,25 +582,43 @@ __global__ __launch_bounds__(TPB) void append_kv_vec_kernel(_Float16* __restrict
                                                             int head_num, int kv_head_num, const float2* __restrict__ rope_tab,
                                                             int tab_len, float rope_base) {
     const int t = blockIdx.x;
-    if (t < cu_q[0] || t >= cu_q[batch]) return;
-    int b = 0, hi_b = batch;                                // largest b with cu_q[b] <= t (empty sequences are stepped over)
-    while (b + 1 < hi_b) {
-        const int mid = (b + hi_b) >> 1;
-        if (cu_q[mid] <= t) b = mid;
-        else hi_b = mid;
-    }
+    const int b = sequence_of_row(cu_q, batch, t);
+    if (b < 0) return;
     const int pos = past_lens[b] + (t - cu_q[b]);
     if (pos < 0 || pos >= max_blocks * PAGE_TOK) return;
     const int dg = threadIdx.x & 7, slot0 = threadIdx.x >> 3;
     const int n = (head_num + 2 * kv_head_num) * DH;
     RopeCS cs[8];
-    if (rope_tab && pos < tab_len) {
-        rope_cs_from_table(rope_tab, pos, dg, cs);
-    } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) cs[j] = rope_coef(8 * dg + j, pos, rope_base, DH);
-    }
+    rope_cs_at(rope_tab, tab_len, rope_base, pos, dg, cs);
     kv_vec_token<INT4>(qkv + (size_t)t * n, cs, b, pos, dg, slot0, kv_pointers, max_blocks, head_num, kv_head_num);
+}
+
+// The writer of a DRAFT TREE (qs_append_tree_rope_update_kv_cache; append_tree.hip has the attention and the path commit): row t is node
+// i = t - cu_q[b] of its sequence's tree, and its 64-bit word of tree_mask (bit j: "sees new token j"; bits >= n ignored) holds its
+// ancestors and itself - so it is NeoX-rotated at position past + popcount(word) - 1, its depth (an empty word: depth 0), while its
+// K / V are quantised into slot past + i, where the attention's pages-then-new-keys order and the path commit expect them.  The
+// per-element arithmetic is kv_vec_token's: with chain words (2 << i) - 1 this is the append writer, byte for byte.
+template <bool INT4>
+__global__ __launch_bounds__(TPB) void append_tree_kv_vec_kernel(_Float16* __restrict__ qkv, const int* __restrict__ cu_q,
+                                                                 const int* __restrict__ past_lens,
+                                                                 const int64_t* __restrict__ kv_pointers,
+                                                                 const uint64_t* __restrict__ tree_mask, int batch, int max_blocks,
+                                                                 int head_num, int kv_head_num, const float2* __restrict__ rope_tab,
+                                                                 int tab_len, float rope_base) {
+    const int t = blockIdx.x;
+    const int b = sequence_of_row(cu_q, batch, t);
+    if (b < 0) return;
+    const int i = t - cu_q[b], nb = cu_q[b + 1] - cu_q[b];
+    uint64_t word = tree_mask[t];
+    if (nb < 64) word &= (1ull << nb) - 1;
+    const int depth = word ? __popcll(word) - 1 : 0;
+    const int slot_pos = past_lens[b] + i, rope_pos = past_lens[b] + depth;
+    if (slot_pos < 0 || rope_pos < 0 || slot_pos >= max_blocks * PAGE_TOK) return;
+    const int dg = threadIdx.x & 7, slot0 = threadIdx.x >> 3;
+    const int n = (head_num + 2 * kv_head_num) * DH;
+    RopeCS cs[8];
+    rope_cs_at(rope_tab, tab_len, rope_base, rope_pos, dg, cs);
+    kv_vec_token<INT4>(qkv + (size_t)t * n, cs, b, slot_pos, dg, slot0, kv_pointers, max_blocks, head_num, kv_head_num);
 }
 
 __global__ void padding_offsets_kernel(int* __restrict__ out, const int* __restrict__ cu, int max_seqlen) {
@@ -848,23 +890,20 @@ extern "C" int qs_apply_bias_rope_update_kv_cache(void* qkv, const int32_t* seq_
 }
 
 // The prefill writer for tokens that CONTINUE a sequence (append attention, include/qserve_amd.h): new token i of sequence b is
-// rotated at position past_lens[b] + i and quantised into that position's page slot.
-extern "C" int qs_append_rope_update_kv_cache(void* qkv, const int32_t* cu_seqlens_q, const int32_t* past_lens,
-                                              const int64_t* kv_pointers, int num_tokens, int batch, int max_blocks,
-                                              int head_num, int kv_head_num, int tokens_per_block, int size_per_token,
-                                              int rotary_embedding_dim, float rotary_base, int int4_kv_cache,
-                                              int kv_cache_with_zeros, qs_stream_t stream) {
-    QS_REQUIRE(qkv && cu_seqlens_q && past_lens && kv_pointers, "append_rope_update_kv_cache: null pointer");
-    QS_REQUIRE(head_num > 0 && kv_head_num > 0 && batch >= 0 && num_tokens >= 0 && max_blocks > 0,
-               "append_rope_update_kv_cache: bad sizes");
+// rotated at position past_lens[b] + i and quantised into that position's page slot.  With tree_mask (the tree entry) the rope
+// position is past + depth instead, the slot stays past + i.  One body for the validation and the table; `what` names the entry.
+static int append_writer(const char* what, void* qkv, const int32_t* cu_seqlens_q, const int32_t* past_lens, const int64_t* kv_pointers,
+                         const uint64_t* tree_mask, int num_tokens, int batch, int max_blocks, int head_num, int kv_head_num,
+                         int tokens_per_block, int size_per_token, int rotary_embedding_dim, float rotary_base, int int4_kv_cache,
+                         int kv_cache_with_zeros, qs_stream_t stream) {
+    QS_REQUIRE(qkv && cu_seqlens_q && past_lens && kv_pointers, "%s: null pointer", what);
+    QS_REQUIRE(head_num > 0 && kv_head_num > 0 && batch >= 0 && num_tokens >= 0 && max_blocks > 0, "%s: bad sizes", what);
     if (rotary_embedding_dim != 128 || tokens_per_block != 64 || !kv_cache_with_zeros) {
-        qs_set_error("append_rope_update_kv_cache: only head_dim=128, tokens_per_block=64 and "
-                     "zero-point KV caches are supported");
+        qs_set_error("%s: only head_dim=128, tokens_per_block=64 and zero-point KV caches are supported", what);
         return QS_ENOSUP;
     }
     const int dhb = int4_kv_cache ? 64 : 128;
-    QS_REQUIRE(size_per_token == kv_head_num * dhb, "append_rope_update_kv_cache: size_per_token=%d, expected %d", size_per_token,
-               kv_head_num * dhb);
+    QS_REQUIRE(size_per_token == kv_head_num * dhb, "%s: size_per_token=%d, expected %d", what, size_per_token, kv_head_num * dhb);
     if (num_tokens == 0 || batch == 0) return QS_OK;
     hipStream_t st = (hipStream_t)stream;
     // (table length: the pointer table's reach rounded up to a power of two >= 2048 - calls with growing tables share an entry
@@ -873,13 +912,41 @@ extern "C" int qs_append_rope_update_kv_cache(void* qkv, const int32_t* cu_seqle
     while (want < max_blocks * PAGE_TOK && want < 32768) want *= 2;
     const float2* tab = g_attn_variant == 2 ? nullptr : qs_rope_table(rotary_base, want, st, &tab_len);
     if (!tab) tab_len = 0;
-    if (int4_kv_cache)
+    if (tree_mask) {
+        if (int4_kv_cache)
+            hipLaunchKernelGGL(append_tree_kv_vec_kernel<true>, dim3(num_tokens), dim3(TPB), 0, st, (_Float16*)qkv, cu_seqlens_q, past_lens,
+                               kv_pointers, tree_mask, batch, max_blocks, head_num, kv_head_num, tab, tab_len, rotary_base);
+        else
+            hipLaunchKernelGGL(append_tree_kv_vec_kernel<false>, dim3(num_tokens), dim3(TPB), 0, st, (_Float16*)qkv, cu_seqlens_q, past_lens,
+                               kv_pointers, tree_mask, batch, max_blocks, head_num, kv_head_num, tab, tab_len, rotary_base);
+    } else if (int4_kv_cache)
         hipLaunchKernelGGL(append_kv_vec_kernel<true>, dim3(num_tokens), dim3(TPB), 0, st, (_Float16*)qkv, cu_seqlens_q, past_lens,
                            kv_pointers, batch, max_blocks, head_num, kv_head_num, tab, tab_len, rotary_base);
     else
         hipLaunchKernelGGL(append_kv_vec_kernel<false>, dim3(num_tokens), dim3(TPB), 0, st, (_Float16*)qkv, cu_seqlens_q, past_lens,
                            kv_pointers, batch, max_blocks, head_num, kv_head_num, tab, tab_len, rotary_base);
-    return qs_launch_status("append_rope_update_kv_cache");
+    return qs_launch_status(what);
+}
+extern "C" int qs_append_rope_update_kv_cache(void* qkv, const int32_t* cu_seqlens_q, const int32_t* past_lens,
+                                              const int64_t* kv_pointers, int num_tokens, int batch, int max_blocks,
+                                              int head_num, int kv_head_num, int tokens_per_block, int size_per_token,
+                                              int rotary_embedding_dim, float rotary_base, int int4_kv_cache,
+                                              int kv_cache_with_zeros, qs_stream_t stream) {
+    return append_writer("append_rope_update_kv_cache", qkv, cu_seqlens_q, past_lens, kv_pointers, nullptr, num_tokens, batch, max_blocks,
+                         head_num, kv_head_num, tokens_per_block, size_per_token, rotary_embedding_dim, rotary_base, int4_kv_cache,
+                         kv_cache_with_zeros, stream);
+}
+extern "C" int qs_append_tree_rope_update_kv_cache(void* qkv, const int32_t* cu_seqlens_q, const int32_t* past_lens,
+                                                   const int64_t* kv_pointers, const uint64_t* tree_mask, int num_tokens, int batch,
+                                                   int max_blocks, int head_num, int kv_head_num, int tokens_per_block, int size_per_token,
+                                                   int rotary_embedding_dim, float rotary_base, int int4_kv_cache, int kv_cache_with_zeros,
+                                                   qs_stream_t stream) {
+    QS_REQUIRE(tree_mask, "append_tree_rope_update_kv_cache: null tree_mask");
+    QS_REQUIRE((reinterpret_cast<uintptr_t>(tree_mask) & 7) == 0, "append_tree_rope_update_kv_cache: tree_mask must be 8-byte aligned");
+    QS_REQUIRE((reinterpret_cast<uintptr_t>(qkv) & 15) == 0, "append_tree_rope_update_kv_cache: qkv must be 16-byte aligned");
+    return append_writer("append_tree_rope_update_kv_cache", qkv, cu_seqlens_q, past_lens, kv_pointers, tree_mask, num_tokens, batch,
+                         max_blocks, head_num, kv_head_num, tokens_per_block, size_per_token, rotary_embedding_dim, rotary_base,
+                         int4_kv_cache, kv_cache_with_zeros, stream);
 }
 
 extern "C" int qs_compute_padding_offsets(int32_t* padding_offsets, const int32_t* cu_seqlens, int batch,

@@ -1,6 +1,6 @@
 // flash_tile.h -- the flash-attention tile core of MI355X (gfx950), once: what a 4-wave workgroup does with ONE 64-key tile of fp16
-// K / V rows in LDS, as device functions behind the two kernels that walk key tiles - the prefill provider (flash_prefill.hip) and
-// append attention over the quantised KV cache (append_attention.hip).  The two differ in WHO the 128 rows of a workgroup are and
+// K / V rows in LDS, as device functions behind the kernels that walk key tiles - the prefill provider (flash_prefill.hip) and
+// append attention over the quantised KV cache (append_walk.h: append_attention.hip, append_attention_split.hip, append_tree.hip).  The two differ in WHO the 128 rows of a workgroup are and
 // WHERE a tile comes from (their key range, tile schedule, page staging and row mapping stay in their own files); the tile itself -
 // its LDS images, the two swapped MFMA products, the online softmax between them and the way O leaves - is this header:
 //   * workgroup = 4 wave64 = 128 rows; wave w owns 32 rows and keeps their Q fragments (8 x 16 dims) in registers;
@@ -186,17 +186,33 @@ __device__ __forceinline__ void read_v(const uint8_t* smem, BUF bufc, int lane, 
 // LAZY running maximum (round 6) - a row's reference maximum moves only when a tile exceeds it by more than 2^8 (probabilities stay
 // <= 256 in fp16, sums in fp32: the same softmax), so the rescale, which ran on ~85 % of the tiles of a 1 024-token prompt,
 // becomes rare.  LAZY = false is the exact running maximum of the prefill kernel of rounds 2-5.
-template <bool LAZY, class LIMIT>
-__device__ __forceinline__ void softmax_tile(v16f (&sacc)[NKB], bool need_mask, LIMIT limit_of_row, int lane, float scale_log2, float& m_run,
-                                             float& l_run, v16f (&oacc)[4], u32 (&pb)[NKB][2][4]) {
+// The two mask rules, both with the lane half OUT of the key index (`hi` = lane >> 5 goes into the limit / the word):
+//   mask_keys_above  a prefix: key <= limit (causal diagonals, the end of the keys, the end of a page's live slots);
+//   mask_keys_by_word  a set: bit `key` of a 64-bit word (the ancestor masks of tree-draft verification, append_tree.hip).
+__device__ __forceinline__ void mask_keys_above(v16f (&sacc)[NKB], int limit_of_row, int hi) {
+    const int limit = limit_of_row - 4 * hi;
+#pragma unroll
+    for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sacc[kb][r] = 32 * kb + (r & 3) + 8 * (r >> 2) <= limit ? sacc[kb][r] : -INFINITY;
+}
+__device__ __forceinline__ void mask_keys_by_word(v16f (&sacc)[NKB], uint64_t word, int hi) {
+    static_assert(NKB == 2, "one 32-bit half of the word per 32-key block");
+    const uint64_t w = word >> (4 * hi);
+    const u32 half[2] = {(u32)w, (u32)(w >> 32)};
+#pragma unroll
+    for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sacc[kb][r] = (half[kb] & (1u << ((r & 3) + 8 * (r >> 2)))) != 0 ? sacc[kb][r] : -INFINITY;
+}
+
+// softmax_tile_masked: the mask is the caller's - mask_tile(sacc, hi) is called only where a mask is needed and applies either rule
+// (or picks one by a wave-uniform test); softmax_tile below is the prefix rule, key <= limit_of_row().
+template <bool LAZY, class MASK>
+__device__ __forceinline__ void softmax_tile_masked(v16f (&sacc)[NKB], bool need_mask, MASK mask_tile, int lane, float scale_log2, float& m_run,
+                                                    float& l_run, v16f (&oacc)[4], u32 (&pb)[NKB][2][4]) {
     const int hi = lane >> 5;
-    if (__builtin_expect(need_mask, 0)) {
-        const int limit = limit_of_row() - 4 * hi;
-#pragma unroll
-        for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sacc[kb][r] = 32 * kb + (r & 3) + 8 * (r >> 2) <= limit ? sacc[kb][r] : -INFINITY;
-    }
+    if (__builtin_expect(need_mask, 0)) mask_tile(sacc, hi);
     float mx = -INFINITY;
 #pragma unroll
     for (int kb = 0; kb < NKB; ++kb)
@@ -235,6 +251,13 @@ __device__ __forceinline__ void softmax_tile(v16f (&sacc)[NKB], bool need_mask, 
 #pragma unroll
             for (int r = 0; r < 16; ++r) oacc[d][r] *= alpha;
     }
+}
+
+template <bool LAZY, class LIMIT>
+__device__ __forceinline__ void softmax_tile(v16f (&sacc)[NKB], bool need_mask, LIMIT limit_of_row, int lane, float scale_log2, float& m_run,
+                                             float& l_run, v16f (&oacc)[4], u32 (&pb)[NKB][2][4]) {
+    softmax_tile_masked<LAZY>(sacc, need_mask, [&](v16f (&s)[NKB], int hi) { mask_keys_above(s, limit_of_row(), hi); }, lane, scale_log2, m_run,
+                              l_run, oacc, pb);
 }
 
 // ---------------- O^T += V^T P^T ----------------

@@ -428,6 +428,76 @@ class DecodeEngine:
             self._prompt_layers(h, bufs, attend)
         self._prompt_head(h.view(B, -1, self.hid)[:, -1], prompt_len)
 
+    # ---- verification of a draft tree (no reference counterpart; qserve_amd.append, csrc/append_tree.hip) ---------------------
+    def verify_tree(self, draft_tokens, parents):
+        """Verify one draft tree per sequence in ONE pass and keep the greedy path.  `parents` [n] (n <= 64, the same tree shape for
+        every sequence): parents[i] is the parent of node i, an EARLIER node; node 0 is the root - the current `tokens`, whose K / V
+        are not in the cache yet - and parents[0] = -1.  `draft_tokens` int64 [B, n]: the drafted token of every node (column 0 is
+        replaced by `tokens`).
+
+        The B * n rows run through the is_prompt layer stack with `append_tree` at past = lengths - 1: node i is rotated at position
+        past + depth(i), sees the context and its ancestors, and parks its K / V in slot past + i.  Then logits and argmax for all
+        rows, and per sequence the greedy walk: from the root, descend to the (first) child whose token equals its parent's argmax,
+        until none matches.  `commit_path` moves the accepted nodes' K / V to slots past .. past + m - 1 of every layer; `tokens`
+        becomes the argmax at the last accepted node, `lengths` grow by m - the state m decode steps would have left, so step() /
+        capture() / run() and a further verify_tree (now with ragged lengths) go on from here.  The slots behind the path keep the
+        rejected nodes' bytes: readers mask them by `lengths`, the next writer overwrites them.
+        -> (accept_idx int32 [B, n] - node indices of the path, the first accept_lens[b] of a row are valid -, accept_lens int32 [B],
+        argmax int64 [B, n]), on the device."""
+        from . import append as appendmod
+        cfg, B, dev = self.cfg, self.B, self.dev
+        par = [int(p) for p in (parents.tolist() if hasattr(parents, "tolist") else parents)]
+        n = len(par)
+        assert self.with_lm_head and not self.vocab_parallel and self.tp_world == 1, "verify_tree: single GPU, with the lm_head"
+        assert 1 <= n <= appendmod.MAX_TREE and par[0] == -1 and all(0 <= p < i for i, p in enumerate(par) if i), \
+            "verify_tree: parents[0] = -1 (the root), every other node hangs off an earlier one; at most 64 nodes"
+        assert tuple(draft_tokens.shape) == (B, n) and draft_tokens.dtype == torch.int64
+        max_past = int(self.lengths.max()) - 1
+        assert max_past + n <= self.mb * 64, "verify_tree: the tree does not fit the sequences' page tables"
+        toks = draft_tokens.to(dev).clone()
+        toks[:, 0] = self.tokens
+        cu = torch.arange(0, B + 1, device=dev, dtype=torch.int32) * n
+        past = (self.lengths - 1).to(torch.int32)
+        masks = appendmod.tree_masks_from_parents(par * B, [i * n for i in range(B + 1)]).to(dev)
+        h = torch.index_select(self.embed, 0, toks.reshape(-1))
+
+        def attend(li, qkv):
+            return appendmod.append_tree(qkv, cu, past, self.tables[li], masks, self.H, self.Hkv, self.size_per_token,
+                                         cfg["rope_theta"], self.int4, max_seqlen_q=n, max_past=max_past).reshape(B * n, -1)
+
+        self._prompt_layers(h, self._prompt_buffers(B * n), attend)
+        final = torch.empty_like(h)
+        layernorm_ops.rms_norm(final, h, self.norm_w, cfg["eps"])
+        logits = torch.matmul(final, self.lm_head.t())
+        am = torch.empty((B * n,), dtype=torch.int64, device=dev)
+        argmax_rows_(logits, am)
+        am = am.view(B, n)
+        # the greedy walk, on the host (n <= 64 nodes per sequence)
+        am_h, tok_h = am.cpu().tolist(), toks.cpu().tolist()
+        kids = [[c for c in range(1, n) if par[c] == i] for i in range(n)]
+        idx_h, len_h = [], []
+        for b in range(B):
+            path, cur = [0], 0
+            while True:
+                nxt = next((c for c in kids[cur] if tok_h[b][c] == am_h[b][cur]), None)
+                if nxt is None:
+                    break
+                path.append(nxt)
+                cur = nxt
+            len_h.append(len(path))
+            idx_h.append(path + [0] * (n - len(path)))
+        accept_idx = torch.tensor(idx_h, dtype=torch.int32, device=dev)
+        accept_lens = torch.tensor(len_h, dtype=torch.int32, device=dev)
+        for li in range(len(self.layers)):
+            appendmod.commit_path(self.tables[li], past, accept_idx, accept_lens, self.Hkv, self.size_per_token, self.int4)
+        last = torch.tensor([b * n + idx_h[b][len_h[b] - 1] for b in range(B)], dtype=torch.int64, device=dev)
+        self.hidden.copy_(torch.index_select(h, 0, last))
+        self.final.copy_(torch.index_select(final, 0, last))
+        self.tokens.copy_(torch.index_select(am.reshape(-1), 0, last))      # in place: captured graphs read these tensors
+        self.lengths.add_(accept_lens)
+        self.last_verify_logits = logits.view(B, n, -1)                     # (kept for callers that sample or score themselves)
+        return accept_idx, accept_lens, am
+
     # ---- one decode step (llama_w4a8_unpad.py:330-361 per layer) --------------------------------------------
     def _segments(self):
         """The step as a generator: yields the row-parallel partial output wherever tensor parallelism needs its sum
