@@ -472,6 +472,39 @@ int qs_debug_flash_variant(int variant);
  *   qs_append_attention_split_plan  pure (no device access, deterministic in its arguments): plan5 = {tokens per query tile, query
  *                      tiles, waves per workgroup [the three of qs_append_attention_plan], splits >= 1, KiB of workspace the partial
  *                      records take (0 with one split)}; all zero for an empty launch.  max_past < 0 is QS_EINVAL.
+ *   qs_append_attention_shared  the same attention - by definition what qs_append_attention gives on the same arguments - for a
+ *                      batch cut into num_groups GROUPS of batch-adjacent sequences whose members hold the same leading pages
+ *                      (prefix reuse: a system prompt, a few-shot header).  Device arrays: group_offsets int32 [num_groups + 1] (group g
+ *                      is sequences group_offsets[g] .. group_offsets[g + 1] - 1; the groups partition 0 .. batch - 1), prefix_lens
+ *                      int32 [num_groups], seq_group int32 [batch] (the group of every sequence, non-decreasing).  prefix_lens[g] is
+ *                      the number of leading cached tokens every member of group g has in common.  PRECONDITIONS, kept by the
+ *                      caller: it is a multiple of 64 (whole pages), at most past_lens[b] of every member b, and entry p of a
+ *                      member's K table and of its V table EQUALS the first member's for every p < prefix_lens[g] / 64.  A prefix
+ *                      of 0, a group of one sequence, members with n = 0 and members whose past equals the prefix are legal.
+ *                      Sharing changes who reads the bytes, never a value beyond fp32 summation order: with P >= 1 prefix splits in
+ *                      effect the prefix pages are read ONCE per group, THROUGH THE FIRST MEMBER'S TABLE ONLY, for all the group's
+ *                      new rows (max_group_tokens: an upper bound of a group's new tokens, as max_seqlen_q is of a sequence's), each
+ *                      sequence's pages behind the prefix and its new tokens as in qs_append_attention_split; partial records go to
+ *                      the split-KV workspace (same allocation rule, not enlarged) and a merge launch joins them: two launches on
+ *                      `stream`, nothing outside the rows' H * 128 elements is written, no page is written.  The equal-entries
+ *                      precondition is also what makes the fall-backs correct: without the workspace (its first use inside a stream
+ *                      capture) the entry runs qs_append_attention, and "do not share" runs qs_append_attention_split over the whole
+ *                      past - both read every member's own table.  On a violated precondition no address outside the tables and the
+ *                      pages they name is formed: the device rounds a prefix down to whole pages and cuts it to 64 * max_blocks, group
+ *                      bounds and indices are cut to the batch; a member whose past is shorter than the prefix gets unspecified rows
+ *                      and nothing else is affected.  max_prefix / max_suffix_past: upper-bound HINTS (of prefix_lens, and of
+ *                      past_lens[b] - prefix) for the planner only, negative = 64 * max_blocks, never something a result depends on.
+ *                      num_prefix_splits / num_suffix_splits: 0 asks qs_append_shared_plan, >= 1 forces that count (clamped to 64 and
+ *                      to what the workspace holds); num_prefix_splits = -1 forces "do not share".  Validation as for
+ *                      qs_append_attention, and QS_EINVAL for a null group array, num_groups outside 1 .. batch, a negative count,
+ *                      num_prefix_splits < -1 or num_suffix_splits < 0 - before any device call.  batch, num_tokens, max_seqlen_q or
+ *                      max_group_tokens of 0: QS_OK without a launch.
+ *   qs_append_shared_plan  pure (no device access, deterministic in its arguments): plan8 = {tokens per query tile, query tiles per
+ *                      sequence, waves per workgroup [the three of qs_append_attention_plan], suffix splits S, query tiles per group
+ *                      at max_group_tokens, prefix splits P, record waves (suffix | prefix << 8: the waves of a workgroup that can own
+ *                      a row - a record block exists only for those), KiB of workspace (rounded up)}; all zero for an empty launch.
+ *                      P = 0 means "do not share" - num_groups == batch, max_prefix < 64, or no room in the workspace: S and the KiB
+ *                      are then qs_append_attention_split_plan's for max_prefix + max_suffix_past, the record waves 4.
  * QS_EINVAL: null pointers, bad sizes / head counts / strides;  QS_ENOSUP: head_dim != 128, tokens_per_block != 64, caches
  * without zero points, H / Hkv > 8.
  *
@@ -513,6 +546,14 @@ int qs_append_attention_split(const void* qkv, void* out, const int32_t* cu_seql
                               qs_stream_t stream);
 int qs_append_attention_split_plan(int batch, int max_seqlen_q, int max_past, int num_heads, int num_kv_heads, int int4_kv_cache,
                                    int* plan5);
+int qs_append_attention_shared(const void* qkv, void* out, const int32_t* cu_seqlens_q, const int32_t* past_lens,
+                               const int64_t* kv_pointers, const int32_t* group_offsets, const int32_t* prefix_lens,
+                               const int32_t* seq_group, int num_tokens, int batch, int num_groups, int max_seqlen_q,
+                               int max_group_tokens, int max_blocks, int num_heads, int num_kv_heads, int head_dim, int64_t qkv_stride0,
+                               int64_t out_stride0, int tokens_per_block, int size_per_token, int int4_kv_cache, int kv_cache_with_zeros,
+                               int max_prefix, int max_suffix_past, int num_prefix_splits, int num_suffix_splits, qs_stream_t stream);
+int qs_append_shared_plan(int batch, int max_seqlen_q, int num_groups, int max_group_tokens, int max_prefix, int max_suffix_past,
+                          int num_heads, int num_kv_heads, int int4_kv_cache, int* plan8);
 int qs_append_tree_rope_update_kv_cache(void* qkv, const int32_t* cu_seqlens_q, const int32_t* past_lens,
                                         const int64_t* kv_pointers, const uint64_t* tree_mask, int num_tokens, int batch,
                                         int max_blocks, int head_num, int kv_head_num, int tokens_per_block, int size_per_token,

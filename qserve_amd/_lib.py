@@ -76,6 +76,9 @@ SIGNATURES = {
     "qs_append_attention_plan": (_i, [_i, _i, _i, _i, _vp]),
     "qs_append_attention_split": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i64, _i64, _i, _i, _i, _i, _i, _i, _vp]),
     "qs_append_attention_split_plan": (_i, [_i, _i, _i, _i, _i, _i, _vp]),
+    "qs_append_attention_shared": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i64, _i64, _i, _i, _i, _i,
+                                        _i, _i, _i, _i, _vp]),
+    "qs_append_shared_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "qs_append_tree_rope_update_kv_cache": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _vp]),
     "qs_append_tree_attention": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i64, _i64, _i, _i, _i, _i, _i, _i, _vp]),
     "qs_kv_cache_commit_path": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),

@@ -13,6 +13,13 @@ un-split `qs_append_attention`; otherwise `qs_append_attention_split` cuts every
 workgroups of their own and merges their partial results - `num_splits` ranges when given, else what the planner
 (`qserve_amd.plan.append_attention_split_plan`) picks for the upper-bound hint `max_past`.
 
+Shared prefixes (prefix reuse): batch-adjacent sequences whose K / V tables name the SAME pages for a common leading context form a
+group; `shared_prefix_groups` builds the three device arrays that describe the groups:
+
+    append_attention_shared       append_attention's result with a group's common pages read ONCE for all its new rows (through the
+                                  first member's table), each sequence's own pages and new tokens behind them, one merge
+    append_shared                 the (unchanged) writer, then append_attention_shared
+
 `past = 0` is the prefill pair (apply_bias_rope_update_kv_cache + flash_attn_varlen_func), `n = 1` is single_query_attention.
 
 Tree-draft verification (several drafted candidates per position, verified in one pass): the n <= 64 new rows of a sequence are the
@@ -25,7 +32,7 @@ token j of its own sequence"; `tree_masks_from_parents` builds ancestor-closed w
     commit_path                        after acceptance: slots past .. past + m - 1 receive the accepted path's K / V; the slots behind
                                        them keep the rejected nodes' stale bytes, which every reader masks by the sequence length
 
-Backed by qserve_amd/csrc/append_attention.hip, append_attention_split.hip, append_tree.hip and the offset-aware writers in
+Backed by qserve_amd/csrc/append_attention.hip, append_attention_split.hip, append_shared.hip, append_tree.hip and the offset-aware writers in
 attention.hip."""
 import torch
 
@@ -103,6 +110,92 @@ def append(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, s
                                 int4_kv)
     return append_attention(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, size_per_token, int4_kv,
                             max_seqlen_q=max_seqlen_q, max_past=max_past, num_splits=num_splits)
+
+
+# ---- shared prefixes ------------------------------------------------------------------------------------------------------------
+def shared_prefix_groups(group_sizes, prefix_lens, device=None, batch=None):
+    """Groups of batch-adjacent sequences with a common cached prefix -> (group_offsets int32 [groups + 1], prefix_lens int32 [groups],
+    seq_group int32 [batch]) on `device` (built on the host).  Group g is the next `group_sizes[g]` sequences of the batch and shares
+    `prefix_lens[g]` leading tokens - whole 64-token pages, 0 for "nothing shared".  Raises on an empty list, lists of different
+    lengths, a size below 1, sizes that do not sum to `batch` (when given), and a prefix that is negative or no multiple of 64."""
+    sizes = [int(x) for x in (group_sizes.tolist() if hasattr(group_sizes, "tolist") else group_sizes)]
+    pref = [int(x) for x in (prefix_lens.tolist() if hasattr(prefix_lens, "tolist") else prefix_lens)]
+    if not sizes or len(sizes) != len(pref):
+        raise RuntimeError(f"shared_prefix_groups: {len(sizes)} group sizes and {len(pref)} prefix lengths (one each per group, at least one)")
+    if any(n < 1 for n in sizes):
+        raise RuntimeError(f"shared_prefix_groups: group sizes {sizes}: a group has at least one sequence")
+    if batch is not None and sum(sizes) != int(batch):
+        raise RuntimeError(f"shared_prefix_groups: group sizes {sizes} sum to {sum(sizes)}, not to the batch {batch}")
+    if any(p < 0 or p % 64 for p in pref):
+        raise RuntimeError(f"shared_prefix_groups: prefix lengths {pref}: a shared prefix is a non-negative multiple of 64 (whole pages)")
+    offs = [0]
+    for n in sizes:
+        offs.append(offs[-1] + n)
+    seq_group = [g for g, n in enumerate(sizes) for _ in range(n)]
+    mk = lambda x: torch.tensor(x, dtype=torch.int32, device=device)      # noqa: E731
+    return mk(offs), mk(pref), mk(seq_group)
+
+
+def append_attention_shared(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, size_per_token, int4_kv, groups,
+                            max_seqlen_q=None, out=None, max_group_tokens=None, max_prefix=None, max_suffix_past=None,
+                            num_prefix_splits=None, num_suffix_splits=None):
+    """`append_attention` (qkv ALREADY rotated -> out fp16 [T, H, 128]) for a batch in groups with common leading pages.  `groups`: the
+    triple of `shared_prefix_groups`; the caller keeps the members' table entries below prefix / 64 equal to the first member's and
+    every member's past >= its group's prefix.  `max_group_tokens`: an upper bound of a group's new tokens (default: all T rows);
+    `max_prefix` / `max_suffix_past`: upper bounds of the prefixes / of past - prefix known on the host - planner hints, never
+    something the result depends on.  `num_prefix_splits` / `num_suffix_splits`: None asks the planner, >= 1 forces the count,
+    `num_prefix_splits=-1` forces "do not share" (the split-KV call over the whole past)."""
+    what = "append.append_attention_shared"
+    batch = _check_common(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, size_per_token, int4_kv, what)
+    try:
+        group_offsets, prefix_lens, seq_group = groups
+    except (TypeError, ValueError):
+        raise RuntimeError(f"{what}: groups must be the (group_offsets, prefix_lens, seq_group) triple of shared_prefix_groups") from None
+    expect(group_offsets, torch.int32, "group_offsets")
+    expect(prefix_lens, torch.int32, "prefix_lens")
+    expect(seq_group, torch.int32, "seq_group")
+    ngroups = prefix_lens.numel()
+    if group_offsets.dim() != 1 or prefix_lens.dim() != 1 or seq_group.dim() != 1 or group_offsets.numel() != ngroups + 1 or \
+            seq_group.numel() != batch or not (batch == 0 or 1 <= ngroups <= batch):
+        raise RuntimeError(f"{what}: group_offsets must be [groups + 1], prefix_lens [groups] and seq_group [batch] with 1 <= groups <= batch, "
+                           f"got {tuple(group_offsets.shape)}, {tuple(prefix_lens.shape)}, {tuple(seq_group.shape)} for batch {batch}")
+    T, H = qkv.size(0), int(num_heads)
+    if out is None:
+        out = torch.empty((T, H, 128), dtype=torch.float16, device=qkv.device)
+    else:
+        expect(out, torch.float16, "out", contiguous=False)
+        if tuple(out.shape) != (T, H, 128) or out.stride(2) != 1 or out.stride(1) != 128 or out.stride(0) % 8 != 0:
+            raise RuntimeError(f"{what}: out must be [T, H, 128] with contiguous heads and a row stride that is a multiple of 8")
+    msq = T if max_seqlen_q is None else int(max_seqlen_q)
+    mgt = T if max_group_tokens is None else int(max_group_tokens)
+    if msq < 0 or mgt < 0:
+        raise RuntimeError(f"{what}: max_seqlen_q={msq}, max_group_tokens={mgt}")
+    if num_prefix_splits is not None and (int(num_prefix_splits) < -1 or int(num_prefix_splits) == 0):
+        raise RuntimeError(f"{what}: num_prefix_splits={num_prefix_splits} (None, a forced count >= 1, or -1 = do not share)")
+    if num_suffix_splits is not None and int(num_suffix_splits) < 1:
+        raise RuntimeError(f"{what}: num_suffix_splits={num_suffix_splits} (None, or a forced count >= 1)")
+    hint = lambda v: -1 if v is None else min(max(int(v), 0), 2 ** 31 - 1)      # noqa: E731
+    with guard(qkv):
+        check(lib.qs_append_attention_shared(ptr(qkv), ptr(out), ptr(cu_seqlens_q), ptr(past_lens), ptr(kv_pointers), ptr(group_offsets),
+                                             ptr(prefix_lens), ptr(seq_group), T, batch, ngroups, min(msq, T), min(mgt, T),
+                                             kv_pointers.size(-1), H, int(num_kv_heads), 128, qkv.stride(0), out.stride(0), 64,
+                                             int(size_per_token), int(bool(int4_kv)), 1, hint(max_prefix), hint(max_suffix_past),
+                                             0 if num_prefix_splits is None else int(num_prefix_splits),
+                                             0 if num_suffix_splits is None else int(num_suffix_splits), stream()), what)
+    return out
+
+
+def append_shared(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, size_per_token, rope_theta, int4_kv, groups,
+                  max_seqlen_q=None, max_group_tokens=None, max_prefix=None, max_suffix_past=None, num_prefix_splits=None,
+                  num_suffix_splits=None):
+    """Writer, then shared-prefix attention.  The writer is append_rope_update_kv_cache: new token i goes to slot past + i >= prefix, a
+    page the sequence owns - the shared pages are only read."""
+    append_rope_update_kv_cache(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, size_per_token, rope_theta,
+                                int4_kv)
+    return append_attention_shared(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, size_per_token, int4_kv, groups,
+                                   max_seqlen_q=max_seqlen_q, max_group_tokens=max_group_tokens, max_prefix=max_prefix,
+                                   max_suffix_past=max_suffix_past, num_prefix_splits=num_prefix_splits,
+                                   num_suffix_splits=num_suffix_splits)
 
 
 # ---- tree-draft verification ------------------------------------------------------------------------------------------------

@@ -428,6 +428,61 @@ class DecodeEngine:
             self._prompt_layers(h, bufs, attend)
         self._prompt_head(h.view(B, -1, self.hid)[:, -1], prompt_len)
 
+    def prefill_shared(self, prefix_tokens, suffix_tokens, chunk=None):
+        """`prefill_chunked` for B prompts that begin with the SAME `prefix_tokens` [P] and go on with their own `suffix_tokens`
+        [B, S] (S >= 1), the common part computed and stored once.  With P64 = 64 * (P // 64), the whole pages of the prefix:
+          1. the first P64 prefix tokens run ONCE, as a single sequence over row 0 of the page tables (chunks through `append`);
+          2. entries < P64 / 64 of every sequence's K and V table rows are pointed at sequence 0's pages, in every layer;
+          3. every sequence's remaining P - P64 prefix tokens and its S suffix tokens run in chunks through `append_shared` with one
+             group of B, prefix P64 and past = P64 + c0: the shared pages are read once per layer and chunk for the whole batch.
+        Ends in the state `prefill` ends in (`hidden`, `tokens`, lengths = P + S + 1); step() / capture() / run() go on unchanged - the
+        decode kernels only read the aliased pages and write at slots >= P64.  `chunk`: tokens per sequence and pass (None: no
+        chunking).  Single GPU, with the lm_head."""
+        from . import append as appendmod
+        cfg, B, dev = self.cfg, self.B, self.dev
+        assert self.with_lm_head and not self.vocab_parallel and self.tp_world == 1, "prefill_shared: single GPU, with the lm_head"
+        prefix_tokens, suffix_tokens = prefix_tokens.to(dev), suffix_tokens.to(dev)
+        assert prefix_tokens.dim() == 1 and suffix_tokens.dim() == 2 and suffix_tokens.size(0) == B and suffix_tokens.size(1) >= 1, \
+            "prefill_shared: prefix_tokens [P], suffix_tokens [B, S] with S >= 1"
+        P, S = prefix_tokens.numel(), suffix_tokens.size(1)
+        P64 = 64 * (P // 64)
+        own = torch.cat([prefix_tokens[P64:].unsqueeze(0).expand(B, -1), suffix_tokens], dim=1)      # [B, R]: what every sequence runs itself
+        R = own.size(1)
+        assert P + S + 1 <= self.max_len and (chunk is None or chunk >= 1)
+        chunk = max(P64, R) if chunk is None else min(chunk, max(P64, R))
+        bufs = self._prompt_buffers(max(B * min(chunk, R), min(chunk, P64)))
+        # 1. the whole pages of the prefix, once, through row 0 of the tables
+        for c0 in range(0, P64, chunk):
+            n = min(chunk, P64 - c0)
+            h = torch.index_select(self.embed, 0, prefix_tokens[c0:c0 + n])
+            cu1 = torch.tensor([0, n], dtype=torch.int32, device=dev)
+            past = torch.full((1,), c0, dtype=torch.int32, device=dev)
+
+            def attend(li, qkv):
+                return appendmod.append(qkv, cu1, past, self.tables[li][0:1], self.H, self.Hkv, self.size_per_token,
+                                        cfg["rope_theta"], self.int4, max_seqlen_q=n, max_past=c0).reshape(n, -1)
+
+            self._prompt_layers(h, bufs, attend)
+        # 2. every sequence names sequence 0's prefix pages
+        for t in self.tables:
+            t[:, :, :P64 // 64] = t[0:1, :, :P64 // 64]
+        # 3. the rest of every prompt, the shared pages read once for the batch
+        groups = appendmod.shared_prefix_groups([B], [P64], dev, batch=B)
+        h = None
+        for c0 in range(0, R, chunk):
+            n = min(chunk, R - c0)
+            h = torch.index_select(self.embed, 0, own[:, c0:c0 + n].reshape(-1))
+            cu = torch.arange(0, B + 1, device=dev, dtype=torch.int32) * n
+            past = torch.full((B,), P64 + c0, dtype=torch.int32, device=dev)
+
+            def attend(li, qkv):
+                return appendmod.append_shared(qkv, cu, past, self.tables[li], self.H, self.Hkv, self.size_per_token, cfg["rope_theta"],
+                                               self.int4, groups, max_seqlen_q=n, max_group_tokens=B * n, max_prefix=P64,
+                                               max_suffix_past=c0).reshape(B * n, -1)
+
+            self._prompt_layers(h, bufs, attend)
+        self._prompt_head(h.view(B, -1, self.hid)[:, -1], P + S)
+
     # ---- verification of a draft tree (no reference counterpart; qserve_amd.append, csrc/append_tree.hip) ---------------------
     def verify_tree(self, draft_tokens, parents):
         """Verify one draft tree per sequence in ONE pass and keep the greedy path.  `parents` [n] (n <= 64, the same tree shape for

@@ -49,3 +49,17 @@ def append_attention_split_plan(batch, max_seqlen_q, max_past, num_heads, num_kv
     check(lib.qs_append_attention_split_plan(batch, max_seqlen_q, max_past, num_heads, num_kv_heads, int(bool(int4_kv_cache)),
                                              C.cast(buf, C.c_void_p)), "append attention split plan")
     return dict(tile_tokens=buf[0], q_tiles=buf[1], waves=buf[2], splits=buf[3], workspace_bytes=buf[4] * 1024)
+
+
+def append_shared_plan(batch, max_seqlen_q, num_groups, max_group_tokens, max_prefix, max_suffix_past, num_heads, num_kv_heads,
+                       int4_kv_cache=True):
+    """-> dict(tile_tokens, q_tiles, waves, suffix_splits, group_q_tiles, prefix_splits, rec_waves_suffix, rec_waves_prefix,
+    workspace_bytes): what `qs_append_attention_shared` launches when it is asked to choose (`qs_append_shared_plan`).  The first
+    three are `append_attention_plan`'s.  `prefix_splits` = 0: "do not share" - the split entry's launch over the whole past
+    (`suffix_splits` and the workspace are then `append_attention_split_plan`'s for max_prefix + max_suffix_past).  All zero for an
+    empty launch."""
+    buf = (C.c_int * 8)()
+    check(lib.qs_append_shared_plan(batch, max_seqlen_q, num_groups, max_group_tokens, max_prefix, max_suffix_past, num_heads,
+                                    num_kv_heads, int(bool(int4_kv_cache)), C.cast(buf, C.c_void_p)), "append shared plan")
+    return dict(tile_tokens=buf[0], q_tiles=buf[1], waves=buf[2], suffix_splits=buf[3], group_q_tiles=buf[4], prefix_splits=buf[5],
+                rec_waves_suffix=buf[6] & 0xFF, rec_waves_prefix=buf[6] >> 8, workspace_bytes=buf[7] * 1024)
