@@ -529,7 +529,22 @@ int qs_debug_flash_variant(int variant);
  *                      max_accept <= 64 (QS_EINVAL otherwise).  Every source is read before any destination is written (a source may
  *                      be another move's destination; moves cross page boundaries); identity moves are skipped; no other byte of any
  *                      page changes.  Slots >= past + accept_lens[b] KEEP WHAT THEY HOLD - the rejected nodes' stale K / V -, which every
- *                      reader masks by the sequence length and the next writer overwrites.  The caller advances its lengths. */
+ *                      reader masks by the sequence length and the next writer overwrites.  The caller advances its lengths.
+ *   qs_tree_accept_greedy  the greedy walk over the verified tree, on the device (nothing is read back).  tokens / argmax: int64 [T], 8-byte
+ *                      aligned - the token every node carries and the model's arg-max at every node; parents: int32 [T], an index INTO THE
+ *                      NODE'S OWN SEQUENCE, -1 = hangs off the context; sequence b has n = cu_seqlens_q[b + 1] - cu_seqlens_q[b] nodes, cut
+ *                      to 64.  If n >= 1 node 0 is accepted; from the current node cur the next one is the LOWEST c with cur < c < n,
+ *                      parents[c] == cur and tokens[c] == argmax[cur]; the walk ends when there is none or the path holds max_accept
+ *                      (1 .. 64) nodes.  accept_idx int32 [batch, max_accept]: the path, 0 behind it; accept_lens int32 [batch]: its length;
+ *                      last_row int64 [batch] (may be null): cu_seqlens_q[b] + the last accepted node, the global row; next_token int64
+ *                      [batch] (may be null): argmax[last_row[b]].  n = 0: length 0, last_row -1, next_token[b] NOT written.  Only c > cur is
+ *                      a candidate, so the walk increases strictly whatever parents holds (p >= i, p < -1, self-loops): it ends within n
+ *                      levels and reads nothing outside the sequence's rows.  QS_EINVAL before any device call: a null required pointer,
+ *                      negative sizes, max_accept outside 1 .. 64, a misaligned 8-byte array.  batch or num_tokens of 0: QS_OK, no launch.
+ *   qs_kv_cache_commit_path_layers  qs_kv_cache_commit_path for every layer in ONE launch.  layer_tables: device int64 [num_layers], 8-byte
+ *                      aligned, entry l = the device address of layer l's kv_pointers [batch, 2, max_blocks]; past_lens, accept_idx and
+ *                      accept_lens are common to the layers.  Per (layer, K | V, KV head, sequence) the rule is qs_kv_cache_commit_path's,
+ *                      word for word - the pages end byte-identical to num_layers calls of it.  Validation as there, plus num_layers >= 1. */
 int qs_append_rope_update_kv_cache(void* qkv, const int32_t* cu_seqlens_q, const int32_t* past_lens,
                                    const int64_t* kv_pointers, int num_tokens, int batch, int max_blocks, int head_num,
                                    int kv_head_num, int tokens_per_block, int size_per_token, int rotary_embedding_dim,
@@ -567,6 +582,13 @@ int qs_append_tree_attention(const void* qkv, void* out, const int32_t* cu_seqle
 int qs_kv_cache_commit_path(const int64_t* kv_pointers, const int32_t* past_lens, const int32_t* accept_idx,
                             const int32_t* accept_lens, int batch, int max_accept, int max_blocks, int kv_head_num,
                             int tokens_per_block, int size_per_token, int int4_kv_cache, int kv_cache_with_zeros, qs_stream_t stream);
+int qs_tree_accept_greedy(const int64_t* tokens, const int64_t* argmax, const int32_t* parents, const int32_t* cu_seqlens_q,
+                          int num_tokens, int batch, int max_accept, int32_t* accept_idx, int32_t* accept_lens, int64_t* last_row,
+                          int64_t* next_token, qs_stream_t stream);
+int qs_kv_cache_commit_path_layers(const int64_t* layer_tables, int num_layers, const int32_t* past_lens, const int32_t* accept_idx,
+                                   const int32_t* accept_lens, int batch, int max_accept, int max_blocks, int kv_head_num,
+                                   int tokens_per_block, int size_per_token, int int4_kv_cache, int kv_cache_with_zeros,
+                                   qs_stream_t stream);
 
 /* Timing tool (scripts/trace_attn.py): device-to-device copy of the first `bytes` of the split-KV workspace, where the
  * trace instantiation of the KV4 decode attention (qs_set_attention_variant(232)) leaves its s_memtime stamps.

@@ -32,8 +32,12 @@ token j of its own sequence"; `tree_masks_from_parents` builds ancestor-closed w
     commit_path                        after acceptance: slots past .. past + m - 1 receive the accepted path's K / V; the slots behind
                                        them keep the rejected nodes' stale bytes, which every reader masks by the sequence length
 
-Backed by qserve_amd/csrc/append_attention.hip, append_attention_split.hip, append_shared.hip, append_tree.hip and the offset-aware writers in
-attention.hip."""
+    accept_greedy                      the greedy walk over the verified tree on the device: path, its length, the last accepted row and
+                                       the token to go on with - nothing is read back
+    commit_path_layers                 commit_path for every layer in one launch (`layer_table_pointers` builds its table of tables)
+
+Backed by qserve_amd/csrc/append_attention.hip, append_attention_split.hip, append_shared.hip, append_tree.hip, tree_accept.hip and the
+offset-aware writers in attention.hip."""
 import torch
 
 from .backend._util import check, expect, guard, lib, ptr, stream
@@ -305,3 +309,119 @@ def commit_path(kv_pointers, past_lens, accept_idx, accept_lens, num_kv_heads, s
     with guard(kv_pointers):
         check(lib.qs_kv_cache_commit_path(ptr(kv_pointers), ptr(past_lens), ptr(accept_idx), ptr(accept_lens), batch, accept_idx.size(1),
                                           kv_pointers.size(-1), Hkv, 64, int(size_per_token), int(bool(int4_kv)), 1, stream()), what)
+
+
+# ---- the tail of a verification on the device (csrc/tree_accept.hip) ---------------------------------------------------------------
+def _expect_host(t, dtype, name):
+    """The host-side part of `expect` (type, dtype): lets the shape checks below come before the device check."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if t.dtype != dtype:
+        raise RuntimeError(f"expected scalar type {dtype} for {name} but found {t.dtype}")
+
+
+def accept_greedy(tokens, argmax, parents, cu_seqlens_q, max_accept=None, out=None):
+    """The greedy walk of tree verification, on the device.  `tokens` / `argmax` int64 [T]: the token every node carries and the
+    model's arg-max at every node; `parents` int32 [T]: the parent of a node as an index INTO ITS OWN SEQUENCE, -1 = hangs off the
+    context; `cu_seqlens_q` int32 [batch + 1] (a sequence's nodes beyond 64 are ignored).  Per sequence with n >= 1 nodes: node 0 is
+    accepted; from the current node `cur` the walk goes to the LOWEST c > cur with parents[c] == cur and tokens[c] == argmax[cur], until
+    there is none or the path holds `max_accept` nodes (1 .. 64; default: min(T, 64)).  Malformed parents cannot make it loop or read
+    elsewhere: only c > cur is ever a candidate.
+    -> (accept_idx int32 [batch, max_accept] - the path, 0 behind it -, accept_lens int32 [batch], last_row int64 [batch] - the global row
+    of the last accepted node, -1 for an empty sequence -, next_token int64 [batch] - argmax[last_row]; the entry of an empty sequence is
+    NOT written: 0 in a tensor allocated here).  `out`: the four tensors to write into (a captured graph's persistent buffers)."""
+    what = "append.accept_greedy"
+    for t, dt, name in ((tokens, torch.int64, "tokens"), (argmax, torch.int64, "argmax"), (parents, torch.int32, "parents"),
+                        (cu_seqlens_q, torch.int32, "cu_seqlens_q")):
+        _expect_host(t, dt, name)
+    if tokens.dim() != 1 or argmax.dim() != 1 or parents.dim() != 1 or argmax.numel() != tokens.numel() or parents.numel() != tokens.numel():
+        raise RuntimeError(f"{what}: tokens, argmax and parents must be [T], one entry per node, got {tuple(tokens.shape)}, "
+                           f"{tuple(argmax.shape)}, {tuple(parents.shape)}")
+    if cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() < 1:
+        raise RuntimeError(f"{what}: cu_seqlens_q must be [batch + 1], got {tuple(cu_seqlens_q.shape)}")
+    T, batch = tokens.numel(), cu_seqlens_q.numel() - 1
+    ma = max(1, min(T, MAX_TREE)) if max_accept is None else int(max_accept)
+    if not 1 <= ma <= MAX_TREE:
+        raise RuntimeError(f"{what}: max_accept={ma}: a path has 1 .. {MAX_TREE} nodes")
+    if out is not None:
+        try:
+            accept_idx, accept_lens, last_row, next_token = out
+        except (TypeError, ValueError):
+            raise RuntimeError(f"{what}: out must be the (accept_idx, accept_lens, last_row, next_token) quadruple") from None
+        for t, dt, name in ((accept_idx, torch.int32, "accept_idx"), (accept_lens, torch.int32, "accept_lens"),
+                            (last_row, torch.int64, "last_row"), (next_token, torch.int64, "next_token")):
+            _expect_host(t, dt, name)
+        if tuple(accept_idx.shape) != (batch, ma) or any(tuple(t.shape) != (batch,) for t in (accept_lens, last_row, next_token)):
+            raise RuntimeError(f"{what}: out must be accept_idx [batch, max_accept] = [{batch}, {ma}] and accept_lens, last_row, next_token "
+                               f"[{batch}], got {tuple(accept_idx.shape)}, {tuple(accept_lens.shape)}, {tuple(last_row.shape)}, "
+                               f"{tuple(next_token.shape)}")
+    for t, dt, name in ((tokens, torch.int64, "tokens"), (argmax, torch.int64, "argmax"), (parents, torch.int32, "parents"),
+                        (cu_seqlens_q, torch.int32, "cu_seqlens_q")):
+        expect(t, dt, name)
+    if out is None:
+        d = tokens.device
+        accept_idx = torch.empty((batch, ma), dtype=torch.int32, device=d)
+        accept_lens = torch.empty((batch,), dtype=torch.int32, device=d)
+        last_row = torch.empty((batch,), dtype=torch.int64, device=d)
+        next_token = torch.zeros((batch,), dtype=torch.int64, device=d)
+    else:
+        for t, dt, name in ((accept_idx, torch.int32, "accept_idx"), (accept_lens, torch.int32, "accept_lens"),
+                            (last_row, torch.int64, "last_row"), (next_token, torch.int64, "next_token")):
+            expect(t, dt, name)
+    with guard(tokens):
+        check(lib.qs_tree_accept_greedy(ptr(tokens), ptr(argmax), ptr(parents), ptr(cu_seqlens_q), T, batch, ma, ptr(accept_idx),
+                                        ptr(accept_lens), ptr(last_row), ptr(next_token), stream()), what)
+    return accept_idx, accept_lens, last_row, next_token
+
+
+def layer_table_pointers(tables):
+    """Per-layer pointer tables (each int64 [batch, 2, max_blocks], all of one shape, on one device) -> int64 [L] on that device: entry l
+    is the device address of tables[l] - what commit_path_layers takes.  Built on the host, once per set of tables; the result keeps
+    references to the tables, so the addresses stay valid as long as it lives."""
+    what = "append.layer_table_pointers"
+    tables = tuple(tables)
+    if not tables:
+        raise RuntimeError(f"{what}: at least one layer")
+    for i, t in enumerate(tables):
+        _expect_host(t, torch.int64, f"tables[{i}]")
+        if t.dim() != 3 or t.size(1) != 2 or t.shape != tables[0].shape:
+            raise RuntimeError(f"{what}: every table must be [batch, 2, max_blocks] of one shape, got {tuple(t.shape)} for layer {i}")
+    for i, t in enumerate(tables):
+        expect(t, torch.int64, f"tables[{i}]")
+        if t.device != tables[0].device:
+            raise RuntimeError(f"{what}: tables[{i}] is on {t.device}, tables[0] on {tables[0].device}")
+    out = torch.tensor([t.data_ptr() for t in tables], dtype=torch.int64).to(tables[0].device)
+    out._qs_tables = tables          # (keeps the pointed-to tensors alive)
+    return out
+
+
+def commit_path_layers(layer_tables, past_lens, accept_idx, accept_lens, max_blocks, num_kv_heads, size_per_token, int4_kv):
+    """`commit_path` for every layer in ONE launch.  `layer_tables` int64 [L]: `layer_table_pointers` of the layers' kv_pointers
+    [batch, 2, max_blocks]; `max_blocks`: their last dimension; past_lens, accept_idx and accept_lens as for commit_path, common to the
+    layers.  The pages end byte-identical to L calls of commit_path."""
+    what = "append.commit_path_layers"
+    for t, dt, name in ((layer_tables, torch.int64, "layer_tables"), (past_lens, torch.int32, "past_lens"),
+                        (accept_idx, torch.int32, "accept_idx"), (accept_lens, torch.int32, "accept_lens")):
+        _expect_host(t, dt, name)
+    if layer_tables.dim() != 1 or layer_tables.numel() < 1:
+        raise RuntimeError(f"{what}: layer_tables must be int64 [layers] with at least one layer, got {tuple(layer_tables.shape)}")
+    batch = past_lens.numel()
+    if past_lens.dim() != 1 or accept_idx.dim() != 2 or accept_idx.size(0) != batch or accept_lens.dim() != 1 or accept_lens.numel() != batch:
+        raise RuntimeError(f"{what}: past_lens must be [batch], accept_idx [batch, max_accept] and accept_lens [batch]")
+    if accept_idx.size(1) > MAX_TREE:
+        raise RuntimeError(f"{what}: max_accept={accept_idx.size(1)}: a path has at most {MAX_TREE} nodes")
+    Hkv, mb = int(num_kv_heads), int(max_blocks)
+    if mb <= 0:
+        raise RuntimeError(f"{what}: max_blocks={mb}")
+    if Hkv <= 0 or int(size_per_token) != Hkv * (64 if int4_kv else 128):
+        raise RuntimeError(f"{what}: size_per_token={size_per_token}, expected {Hkv * (64 if int4_kv else 128)}")
+    tabs = getattr(layer_tables, "_qs_tables", None)
+    if tabs is not None and (tabs[0].size(0) != batch or tabs[0].size(-1) != mb):
+        raise RuntimeError(f"{what}: the layers' tables are {tuple(tabs[0].shape)}, not [batch, 2, max_blocks] = [{batch}, 2, {mb}]")
+    for t, dt, name in ((layer_tables, torch.int64, "layer_tables"), (past_lens, torch.int32, "past_lens"),
+                        (accept_idx, torch.int32, "accept_idx"), (accept_lens, torch.int32, "accept_lens")):
+        expect(t, dt, name)
+    with guard(layer_tables):
+        check(lib.qs_kv_cache_commit_path_layers(ptr(layer_tables), layer_tables.numel(), ptr(past_lens), ptr(accept_idx), ptr(accept_lens),
+                                                 batch, accept_idx.size(1), mb, Hkv, 64, int(size_per_token), int(bool(int4_kv)), 1,
+                                                 stream()), what)

@@ -24,6 +24,7 @@
 //              EVERY source into LDS, takes a barrier, then stores.  Identity moves are skipped; nothing else in a page is written;
 //              slots >= past + accept_len keep what they hold (every reader masks them).  Vector stores only.
 #include "append_walk.h"
+#include "kv_commit.h"
 
 namespace {
 
@@ -116,7 +117,8 @@ __global__ __launch_bounds__(64 * NWV, 2) void append_tree_attention_split_kerne
 // ---- path commit.  grid = (KV heads, 2 = K | V, sequences), 256 threads; DHB = bytes per cached token and head (64 KV4, 128 KV8).
 // A page: data [Hkv][64][DHB], then fp16 scales [Hkv][64], then fp16 zeros [Hkv][64].  Move k: thread (k, c) of the data pass copies
 // the 16-byte chunk c of the token, thread k of the parameter pass its scale and zero.  A move whose source or destination lies beyond
-// the pointer table, or whose index is not in 0 .. 63, is dropped.
+// the pointer table, or whose index is not in 0 .. 63, is dropped.  The moves themselves are kv_commit.h's, shared with the all-layers
+// launch of tree_accept.hip.
 template <int DHB>
 __global__ __launch_bounds__(256) void kv_commit_path_kernel(const int64_t* __restrict__ kv_pointers, const int* __restrict__ past_lens,
                                                              const int* __restrict__ accept_idx, const int* __restrict__ accept_lens,
@@ -130,33 +132,7 @@ __global__ __launch_bounds__(256) void kv_commit_path_kernel(const int64_t* __re
     const int past = past_lens[b];
     const int64_t* tab = kv_pointers + ((size_t)b * 2 + which) * max_blocks;
     const int* idx = accept_idx + (size_t)b * max_accept;
-    const size_t par_off = (size_t)kv_head_num * BN * DHB;      // the scales behind the data, the zeros kv_head_num * 64 fp16 further
-    auto moves = [&](int k, int& src, int& dst) {               // -> does move k change anything?
-        const int i = idx[k];
-        src = past + i, dst = past + k;
-        return i != k && i >= 0 && i < MAX_TREE && past >= 0 && src < max_blocks * BN && dst < max_blocks * BN;
-    };
-    auto token = [&](int pos) { return reinterpret_cast<uint8_t*>(tab[pos >> 6]) + ((size_t)hkv * BN + (pos & 63)) * DHB; };
-    auto param = [&](int pos) {
-        return reinterpret_cast<uint16_t*>(reinterpret_cast<uint8_t*>(tab[pos >> 6]) + par_off) + hkv * BN + (pos & 63);
-    };
-    int src, dst;
-    for (int j = threadIdx.x; j < m * CH; j += blockDim.x)
-        if (moves(j / CH, src, dst)) s_data[j] = *reinterpret_cast<const v4u*>(token(src) + (j % CH) * 16);
-    for (int k = threadIdx.x; k < m; k += blockDim.x)
-        if (moves(k, src, dst)) {
-            const uint16_t* p = param(src);
-            s_par[k] = (u32)p[0] | ((u32)p[kv_head_num * BN] << 16);
-        }
-    __syncthreads();                                     // every source is read (its data sits in LDS) before any destination is written
-    for (int j = threadIdx.x; j < m * CH; j += blockDim.x)
-        if (moves(j / CH, src, dst)) *reinterpret_cast<v4u*>(token(dst) + (j % CH) * 16) = s_data[j];
-    for (int k = threadIdx.x; k < m; k += blockDim.x)
-        if (moves(k, src, dst)) {
-            uint16_t* p = param(dst);
-            p[0] = (uint16_t)(s_par[k] & 0xFFFFu);
-            p[kv_head_num * BN] = (uint16_t)(s_par[k] >> 16);
-        }
+    qs_commit::commit_path_moves<DHB>(tab, idx, m, past, hkv, max_blocks, kv_head_num, s_data, s_par);      // the rule itself: kv_commit.h
 }
 
 }  // namespace

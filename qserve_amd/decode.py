@@ -266,6 +266,13 @@ class DecodeEngine:
             self.head_cand_res = self.proj_res.view(-1)[:n].view(tp_world, B, 8)  # the sum over the ranks
         self.graph = None
         self.pieces = None
+        # an integer upper bound of `lengths`, kept on the host: set by the prefill entries, + 1 per step() / run(), + n per device-walk
+        # verify_tree (which cannot know how many nodes were accepted without reading the device).  A planner hint and the "does it fit
+        # the page tables" bound only - no result depends on it.  sync_length_bound() makes it exact again, at the price of one read-back.
+        self._len_bound = prompt_len
+        self._tree_cache = {}            # parent tuple -> the per-tree device constants of the device-walk verify_tree
+        self._layer_tables = None        # append.layer_table_pointers(self.tables), built on first use
+        self.verify_graph = None
 
     # ---- fill the cache for positions [0, prompt_len) through the prefill writer (random K/V source) ----------
     def prefill_cache(self, prompt_len, chunk=8):
@@ -281,6 +288,7 @@ class DecodeEngine:
                 work, seq, pad, self.tables[li], self.H, self.Hkv, prompt_len, 64, self.size_per_token, 128,
                 self.cfg["rope_theta"], 8192, True, self.int4, True)
         self.lengths.fill_(prompt_len + 1)
+        self._len_bound = prompt_len + 1
         torch.cuda.synchronize()
 
     # ---- real prefill: the reference's is_prompt=True path (llama_w4a8_unpad.py:199-243, 330-361) -------------
@@ -366,6 +374,7 @@ class DecodeEngine:
             logits = torch.matmul(self.final, self.lm_head.t())
             argmax_rows_(logits, self.tokens)
         self.lengths.fill_(prompt_len + 1)
+        self._len_bound = prompt_len + 1
 
     def prefill(self, prompt_len, tokens=None):
         """Run the prompt through the model: per layer  norm+quant -> qkv GEMM -> apply_bias_rope_update_kv_cache
@@ -484,7 +493,7 @@ class DecodeEngine:
         self._prompt_head(h.view(B, -1, self.hid)[:, -1], P + S)
 
     # ---- verification of a draft tree (no reference counterpart; qserve_amd.append, csrc/append_tree.hip) ---------------------
-    def verify_tree(self, draft_tokens, parents):
+    def verify_tree(self, draft_tokens, parents, device_walk=False):
         """Verify one draft tree per sequence in ONE pass and keep the greedy path.  `parents` [n] (n <= 64, the same tree shape for
         every sequence): parents[i] is the parent of node i, an EARLIER node; node 0 is the root - the current `tokens`, whose K / V
         are not in the cache yet - and parents[0] = -1.  `draft_tokens` int64 [B, n]: the drafted token of every node (column 0 is
@@ -498,7 +507,15 @@ class DecodeEngine:
         capture() / run() and a further verify_tree (now with ragged lengths) go on from here.  The slots behind the path keep the
         rejected nodes' bytes: readers mask them by `lengths`, the next writer overwrites them.
         -> (accept_idx int32 [B, n] - node indices of the path, the first accept_lens[b] of a row are valid -, accept_lens int32 [B],
-        argmax int64 [B, n]), on the device."""
+        argmax int64 [B, n]), on the device.
+
+        `device_walk=True`: the same call with nothing leaving the device after the argument checks - no read-back, no host-built
+        tensor.  The walk is `append.accept_greedy`, the commit ONE `append.commit_path_layers` launch for all layers, the last accepted
+        rows are gathered by index; masks, cu_seqlens, the parents array and the table of layer tables come from a cache keyed by the
+        parent tuple.  The planner hint and the "fits the page tables" bound are the engine's host-side upper bound of `lengths`, which
+        such a call can only advance by n (sync_length_bound() tightens it).  Same triple and same state as the host path - bit for bit
+        wherever both hints give the same split plan (the merge of split-KV partial results rounds differently from the un-split
+        sum); it can be captured (capture_verify / run_verify)."""
         from . import append as appendmod
         cfg, B, dev = self.cfg, self.B, self.dev
         par = [int(p) for p in (parents.tolist() if hasattr(parents, "tolist") else parents)]
@@ -507,6 +524,8 @@ class DecodeEngine:
         assert 1 <= n <= appendmod.MAX_TREE and par[0] == -1 and all(0 <= p < i for i, p in enumerate(par) if i), \
             "verify_tree: parents[0] = -1 (the root), every other node hangs off an earlier one; at most 64 nodes"
         assert tuple(draft_tokens.shape) == (B, n) and draft_tokens.dtype == torch.int64
+        if device_walk:
+            return self._verify_tree_device(draft_tokens, par)
         max_past = int(self.lengths.max()) - 1
         assert max_past + n <= self.mb * 64, "verify_tree: the tree does not fit the sequences' page tables"
         toks = draft_tokens.to(dev).clone()
@@ -550,8 +569,113 @@ class DecodeEngine:
         self.final.copy_(torch.index_select(final, 0, last))
         self.tokens.copy_(torch.index_select(am.reshape(-1), 0, last))      # in place: captured graphs read these tensors
         self.lengths.add_(accept_lens)
+        self._len_bound = max_past + 1 + max(len_h)                         # (tight again: both are known on the host)
         self.last_verify_logits = logits.view(B, n, -1)                     # (kept for callers that sample or score themselves)
         return accept_idx, accept_lens, am
+
+    def sync_length_bound(self):
+        """Make the host-side upper bound of `lengths` exact again (one device read-back): device-walk verifications advance it by the
+        tree's n nodes each, whatever was accepted."""
+        self._len_bound = int(self.lengths.max())
+        return self._len_bound
+
+    def _tree_constants(self, par):
+        """The device tensors a device-walk verify needs for the tree `par` (built on the host once, then served from the cache)."""
+        from . import append as appendmod
+        key = tuple(par)
+        c = self._tree_cache.get(key)
+        if c is None:
+            B, n, dev = self.B, len(par), self.dev
+            if self._layer_tables is None:
+                self._layer_tables = appendmod.layer_table_pointers(self.tables)
+            if len(self._tree_cache) >= 16:              # (a serving loop uses a handful of tree shapes)
+                self._tree_cache.pop(next(iter(self._tree_cache)))
+            c = dict(masks=appendmod.tree_masks_from_parents(par * B, [i * n for i in range(B + 1)]).to(dev),
+                     cu=torch.arange(0, B + 1, device=dev, dtype=torch.int32) * n,
+                     parents=torch.tensor(par * B, dtype=torch.int32, device=dev), layer_tables=self._layer_tables)
+            self._tree_cache[key] = c
+        return c
+
+    def _verify_tree_device(self, draft_tokens, par, max_past=None, out=None):
+        """verify_tree(device_walk=True) behind its argument checks.  `max_past`: the planner hint (None: the host-side bound);
+        `out`: accept_greedy's four output tensors (None: fresh ones)."""
+        from . import append as appendmod
+        cfg, B, dev, n = self.cfg, self.B, self.dev, len(par)
+        assert self._len_bound - 1 + n <= self.mb * 64, \
+            "verify_tree: the tree does not fit the sequences' page tables (by the host-side bound of the lengths: sync_length_bound())"
+        hint = self._len_bound - 1 if max_past is None else int(max_past)
+        c = self._tree_constants(par)
+        cu, masks = c["cu"], c["masks"]
+        toks = draft_tokens.to(dev).clone(memory_format=torch.contiguous_format)
+        toks[:, 0] = self.tokens
+        past = self.lengths - 1
+        h = torch.index_select(self.embed, 0, toks.reshape(-1))
+
+        def attend(li, qkv):
+            return appendmod.append_tree(qkv, cu, past, self.tables[li], masks, self.H, self.Hkv, self.size_per_token,
+                                         cfg["rope_theta"], self.int4, max_seqlen_q=n, max_past=hint).reshape(B * n, -1)
+
+        self._prompt_layers(h, self._prompt_buffers(B * n), attend)
+        final = torch.empty_like(h)
+        layernorm_ops.rms_norm(final, h, self.norm_w, cfg["eps"])
+        logits = torch.matmul(final, self.lm_head.t())
+        am = torch.empty((B * n,), dtype=torch.int64, device=dev)
+        argmax_rows_(logits, am)
+        accept_idx, accept_lens, last, nxt = appendmod.accept_greedy(toks.view(-1), am, c["parents"], cu, max_accept=n, out=out)
+        appendmod.commit_path_layers(c["layer_tables"], past, accept_idx, accept_lens, self.mb, self.Hkv, self.size_per_token, self.int4)
+        self.hidden.copy_(torch.index_select(h, 0, last))
+        self.final.copy_(torch.index_select(final, 0, last))
+        self.tokens.copy_(nxt)                                              # in place: captured graphs read these tensors
+        self.lengths.add_(accept_lens)
+        self._len_bound += n
+        self.last_verify_logits = logits.view(B, n, -1)
+        return accept_idx, accept_lens, am.view(B, n)
+
+    def capture_verify(self, parents, max_past=None):
+        """Capture one device-walk verify_tree of the tree `parents` in a hipGraph, the way capture() captures step(): a warm-up call on
+        a side stream first (allocator, lazy initialisation, the split-KV workspace - whose first use must not fall inside a capture),
+        then the capture over a persistent [B, n] draft buffer.  run_verify(draft_tokens) replays it.  `max_past`: the hint the split
+        plan is frozen with (default: the engine's capacity, prompt_len + max_new); results never depend on it.  The warm-up is a real
+        verification of an all-zero draft: it advances `tokens`, `lengths` and the cache like any other, so capture on a state you
+        restore or do not care about - what capture() implies for step().  Single GPU, with the lm_head."""
+        from . import append as appendmod
+        par = [int(p) for p in (parents.tolist() if hasattr(parents, "tolist") else parents)]
+        n, B, dev = len(par), self.B, self.dev
+        assert self.with_lm_head and not self.vocab_parallel and self.tp_world == 1, "capture_verify: single GPU, with the lm_head"
+        assert 1 <= n <= appendmod.MAX_TREE and par[0] == -1 and all(0 <= p < i for i, p in enumerate(par) if i), \
+            "capture_verify: parents[0] = -1 (the root), every other node hangs off an earlier one; at most 64 nodes"
+        hint = self.max_len if max_past is None else int(max_past)
+        self._verify_draft = torch.zeros((B, n), dtype=torch.int64, device=dev)
+        out = (torch.zeros((B, n), dtype=torch.int32, device=dev), torch.zeros((B,), dtype=torch.int32, device=dev),
+               torch.zeros((B,), dtype=torch.int64, device=dev), torch.zeros((B,), dtype=torch.int64, device=dev))
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            self._verify_tree_device(self._verify_draft, par, max_past=hint, out=out)     # warm-up outside capture
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            res = self._verify_tree_device(self._verify_draft, par, max_past=hint, out=out)
+        self._len_bound -= n                       # (the captured call has not run: only replays advance the lengths)
+        # every tensor the graph touches and that was allocated outside the capture stays referenced as long as the graph does: the
+        # four outputs of the walk (two of them are not part of the result) and the tree's constants (the cache may evict them)
+        self._verify_keep = (out, self._tree_constants(par))
+        self.verify_graph, self._verify_n, self._verify_result = g, n, res
+        return g
+
+    def run_verify(self, draft_tokens):
+        """Replay the verification capture_verify captured on `draft_tokens` int64 [B, n] -> the persistent (accept_idx, accept_lens,
+        argmax) tensors of the capture (overwritten by the next replay)."""
+        assert self.verify_graph is not None, "run_verify: capture_verify first"
+        n = self._verify_n
+        assert tuple(draft_tokens.shape) == (self.B, n) and draft_tokens.dtype == torch.int64
+        assert self._len_bound - 1 + n <= self.mb * 64, \
+            "run_verify: the tree does not fit the sequences' page tables (by the host-side bound of the lengths: sync_length_bound())"
+        self._verify_draft.copy_(draft_tokens)
+        self.verify_graph.replay()
+        self._len_bound += n
+        return self._verify_result
 
     # ---- one decode step (llama_w4a8_unpad.py:330-361 per layer) --------------------------------------------
     def _segments(self):
@@ -687,6 +811,7 @@ class DecodeEngine:
     def step(self):
         for partial in self._segments():
             self._reduce(partial)
+        self._len_bound += 1
 
     def capture(self, piecewise=None):
         """Capture one step in hipGraph(s) (removes ~400 launches of host overhead per step).
@@ -708,6 +833,7 @@ class DecodeEngine:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 self.step()
+            self._len_bound -= 1              # (the captured step has not run)
             self.graph = g
             return g
         pool = torch.cuda.graph_pool_handle()
@@ -748,7 +874,9 @@ class DecodeEngine:
                 g.replay()
                 if partial is not None:
                     self._reduce(partial)
+            self._len_bound += 1
         elif self.graph is not None:
             self.graph.replay()
+            self._len_bound += 1
         else:
             self.step()
