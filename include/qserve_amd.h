@@ -590,6 +590,37 @@ int qs_kv_cache_commit_path_layers(const int64_t* layer_tables, int num_layers, 
                                    int tokens_per_block, int size_per_token, int int4_kv_cache, int kv_cache_with_zeros,
                                    qs_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Row sampler (no reference counterpart: the reference's sampler layer applies its logits warpers and draws with torch ops,
+ * qserve/modeling/layers/sampler.py).  One token per row of fp16 logits [rows, row_stride] under temperature, top-k and top-p, on the
+ * device: capturable, nothing allocated, nothing read back, no hidden state.  temperature / top_k / top_p apply where the per-row
+ * device array (row_temperature / row_top_p float [rows], row_top_k int32 [rows]) is null.
+ *
+ * Per row, in exact arithmetic (x_i the fp16 logit, T, k, p the row's parameters, m = max x, w_i = exp((x_i - m) / T), W = sum w):
+ *   greedy     T < 1e-5 or p < 1e-8 (the reference's greedy conditions): out = the first index of the maximum (qs_argmax_rows).
+ *   nucleus    tau_p = the largest logit VALUE v with sum_{x_i >= v} w_i >= p * W; p >= 1: off.  The cut is at the granularity of values:
+ *              every token tied at the threshold stays (a sort-based sampler cuts inside a tie class, by sort order).
+ *   top-k      tau_k = the k-th largest logit; ties at it stay; k <= 0 or k >= n: off.
+ *   order      the nucleus is taken on the full tempered distribution, then intersected with top-k (the reference's warper order):
+ *              S = {i : x_i >= max(tau_p, tau_k)}, W_S = sum_S w.
+ *   draw       out = the smallest j in S with sum_{i in S, i <= j} w_i > u * W_S, the sum in INDEX order.
+ *   -inf logits (masked tokens) weigh 0 and are never returned while a finite logit exists.  Rows with +inf, NaN or no finite logit are
+ *   the caller's error; the call still ends and returns an index in [0, n).
+ * Arithmetic: w from one fp32 exp2 per element, then every sum in 2^-40 fixed point - exact integer additions.  Results are bit-identical
+ * run to run and eager against graph replay; against the exact rule they differ by less than 1e-4 of normalised cumulative probability.
+ *
+ * u: uniforms[row] if `uniforms` (device float [rows], values in [0, 1)) is given; else Philox4x32-10 with counter (key_lo, key_hi, 0, 0)
+ * and key (seed_lo, seed_hi), first output word, u = (word >> 8) * 2^-24, where key = row_keys[row] (device int64 [rows]) or the row
+ * index when row_keys is null.  Counter-based: a replayed graph draws new numbers exactly when the caller changes row_keys on the device.
+ * u_out (device float [rows], may be null) receives the uniform every row used.
+ *
+ * QS_EINVAL before any device call: logits or out null, n < 8 or n > 2^22, row_stride < n or not a multiple of 8, rows < 0, logits not
+ * 16-byte, out / row_keys not 8-byte, a float / int32 array not 4-byte aligned.  rows == 0: QS_OK, no launch.
+ * ---------------------------------------------------------------------------------------------------------- */
+int qs_sample_rows(const void* logits, int64_t* out, int rows, int n, int64_t row_stride, float temperature, int top_k, float top_p,
+                   const float* row_temperature, const int32_t* row_top_k, const float* row_top_p, const float* uniforms, uint64_t seed,
+                   const int64_t* row_keys, float* u_out, qs_stream_t stream);
+
 /* Timing tool (scripts/trace_attn.py): device-to-device copy of the first `bytes` of the split-KV workspace, where the
  * trace instantiation of the KV4 decode attention (qs_set_attention_variant(232)) leaves its s_memtime stamps.
  * (A library built with -DQS_RING_TRACE additionally exports qs_debug_ring_trace(void* buf) for scripts/trace_gemm.py;

@@ -84,6 +84,7 @@ SIGNATURES = {
     "qs_kv_cache_commit_path": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "qs_tree_accept_greedy": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "qs_kv_cache_commit_path_layers": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "qs_sample_rows": (_i, [_vp, _vp, _i, _i, _i64, _f, _i, _f, _vp, _vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp]),
 }
 
 

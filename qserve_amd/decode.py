@@ -28,6 +28,7 @@ import qserve_backend.qgemm_w4a8_per_chn as gemm_chn
 import qserve_backend.qgemm_w4a8_per_group as gemm_grp
 
 from . import fused as fusedmod
+from . import sampling as samplingmod
 from . import tp as tpmod
 from ._lib import device_status as _device_status
 from .backend._util import check as _check, lib as _lib, stream
@@ -45,6 +46,14 @@ def argmax_rows_(logits, out):
         return
     _check(_lib.qs_argmax_rows(logits.data_ptr(), out.data_ptr(), logits.size(0), logits.size(1), logits.stride(0), stream()),
            "argmax_rows")
+
+
+def _tree_depths(par):
+    """Depth of every node of the tree `par` (parents[i] < i, the root's is -1): the root has depth 0."""
+    d = []
+    for i, p in enumerate(par):
+        d.append(0 if i == 0 else d[p] + 1)
+    return d
 
 
 LLAMA3_8B = dict(name="Llama-3-8B", hidden=4096, heads=32, kv_heads=8, inter=14336, layers=32, vocab=128256,
@@ -273,6 +282,43 @@ class DecodeEngine:
         self._tree_cache = {}            # parent tuple -> the per-tree device constants of the device-walk verify_tree
         self._layer_tables = None        # append.layer_table_pointers(self.tables), built on first use
         self.verify_graph = None
+        self.sampling = None             # set_sampling: {"seed"} while the head samples; the parameters live in device tensors
+
+    # ---- the sampling head (qserve_amd.sampling, csrc/sample_rows.hip) --------------------------------------------------------
+    def set_sampling(self, temperature, top_k=0, top_p=1.0, seed=0):
+        """Make the head of step() / capture() / run(), of the prefill entries and of verify_tree(sampled=True) draw from the
+        temperature / top-k / top-p distribution (`sampling.sample_rows`) instead of taking the arg-max; set_sampling(None) goes back to
+        greedy.  The three values live in persistent device tensors that are filled in place, so a captured graph sees later changes of
+        them; whether the head samples at all, and `seed`, are frozen into a capture - capture after switching, re-capture for another
+        seed.  The randomness of a token is a function of (seed, sequence, position) alone (`sampling.position_keys`): a captured step
+        advances it by advancing `lengths`, and the token sequence does not depend on what verify_tree was given as a draft, up to the
+        numerics of the append path against the decode path - a draft only decides how many positions one pass yields.  Single GPU, with
+        the lm_head; under tensor parallelism the greedy head stays the only one."""
+        if temperature is None:
+            self.sampling = None
+            return
+        assert self.with_lm_head and not self.vocab_parallel and self.tp_world == 1, "set_sampling: single GPU, with the lm_head"
+        from .append import MAX_TREE
+        if getattr(self, "_samp_t", None) is None:
+            rows = self.B * MAX_TREE                      # (verify_tree samples B * n rows, n <= MAX_TREE)
+            self._samp_t = torch.empty((rows,), dtype=torch.float32, device=self.dev)
+            self._samp_k = torch.empty((rows,), dtype=torch.int32, device=self.dev)
+            self._samp_p = torch.empty((rows,), dtype=torch.float32, device=self.dev)
+            self._samp_ids = torch.arange(self.B, dtype=torch.int64, device=self.dev)
+        self._samp_t.fill_(float(temperature))
+        self._samp_k.fill_(int(top_k))
+        self._samp_p.fill_(float(top_p))
+        self.sampling = dict(seed=int(seed))
+
+    def _sample(self, logits, out, keys):
+        """out[r] = the token drawn from row r of `logits` under the engine's sampling parameters and the Philox key keys[r]."""
+        rows = logits.size(0)
+        samplingmod.sample_rows(logits, out, self._samp_t[:rows], self._samp_k[:rows], self._samp_p[:rows], seed=self.sampling["seed"],
+                                row_keys=keys)
+
+    def _step_keys(self):
+        """The keys of the tokens the head is about to draw: (b, lengths[b]) - the position the new token will hold."""
+        return samplingmod.position_keys(self._samp_ids, self.lengths)
 
     # ---- fill the cache for positions [0, prompt_len) through the prefill writer (random K/V source) ----------
     def prefill_cache(self, prompt_len, chunk=8):
@@ -372,7 +418,11 @@ class DecodeEngine:
             self._head_finish(self.head_cand)
         else:
             logits = torch.matmul(self.final, self.lm_head.t())
-            argmax_rows_(logits, self.tokens)
+            if self.sampling is not None:
+                self.lengths.fill_(prompt_len)                       # the first new token will hold position prompt_len
+                self._sample(logits, self.tokens, self._step_keys())
+            else:
+                argmax_rows_(logits, self.tokens)
         self.lengths.fill_(prompt_len + 1)
         self._len_bound = prompt_len + 1
 
@@ -493,7 +543,7 @@ class DecodeEngine:
         self._prompt_head(h.view(B, -1, self.hid)[:, -1], P + S)
 
     # ---- verification of a draft tree (no reference counterpart; qserve_amd.append, csrc/append_tree.hip) ---------------------
-    def verify_tree(self, draft_tokens, parents, device_walk=False):
+    def verify_tree(self, draft_tokens, parents, device_walk=False, sampled=False):
         """Verify one draft tree per sequence in ONE pass and keep the greedy path.  `parents` [n] (n <= 64, the same tree shape for
         every sequence): parents[i] is the parent of node i, an EARLIER node; node 0 is the root - the current `tokens`, whose K / V
         are not in the cache yet - and parents[0] = -1.  `draft_tokens` int64 [B, n]: the drafted token of every node (column 0 is
@@ -515,7 +565,13 @@ class DecodeEngine:
         parent tuple.  The planner hint and the "fits the page tables" bound are the engine's host-side upper bound of `lengths`, which
         such a call can only advance by n (sync_length_bound() tightens it).  Same triple and same state as the host path - bit for bit
         wherever both hints give the same split plan (the merge of split-KV partial results rounds differently from the un-split
-        sum); it can be captured (capture_verify / run_verify)."""
+        sum); it can be captured (capture_verify / run_verify).
+
+        `sampled=True` (after set_sampling; both paths): lossless speculative sampling for point proposals.  The B * n rows are sampled in
+        one `sampling.sample_rows` launch, node i of sequence b keyed by (b, lengths[b] - 1 + depth(i) + 1) - the position of the token
+        that FOLLOWS the node - and the sampled tokens take the place of the arg-max in the walk: descend to the child that carries the
+        token drawn at its parent, else that token is the bonus token.  (Siblings' subtrees share keys at equal depth; one path is
+        walked.)  Commit, `tokens`, `lengths` as above; the third element of the triple is the sampled tokens."""
         from . import append as appendmod
         cfg, B, dev = self.cfg, self.B, self.dev
         par = [int(p) for p in (parents.tolist() if hasattr(parents, "tolist") else parents)]
@@ -524,8 +580,9 @@ class DecodeEngine:
         assert 1 <= n <= appendmod.MAX_TREE and par[0] == -1 and all(0 <= p < i for i, p in enumerate(par) if i), \
             "verify_tree: parents[0] = -1 (the root), every other node hangs off an earlier one; at most 64 nodes"
         assert tuple(draft_tokens.shape) == (B, n) and draft_tokens.dtype == torch.int64
+        assert not sampled or self.sampling is not None, "verify_tree(sampled=True): set_sampling first"
         if device_walk:
-            return self._verify_tree_device(draft_tokens, par)
+            return self._verify_tree_device(draft_tokens, par, sampled=sampled)
         max_past = int(self.lengths.max()) - 1
         assert max_past + n <= self.mb * 64, "verify_tree: the tree does not fit the sequences' page tables"
         toks = draft_tokens.to(dev).clone()
@@ -544,7 +601,10 @@ class DecodeEngine:
         layernorm_ops.rms_norm(final, h, self.norm_w, cfg["eps"])
         logits = torch.matmul(final, self.lm_head.t())
         am = torch.empty((B * n,), dtype=torch.int64, device=dev)
-        argmax_rows_(logits, am)
+        if sampled:
+            self._sample(logits, am, self._node_keys(torch.tensor(_tree_depths(par), dtype=torch.int32, device=dev)))
+        else:
+            argmax_rows_(logits, am)
         am = am.view(B, n)
         # the greedy walk, on the host (n <= 64 nodes per sequence)
         am_h, tok_h = am.cpu().tolist(), toks.cpu().tolist()
@@ -592,11 +652,17 @@ class DecodeEngine:
                 self._tree_cache.pop(next(iter(self._tree_cache)))
             c = dict(masks=appendmod.tree_masks_from_parents(par * B, [i * n for i in range(B + 1)]).to(dev),
                      cu=torch.arange(0, B + 1, device=dev, dtype=torch.int32) * n,
-                     parents=torch.tensor(par * B, dtype=torch.int32, device=dev), layer_tables=self._layer_tables)
+                     parents=torch.tensor(par * B, dtype=torch.int32, device=dev), layer_tables=self._layer_tables,
+                     depth=torch.tensor(_tree_depths(par), dtype=torch.int32, device=dev))
             self._tree_cache[key] = c
         return c
 
-    def _verify_tree_device(self, draft_tokens, par, max_past=None, out=None):
+    def _node_keys(self, depth):
+        """The keys of the B * n rows of a sampled verification: node i of sequence b draws the token at position lengths[b] + depth(i)."""
+        n = depth.numel()
+        return samplingmod.position_keys(self._samp_ids.view(-1, 1).expand(self.B, n), self.lengths.view(-1, 1) + depth.view(1, -1)).reshape(-1)
+
+    def _verify_tree_device(self, draft_tokens, par, max_past=None, out=None, sampled=False):
         """verify_tree(device_walk=True) behind its argument checks.  `max_past`: the planner hint (None: the host-side bound);
         `out`: accept_greedy's four output tensors (None: fresh ones)."""
         from . import append as appendmod
@@ -620,7 +686,10 @@ class DecodeEngine:
         layernorm_ops.rms_norm(final, h, self.norm_w, cfg["eps"])
         logits = torch.matmul(final, self.lm_head.t())
         am = torch.empty((B * n,), dtype=torch.int64, device=dev)
-        argmax_rows_(logits, am)
+        if sampled:
+            self._sample(logits, am, self._node_keys(c["depth"]))
+        else:
+            argmax_rows_(logits, am)
         accept_idx, accept_lens, last, nxt = appendmod.accept_greedy(toks.view(-1), am, c["parents"], cu, max_accept=n, out=out)
         appendmod.commit_path_layers(c["layer_tables"], past, accept_idx, accept_lens, self.mb, self.Hkv, self.size_per_token, self.int4)
         self.hidden.copy_(torch.index_select(h, 0, last))
@@ -631,19 +700,21 @@ class DecodeEngine:
         self.last_verify_logits = logits.view(B, n, -1)
         return accept_idx, accept_lens, am.view(B, n)
 
-    def capture_verify(self, parents, max_past=None):
+    def capture_verify(self, parents, max_past=None, sampled=False):
         """Capture one device-walk verify_tree of the tree `parents` in a hipGraph, the way capture() captures step(): a warm-up call on
         a side stream first (allocator, lazy initialisation, the split-KV workspace - whose first use must not fall inside a capture),
         then the capture over a persistent [B, n] draft buffer.  run_verify(draft_tokens) replays it.  `max_past`: the hint the split
         plan is frozen with (default: the engine's capacity, prompt_len + max_new); results never depend on it.  The warm-up is a real
         verification of an all-zero draft: it advances `tokens`, `lengths` and the cache like any other, so capture on a state you
-        restore or do not care about - what capture() implies for step().  Single GPU, with the lm_head."""
+        restore or do not care about - what capture() implies for step().  `sampled=True` captures verify_tree(sampled=True) (after
+        set_sampling).  Single GPU, with the lm_head."""
         from . import append as appendmod
         par = [int(p) for p in (parents.tolist() if hasattr(parents, "tolist") else parents)]
         n, B, dev = len(par), self.B, self.dev
         assert self.with_lm_head and not self.vocab_parallel and self.tp_world == 1, "capture_verify: single GPU, with the lm_head"
         assert 1 <= n <= appendmod.MAX_TREE and par[0] == -1 and all(0 <= p < i for i, p in enumerate(par) if i), \
             "capture_verify: parents[0] = -1 (the root), every other node hangs off an earlier one; at most 64 nodes"
+        assert not sampled or self.sampling is not None, "capture_verify(sampled=True): set_sampling first"
         hint = self.max_len if max_past is None else int(max_past)
         self._verify_draft = torch.zeros((B, n), dtype=torch.int64, device=dev)
         out = (torch.zeros((B, n), dtype=torch.int32, device=dev), torch.zeros((B,), dtype=torch.int32, device=dev),
@@ -651,12 +722,12 @@ class DecodeEngine:
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
-            self._verify_tree_device(self._verify_draft, par, max_past=hint, out=out)     # warm-up outside capture
+            self._verify_tree_device(self._verify_draft, par, max_past=hint, out=out, sampled=sampled)     # warm-up outside capture
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            res = self._verify_tree_device(self._verify_draft, par, max_past=hint, out=out)
+            res = self._verify_tree_device(self._verify_draft, par, max_past=hint, out=out, sampled=sampled)
         self._len_bound -= n                       # (the captured call has not run: only replays advance the lengths)
         # every tensor the graph touches and that was allocated outside the capture stays referenced as long as the graph does: the
         # four outputs of the walk (two of them are not part of the result) and the tree's constants (the cache may evict them)
@@ -777,7 +848,10 @@ class DecodeEngine:
             self._head_finish(self.head_cand_res)
         elif self.with_lm_head:
             logits = torch.matmul(self.final, self.lm_head.t())      # un-quantised fp16 lm_head (:392,476)
-            argmax_rows_(logits, self.tokens)                        # greedy sampler
+            if self.sampling is not None:
+                self._sample(logits, self.tokens, self._step_keys())
+            else:
+                argmax_rows_(logits, self.tokens)                    # greedy sampler
         self.lengths.add_(1)
 
 
