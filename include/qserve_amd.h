@@ -621,6 +621,45 @@ int qs_sample_rows(const void* logits, int64_t* out, int rows, int n, int64_t ro
                    const float* row_temperature, const int32_t* row_top_k, const float* row_top_p, const float* uniforms, uint64_t seed,
                    const int64_t* row_keys, float* u_out, qs_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * N-gram (prompt-lookup) tree drafter and the history it reads (no reference counterpart).  One draft tree per sequence, proposed from
+ * the sequence's own tokens, on the device: capturable, nothing allocated, nothing read back.  With qs_history_append behind a
+ * verification, history[b, :lengths[b]] is the text of sequence b and nothing of the loop draft -> verify -> accept -> commit -> record
+ * crosses to the host.
+ *
+ * qs_ngram_draft_tree.  history int32 [batch, cap] with row stride hist_stride >= cap (elements); lengths int32 [batch]; per sequence
+ * L = min(max(lengths[b], 0), cap) and h = history[b, :L]; h[L-1] is the root - the token whose K / V is not in the cache yet.  parents
+ * int32 [n] (device; ONE tree shape per call, 1 <= n <= 64): node 0 is the root whatever parents[0] holds (-1 by convention), and
+ * 0 <= parents[i] < i otherwise.  draft int64 [batch, n]:
+ *   draft[b, 0] = h[L-1], or pad_token if L == 0.
+ *   i >= 1, a = parents[i]:  c = h followed by the draft tokens on the path root -> a, the root's column excluded (len(c) = L + depth(a)).
+ *     For a history position p, 1 <= p <= L-1, the match length is
+ *         m(p) = max { m <= min(max_ngram, p) : h[p-1-j] == c[len(c)-1-j] for all 0 <= j < m }
+ *     - matches are looked for in the history only, continuations are taken from the history only.  p is a candidate if
+ *     m(p) >= min_match and h[p] differs from draft[b, s] of every earlier sibling (1 <= s < i, parents[s] == a).  draft[b, i] = h[p*] where
+ *     p* maximises (m(p), p) lexicographically: the longest match, then the most recent.  No candidate: draft[b, i] = pad_token.
+ *   A node whose parents[i] is not in 0 .. i-1 gets pad_token; its path is the node alone (its children see c = h followed by pad_token).
+ *   A pad node's descendants follow the rule, pad_token being a token like any other in c.  Tokens compare as 64-bit integers (a history
+ *   token is sign-extended).
+ * 1 <= min_match <= max_ngram <= 16.  One workgroup per sequence; while L <= qs_ngram_draft_lds_tokens() the history is staged in LDS,
+ * beyond it it is read from global memory - the results are the same.
+ *
+ * qs_history_append, after a verification.  past_lens int32 [batch] = lengths - 1 from BEFORE the lengths advanced; node_tokens int64
+ * [batch, n] (the draft); accept_idx int32 [batch, max_accept], accept_lens int32 [batch] (m, cut to max_accept), next_token int64 [batch]:
+ *   history[b, past + j] = node_tokens[b, accept_idx[b, j]]  for 1 <= j < m,      history[b, past + m] = next_token[b].
+ * A write at an index outside 0 .. cap-1 is skipped, and so is one whose accept_idx entry names no node of the tree; m < 1 writes
+ * nothing.  Nothing else in the row changes.  (Tokens are stored as int32.)
+ *
+ * QS_EINVAL before any device call: a null pointer, n or max_accept outside 1 .. 64, max_ngram / min_match outside the range above,
+ * cap < 1, hist_stride < cap, batch < 0.  batch == 0: QS_OK, no launch.
+ * ---------------------------------------------------------------------------------------------------------- */
+int qs_ngram_draft_tree(const int32_t* history, int64_t hist_stride, int cap, const int32_t* lengths, const int32_t* parents,
+                        int batch, int n, int max_ngram, int min_match, int64_t pad_token, int64_t* draft, qs_stream_t stream);
+int qs_history_append(int32_t* history, int64_t hist_stride, int cap, const int32_t* past_lens, const int64_t* node_tokens,
+                      const int32_t* accept_idx, const int32_t* accept_lens, const int64_t* next_token,
+                      int batch, int n, int max_accept, qs_stream_t stream);
+int qs_ngram_draft_lds_tokens(void);   /* history tokens the drafter stages in LDS (a compile-time constant of the library) */
+
 /* Timing tool (scripts/trace_attn.py): device-to-device copy of the first `bytes` of the split-KV workspace, where the
  * trace instantiation of the KV4 decode attention (qs_set_attention_variant(232)) leaves its s_memtime stamps.
  * (A library built with -DQS_RING_TRACE additionally exports qs_debug_ring_trace(void* buf) for scripts/trace_gemm.py;

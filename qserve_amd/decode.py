@@ -27,6 +27,7 @@ import qserve_backend.layernorm_ops as layernorm_ops
 import qserve_backend.qgemm_w4a8_per_chn as gemm_chn
 import qserve_backend.qgemm_w4a8_per_group as gemm_grp
 
+from . import drafting as draftingmod
 from . import fused as fusedmod
 from . import sampling as samplingmod
 from . import tp as tpmod
@@ -282,6 +283,7 @@ class DecodeEngine:
         self._tree_cache = {}            # parent tuple -> the per-tree device constants of the device-walk verify_tree
         self._layer_tables = None        # append.layer_table_pointers(self.tables), built on first use
         self.verify_graph = None
+        self.speculate_graph = None
         self.sampling = None             # set_sampling: {"seed"} while the head samples; the parameters live in device tensors
 
     # ---- the sampling head (qserve_amd.sampling, csrc/sample_rows.hip) --------------------------------------------------------
@@ -653,6 +655,7 @@ class DecodeEngine:
             c = dict(masks=appendmod.tree_masks_from_parents(par * B, [i * n for i in range(B + 1)]).to(dev),
                      cu=torch.arange(0, B + 1, device=dev, dtype=torch.int32) * n,
                      parents=torch.tensor(par * B, dtype=torch.int32, device=dev), layer_tables=self._layer_tables,
+                     tree=torch.tensor(par, dtype=torch.int32, device=dev),          # [n]: the one tree shape the drafter takes
                      depth=torch.tensor(_tree_depths(par), dtype=torch.int32, device=dev))
             self._tree_cache[key] = c
         return c
@@ -747,6 +750,121 @@ class DecodeEngine:
         self.verify_graph.replay()
         self._len_bound += n
         return self._verify_result
+
+    # ---- n-gram drafting and the closed speculative loop (qserve_amd.drafting, csrc/ngram_draft.hip) -----------------------------
+    def enable_drafting(self, prompt_tokens, max_ngram=4, min_match=1, pad_token=0):
+        """Start keeping the text of every sequence on the device, for the n-gram drafter: `history` int32 [B, max_len], columns
+        0 .. P - 1 the prompt (`prompt_tokens`: what the prefill entry was given, [B * P] sequence-major or [B, P]), column P the first
+        sampled token (`tokens`) - history[b, :lengths[b]] is the text, its last entry the token whose K / V is not in the cache yet.
+        Call it right after a prefill entry that was given `tokens` (all sequences hold P + 1 tokens: checked, one read-back).  From
+        then on step() records history[b, lengths[b] - 1] = tokens[b] behind its head (one more launch pair; a graph captured AFTER
+        this call contains it, one captured before does not record) and speculate() records what it accepted.  verify_tree() itself
+        does not touch `history`: a caller that verifies drafts of its own appends with drafting.history_append.  `max_ngram`,
+        `min_match`: the drafter's parameters (drafting.ngram_draft_tree) from now on.  `pad_token`: what a node without a candidate
+        holds - the verification embeds every node, so it must be a token of the vocabulary (0 <= pad_token < vocab; checked).  A
+        second call (after another prefill) refills the SAME buffers in place: graphs captured since the first call stay valid.
+        Single GPU, with the lm_head."""
+        assert self.with_lm_head and not self.vocab_parallel and self.tp_world == 1, "enable_drafting: single GPU, with the lm_head"
+        assert 1 <= int(min_match) <= int(max_ngram) <= draftingmod.MAX_NGRAM, \
+            f"enable_drafting: 1 <= min_match <= max_ngram <= {draftingmod.MAX_NGRAM}"
+        assert 0 <= int(pad_token) < self.cfg["vocab"], \
+            f"enable_drafting: pad_token={int(pad_token)} must be a token of the vocabulary (0 .. {self.cfg['vocab'] - 1}): pad nodes are embedded"
+        B, dev = self.B, self.dev
+        prompt = prompt_tokens.to(dev).reshape(B, -1)
+        P = prompt.size(1)
+        assert P + 1 <= self.max_len and bool((self.lengths == P + 1).all()), \
+            "enable_drafting: call it right after a prefill of these prompt tokens (every sequence holds P + 1 tokens)"
+        if getattr(self, "history", None) is None:
+            self.history = torch.zeros((B, self.max_len), dtype=torch.int32, device=dev)
+            # what history_append needs to record ONE token per sequence (a path of the root alone): constants of step()'s record,
+            # and the buffer its `past` is computed into
+            self._step_record = (torch.zeros((B, 1), dtype=torch.int64, device=dev), torch.zeros((B, 1), dtype=torch.int32, device=dev),
+                                 torch.ones((B,), dtype=torch.int32, device=dev), torch.zeros((B,), dtype=torch.int32, device=dev))
+        self.history.zero_()
+        self.history[:, :P] = prompt
+        self.history[:, P] = self.tokens
+        self._draft_params = (int(max_ngram), int(min_match), int(pad_token))
+
+    def _record_step(self):
+        """history[b, lengths[b] - 1] = tokens[b], after step() advanced the lengths: history_append with a path of the root alone at
+        past = lengths - 2 (its bonus token lands at past + 1).  A sequence that has outgrown `history` records nothing."""
+        nodes, idx, ones, past = self._step_record
+        torch.sub(self.lengths, 2, out=past)
+        draftingmod.history_append(self.history, past, nodes, idx, ones, self.tokens)
+
+    def _tree_arg(self, parents, what):
+        from . import append as appendmod
+        par = [int(p) for p in (parents.tolist() if hasattr(parents, "tolist") else parents)]
+        assert self.with_lm_head and not self.vocab_parallel and self.tp_world == 1, f"{what}: single GPU, with the lm_head"
+        assert 1 <= len(par) <= appendmod.MAX_TREE and par[0] == -1 and all(0 <= p < i for i, p in enumerate(par) if i), \
+            f"{what}: parents[0] = -1 (the root), every other node hangs off an earlier one; at most 64 nodes"
+        assert getattr(self, "history", None) is not None, f"{what}: enable_drafting first"
+        return par
+
+    def draft_tree(self, parents, out=None):
+        """One n-gram draft tree per sequence from `history` (drafting.ngram_draft_tree with the parameters of enable_drafting) ->
+        int64 [B, n] on the device; column 0 is the root, the current `tokens`.  Nothing leaves the device."""
+        par = self._tree_arg(parents, "draft_tree")
+        max_ngram, min_match, pad = self._draft_params
+        return draftingmod.ngram_draft_tree(self.history, self.lengths, self._tree_constants(par)["tree"], max_ngram, min_match, pad, out=out)
+
+    def speculate(self, parents, sampled=False):
+        """One round of speculative decoding with nothing crossing to the host: draft_tree -> verify_tree(device_walk=True) ->
+        drafting.history_append.  `tokens`, `lengths`, the cache and `history` end where accept_lens[b] decode steps would have left
+        them.  -> the triple of verify_tree.  `sampled=True`: verify_tree(sampled=True), after set_sampling."""
+        par = self._tree_arg(parents, "speculate")
+        assert not sampled or self.sampling is not None, "speculate(sampled=True): set_sampling first"
+        return self._speculate(par, sampled=sampled)
+
+    def _speculate(self, par, max_past=None, out=None, draft=None, sampled=False):
+        """speculate() behind its argument checks.  `max_past`, `out`: as for _verify_tree_device; `draft`: the [B, n] buffer the
+        drafter fills (None: a fresh one)."""
+        draft = self.draft_tree(par, out=draft)
+        past = self.lengths - 1                                             # before the verification advances the lengths
+        res = self._verify_tree_device(draft, par, max_past=max_past, out=out, sampled=sampled)
+        draftingmod.history_append(self.history, past, draft, res[0], res[1], self.tokens)
+        return res
+
+    def capture_speculate(self, parents, max_past=None, sampled=False):
+        """Capture one speculate() round of the tree `parents` in ONE hipGraph, the way capture_verify captures a verification: a
+        warm-up round on a side stream first (allocator, lazy initialisation, the split-KV workspace - whose first use must not fall
+        inside a capture), then the capture on one stream over persistent draft and output buffers.  run_speculate() replays it.
+        `max_past`: the hint the split plan is frozen with (default: the engine's capacity, prompt_len + max_new); results never depend
+        on it.  The warm-up is a real round: it advances `tokens`, `lengths`, the cache and `history` like any other.  `sampled=True`
+        captures speculate(sampled=True) (after set_sampling).  Single GPU, with the lm_head, after enable_drafting."""
+        par = self._tree_arg(parents, "capture_speculate")
+        n, B, dev = len(par), self.B, self.dev
+        assert not sampled or self.sampling is not None, "capture_speculate(sampled=True): set_sampling first"
+        hint = self.max_len if max_past is None else int(max_past)
+        draft = torch.zeros((B, n), dtype=torch.int64, device=dev)
+        out = (torch.zeros((B, n), dtype=torch.int32, device=dev), torch.zeros((B,), dtype=torch.int32, device=dev),
+               torch.zeros((B,), dtype=torch.int64, device=dev), torch.zeros((B,), dtype=torch.int64, device=dev))
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            self._speculate(par, max_past=hint, out=out, draft=draft, sampled=sampled)      # warm-up outside capture
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            res = self._speculate(par, max_past=hint, out=out, draft=draft, sampled=sampled)
+        self._len_bound -= n                       # (the captured round has not run: only replays advance the lengths)
+        # every tensor the graph touches and that was allocated outside the capture stays referenced as long as the graph does: the
+        # draft buffer, the four outputs of the walk, the tree's constants (the cache may evict them), step()'s record constants
+        self._speculate_keep = (draft, out, self._tree_constants(par), self._step_record, self.history)
+        self.speculate_graph, self._speculate_n, self._speculate_result = g, n, res
+        return g
+
+    def run_speculate(self):
+        """Replay the round capture_speculate captured: no argument, nothing copied from the host -> the persistent (accept_idx,
+        accept_lens, argmax) tensors of the capture (overwritten by the next replay)."""
+        assert self.speculate_graph is not None, "run_speculate: capture_speculate first"
+        n = self._speculate_n
+        assert self._len_bound - 1 + n <= self.mb * 64, \
+            "run_speculate: the tree does not fit the sequences' page tables (by the host-side bound of the lengths: sync_length_bound())"
+        self.speculate_graph.replay()
+        self._len_bound += n
+        return self._speculate_result
 
     # ---- one decode step (llama_w4a8_unpad.py:330-361 per layer) --------------------------------------------
     def _segments(self):
@@ -853,6 +971,8 @@ class DecodeEngine:
             else:
                 argmax_rows_(logits, self.tokens)                    # greedy sampler
         self.lengths.add_(1)
+        if getattr(self, "history", None) is not None:               # enable_drafting: the new token joins the text
+            self._record_step()
 
 
     def _head_local(self):
