@@ -622,6 +622,42 @@ int qs_sample_rows(const void* logits, int64_t* out, int rows, int n, int64_t ro
                    const int64_t* row_keys, float* u_out, qs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Repetition, presence and frequency penalties (the three knobs of the reference's SamplingParams; no kernel counterpart there).  Edits
+ * fp16 logit rows IN PLACE from the tokens in front of each row's position, on the device, in front of qs_argmax_rows / qs_sample_rows:
+ * capturable, nothing allocated, nothing read back, no scratch.  The result is an fp16 row again.
+ *
+ * logits fp16 [batch * n_nodes, n] with row stride row_stride (elements).  history int32 [batch, cap] with row stride hist_stride >= cap;
+ * lengths int32 [batch]; prompt_lens int32 [batch] or null (= 0); node_tokens int64 [batch, n_nodes] or null; parents int32 [n_nodes]
+ * (ONE tree shape, as for the drafter; parents[0] = -1 by convention; may be null when node_tokens is).
+ *
+ * Row r = b * n_nodes + i.  Its CONTEXT is h[b, 0 .. L) with L = min(max(lengths[b], 0), cap), followed by node_tokens[b, j] for the nodes
+ * j != 0 on the path root -> i, i itself included (the root is h[L-1] already).  node_tokens null: the history alone - with n_nodes = 1
+ * the case of a plain decode step.  A sibling's token, or any node off the path, is in no context.  A node whose parent entry is not in
+ * 0 .. j-1 hangs off the root (its path is the node alone; its children's paths go through it), as for qs_ngram_draft_tree.
+ * For a token id t in [0, n):  c_all(t) = occurrences of t in the context;  c_gen(t) = occurrences at context positions >= prompt_lens[b]
+ * (path tokens are all generated).  Ids outside [0, n), in the history or on the path, are ignored and no address is formed from them.
+ *
+ * The edit, for every t with c_all(t) > 0 and a logit other than -inf, from x = float(logit), every operation a float32 operation
+ * rounded on its own (no fused multiply-add; IEEE division):
+ *     x = x > 0 ? x / rep : x * rep                        (the HF / reference repetition rule)
+ *     x = x - (freq * float(c_gen) + (c_gen > 0 ? pres : 0))
+ *     logit = fp16(x), round to nearest even.
+ * -inf stays -inf.  Ids not in the context, the padding between n and the row stride, and every row of a sequence whose parameters are
+ * neutral (rep == 1, freq == 0, pres == 0) are NOT WRITTEN at all.  rep / freq / pres of sequence b: seq_repetition[b] / seq_frequency[b] /
+ * seq_presence[b] where that device array (float [batch]) is given, else the scalar.  rep > 0 is the caller's duty.
+ *
+ * Counts are 16-bit: cap + 63 <= 65 535, anything larger is QS_EINVAL.  QS_EINVAL before any device call as well: logits, history or
+ * lengths null, node_tokens without parents, n < 8 or n > 2^22, row_stride < n or not a multiple of 8, n_nodes outside 1 .. 64, cap < 1,
+ * hist_stride < cap, batch < 0 or > 65 535 (one grid row per sequence), node_tokens not 8-byte or an int32 / float array not 4-byte aligned.  batch == 0: QS_OK, no launch.
+ * One workgroup per (slice of 32 768 ids, sequence): the history is counted once per (sequence, slice), not once per row.  Bit-identical
+ * run to run and eager against graph replay.
+ * ---------------------------------------------------------------------------------------------------------- */
+int qs_penalize_rows(void* logits, int64_t row_stride, int n, const int32_t* history, int64_t hist_stride, int cap,
+                     const int32_t* lengths, const int32_t* prompt_lens, const int64_t* node_tokens, const int32_t* parents,
+                     int batch, int n_nodes, float repetition, float frequency, float presence, const float* seq_repetition,
+                     const float* seq_frequency, const float* seq_presence, qs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * N-gram (prompt-lookup) tree drafter and the history it reads (no reference counterpart).  One draft tree per sequence, proposed from
  * the sequence's own tokens, on the device: capturable, nothing allocated, nothing read back.  With qs_history_append behind a
  * verification, history[b, :lengths[b]] is the text of sequence b and nothing of the loop draft -> verify -> accept -> commit -> record

@@ -85,6 +85,7 @@ SIGNATURES = {
     "qs_tree_accept_greedy": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "qs_kv_cache_commit_path_layers": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "qs_sample_rows": (_i, [_vp, _vp, _i, _i, _i64, _f, _i, _f, _vp, _vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp]),
+    "qs_penalize_rows": (_i, [_vp, _i64, _i, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "qs_ngram_draft_tree": (_i, [_vp, _i64, _i, _vp, _vp, _i, _i, _i, _i, _i64, _vp, _vp]),
     "qs_history_append": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "qs_ngram_draft_lds_tokens": (_i, []),

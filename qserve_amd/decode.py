@@ -29,6 +29,7 @@ import qserve_backend.qgemm_w4a8_per_group as gemm_grp
 
 from . import drafting as draftingmod
 from . import fused as fusedmod
+from . import penalties as penaltiesmod
 from . import sampling as samplingmod
 from . import tp as tpmod
 from ._lib import device_status as _device_status
@@ -285,6 +286,7 @@ class DecodeEngine:
         self.verify_graph = None
         self.speculate_graph = None
         self.sampling = None             # set_sampling: {"seed"} while the head samples; the parameters live in device tensors
+        self.penalties = None            # set_penalties: the (repetition, frequency, presence) device tensors while the heads penalise
 
     # ---- the sampling head (qserve_amd.sampling, csrc/sample_rows.hip) --------------------------------------------------------
     def set_sampling(self, temperature, top_k=0, top_p=1.0, seed=0):
@@ -411,6 +413,13 @@ class DecodeEngine:
             else:
                 residual_add_(h, proj)
 
+    def _prefill_entry(self, what):
+        """What every prefill entry refuses BEFORE it touches the cache: penalties on - the head of a prefill draws its token before
+        the new prompt's history exists, so it could not penalise."""
+        assert self.penalties is None, \
+            f"{what}: the prefill head does not penalise (the history of the new prompt does not exist yet) - set_penalties(None), " \
+            "prefill, enable_drafting, then set_penalties again"
+
     def _prompt_head(self, last_rows, prompt_len):
         """Last-token states -> `hidden`, first sampled token -> `tokens`, lengths = prompt_len + 1."""
         self.hidden.copy_(last_rows)
@@ -434,6 +443,7 @@ class DecodeEngine:
         -> gate_up -> silu_and_mul+quant -> down -> residual.  All sequences have `prompt_len` tokens.  Leaves the
         cache filled, `hidden` = last-token states, `tokens` = first sampled token, lengths = prompt_len + 1."""
         from .flash import flash_attn_varlen_func
+        self._prefill_entry("prefill")
         cfg, B, dev = self.cfg, self.B, self.dev
         assert self.with_lm_head and prompt_len + 1 <= self.max_len
         T = B * prompt_len
@@ -467,6 +477,7 @@ class DecodeEngine:
         `prefill`, [B * prompt_len], sequence-major."""
         from . import append as appendmod      # (looked up per call: `appendmod.append` is the seam tests wrap)
         # (max_past = c0, known on the host: a long past at a small batch is cut into page ranges - append_attention_split.hip)
+        self._prefill_entry("prefill_chunked")
         cfg, B, dev = self.cfg, self.B, self.dev
         assert self.with_lm_head and prompt_len + 1 <= self.max_len and chunk >= 1
         if tokens is None:
@@ -500,6 +511,7 @@ class DecodeEngine:
         decode kernels only read the aliased pages and write at slots >= P64.  `chunk`: tokens per sequence and pass (None: no
         chunking).  Single GPU, with the lm_head."""
         from . import append as appendmod
+        self._prefill_entry("prefill_shared")
         cfg, B, dev = self.cfg, self.B, self.dev
         assert self.with_lm_head and not self.vocab_parallel and self.tp_world == 1, "prefill_shared: single GPU, with the lm_head"
         prefix_tokens, suffix_tokens = prefix_tokens.to(dev), suffix_tokens.to(dev)
@@ -585,6 +597,7 @@ class DecodeEngine:
         assert not sampled or self.sampling is not None, "verify_tree(sampled=True): set_sampling first"
         if device_walk:
             return self._verify_tree_device(draft_tokens, par, sampled=sampled)
+        assert self.penalties is None, "verify_tree: penalties (set_penalties) need device_walk=True - the host walk does not penalise"
         max_past = int(self.lengths.max()) - 1
         assert max_past + n <= self.mb * 64, "verify_tree: the tree does not fit the sequences' page tables"
         toks = draft_tokens.to(dev).clone()
@@ -689,6 +702,8 @@ class DecodeEngine:
         layernorm_ops.rms_norm(final, h, self.norm_w, cfg["eps"])
         logits = torch.matmul(final, self.lm_head.t())
         am = torch.empty((B * n,), dtype=torch.int64, device=dev)
+        if self.penalties is not None:                                      # (the lengths have not advanced yet)
+            self._penalize(logits, toks, c["tree"])
         if sampled:
             self._sample(logits, am, self._node_keys(c["depth"]))
         else:
@@ -700,7 +715,7 @@ class DecodeEngine:
         self.tokens.copy_(nxt)                                              # in place: captured graphs read these tensors
         self.lengths.add_(accept_lens)
         self._len_bound += n
-        self.last_verify_logits = logits.view(B, n, -1)
+        self.last_verify_logits = logits.view(B, n, -1)                     # (penalised, while set_penalties is on)
         return accept_idx, accept_lens, am.view(B, n)
 
     def capture_verify(self, parents, max_past=None, sampled=False):
@@ -734,7 +749,7 @@ class DecodeEngine:
         self._len_bound -= n                       # (the captured call has not run: only replays advance the lengths)
         # every tensor the graph touches and that was allocated outside the capture stays referenced as long as the graph does: the
         # four outputs of the walk (two of them are not part of the result) and the tree's constants (the cache may evict them)
-        self._verify_keep = (out, self._tree_constants(par))
+        self._verify_keep = (out, self._tree_constants(par), self.penalties, getattr(self, "prompt_lens", None))
         self.verify_graph, self._verify_n, self._verify_result = g, n, res
         return g
 
@@ -763,6 +778,7 @@ class DecodeEngine:
         `min_match`: the drafter's parameters (drafting.ngram_draft_tree) from now on.  `pad_token`: what a node without a candidate
         holds - the verification embeds every node, so it must be a token of the vocabulary (0 <= pad_token < vocab; checked).  A
         second call (after another prefill) refills the SAME buffers in place: graphs captured since the first call stay valid.
+        `prompt_lens` int32 [B] holds P, where the generated text begins (what set_penalties counts as generated); refilled as well.
         Single GPU, with the lm_head."""
         assert self.with_lm_head and not self.vocab_parallel and self.tp_world == 1, "enable_drafting: single GPU, with the lm_head"
         assert 1 <= int(min_match) <= int(max_ngram) <= draftingmod.MAX_NGRAM, \
@@ -780,10 +796,46 @@ class DecodeEngine:
             # and the buffer its `past` is computed into
             self._step_record = (torch.zeros((B, 1), dtype=torch.int64, device=dev), torch.zeros((B, 1), dtype=torch.int32, device=dev),
                                  torch.ones((B,), dtype=torch.int32, device=dev), torch.zeros((B,), dtype=torch.int32, device=dev))
+            self.prompt_lens = torch.zeros((B,), dtype=torch.int32, device=dev)   # P: where the generated text begins (set_penalties)
         self.history.zero_()
+        self.prompt_lens.fill_(P)
         self.history[:, :P] = prompt
         self.history[:, P] = self.tokens
         self._draft_params = (int(max_ngram), int(min_match), int(pad_token))
+
+    # ---- repetition, presence and frequency penalties (qserve_amd.penalties, csrc/penalize_rows.hip) ----------------------------
+    def set_penalties(self, repetition=1.0, frequency=0.0, presence=0.0):
+        """Penalise the logits in front of every head that reads `history` (after enable_drafting): one `penalties.penalize_rows` launch
+        directly in front of the arg-max / the sampler of step() (hence capture() / run()) - context: the text history[b, :lengths[b]] -
+        and of verify_tree(device_walk=True) (hence capture_verify, speculate, capture_speculate) - context of node i: the text plus the
+        drafted tokens on the path to i, what a plain step() would see at that position if the path is accepted, so the generated tokens
+        still do not depend on what was drafted.  Greedy heads are penalised too.  x = x / repetition if x > 0 else x * repetition for
+        every token of the context; then x -= frequency * c + presence * (c > 0), c = the token's occurrences behind the prompt (the P
+        of enable_drafting).  set_penalties(None) switches it off: every path launches exactly what it launches without this call.
+        The three values live in persistent float32 [B] device tensors that are filled in place, so a captured graph sees later changes
+        of them; whether the launch exists at all is frozen into a capture - capture after switching.  `last_verify_logits` holds the
+        PENALISED logits while on.  Limits: the first token of a sequence is drawn by the prefill head, unpenalised (a prefill entry
+        refuses to run while penalties are on); the host-walk verify_tree(device_walk=False) refuses too; single GPU, with the lm_head;
+        the history's capacity prompt_len + max_new must not exceed 65 472 (16-bit counts)."""
+        if repetition is None:
+            self.penalties = None
+            return
+        assert self.with_lm_head and not self.vocab_parallel and self.tp_world == 1, "set_penalties: single GPU, with the lm_head"
+        assert getattr(self, "history", None) is not None, "set_penalties: enable_drafting first (the penalties read `history`)"
+        assert self.history.size(1) <= penaltiesmod.MAX_CAP, \
+            f"set_penalties: the history holds {self.history.size(1)} tokens per sequence, the penalty counts at most {penaltiesmod.MAX_CAP}"
+        assert self.cfg["vocab"] >= 8 and self.cfg["vocab"] % 8 == 0, "set_penalties: the logit rows need a vocabulary that is a multiple of 8"
+        assert float(repetition) > 0.0, f"set_penalties: repetition={float(repetition)} must be > 0"
+        if getattr(self, "_pen_values", None) is None:
+            self._pen_values = tuple(torch.empty((self.B,), dtype=torch.float32, device=self.dev) for _ in range(3))
+        for t, v in zip(self._pen_values, (repetition, frequency, presence)):
+            t.fill_(float(v))
+        self.penalties = self._pen_values
+
+    def _penalize(self, logits, node_tokens=None, tree=None):
+        """The launch in front of a head: `logits` [B * n, V] in place, from `history`, the lengths as they stand and the draft."""
+        rep, freq, pres = self.penalties
+        penaltiesmod.penalize_rows(logits, self.history, self.lengths, self.prompt_lens, node_tokens, tree, rep, freq, pres)
 
     def _record_step(self):
         """history[b, lengths[b] - 1] = tokens[b], after step() advanced the lengths: history_append with a path of the root alone at
@@ -851,7 +903,7 @@ class DecodeEngine:
         self._len_bound -= n                       # (the captured round has not run: only replays advance the lengths)
         # every tensor the graph touches and that was allocated outside the capture stays referenced as long as the graph does: the
         # draft buffer, the four outputs of the walk, the tree's constants (the cache may evict them), step()'s record constants
-        self._speculate_keep = (draft, out, self._tree_constants(par), self._step_record, self.history)
+        self._speculate_keep = (draft, out, self._tree_constants(par), self._step_record, self.history, self.penalties, self.prompt_lens)
         self.speculate_graph, self._speculate_n, self._speculate_result = g, n, res
         return g
 
@@ -966,6 +1018,8 @@ class DecodeEngine:
             self._head_finish(self.head_cand_res)
         elif self.with_lm_head:
             logits = torch.matmul(self.final, self.lm_head.t())      # un-quantised fp16 lm_head (:392,476)
+            if self.penalties is not None:                           # context: history[b, :lengths[b]], the text so far
+                self._penalize(logits)
             if self.sampling is not None:
                 self._sample(logits, self.tokens, self._step_keys())
             else:
