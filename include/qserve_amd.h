@@ -702,6 +702,13 @@ int qs_ngram_draft_lds_tokens(void);   /* history tokens the drafter stages in L
  * it is not part of the shipped ABI.) */
 int qs_debug_copy_split_workspace(void* dst, size_t bytes);
 
+/* Tests: where the RoPE cos / sin values of the current device come from.  The writers and the decode kernels read a library-managed
+ * table where one covers a row's position and evaluate the same values in the kernel elsewhere; the tables live in 8 slots per device,
+ * keyed by (base, length), and are never freed.  *slots_used = occupied slots, *longest_len_for_base = rows of the longest table whose
+ * base equals `base` exactly (0: none - every position of that base is evaluated in the kernel).  Host only, read only: no launch,
+ * no allocation, nothing but hipGetDevice; safe inside a stream capture.  QS_EINVAL: null output, no current device. */
+int qs_debug_rope_table_state(float base, int* slots_used, int* longest_len_for_base);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1027,13 +1027,33 @@ struct RopeTable {
 // address.  A longer table for the same base is a new entry (the old one stays alive for the graphs that captured it).
 constexpr int ROPE_SLOTS = 8;
 RopeTable g_rope[16][ROPE_SLOTS];
+std::mutex g_rope_mutex;   // host state of the slots (several host threads may drive their own bound streams)
 
 }  // namespace
+
+// tests (include/qserve_amd.h): the table slots of the current device as qs_rope_table would find them - read only, no device work
+extern "C" int qs_debug_rope_table_state(float base, int* slots_used, int* longest_len_for_base) {
+    QS_REQUIRE(slots_used && longest_len_for_base, "debug_rope_table_state: null output");
+    std::lock_guard<std::mutex> lock(g_rope_mutex);
+    int dev = 0;
+    *slots_used = *longest_len_for_base = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) {
+        (void)hipGetLastError();
+        qs_set_error("debug_rope_table_state: no current device");
+        return QS_EINVAL;
+    }
+    for (int i = 0; i < ROPE_SLOTS; ++i) {
+        const RopeTable& r = g_rope[dev][i];
+        if (!r.tab) continue;
+        ++*slots_used;
+        if (r.base == base && r.len > *longest_len_for_base) *longest_len_for_base = r.len;
+    }
+    return QS_OK;
+}
 
 // Library-managed RoPE table (per device, per base).  Returns nullptr when it cannot be (re)built right now, e.g.
 // while the stream is being captured into a graph before the first eager call; callers then compute in-kernel.
 const float2* qs_rope_table(float base, int max_pos, hipStream_t st, int* len_out) {
-    static std::mutex g_rope_mutex;   // host state of the slots (several host threads may drive their own bound streams)
     std::lock_guard<std::mutex> lock(g_rope_mutex);
     int dev = 0;
     *len_out = 0;

@@ -97,3 +97,13 @@ def per_group_problem_torch(M, N, K, device, seed=0):
     ascales = (torch.rand((M,), device=device, generator=g) * 0.045 + 0.005).half()
     return dict(A=A, qweight=qweight, s2_scales=s2_scales, s2_zeros=s2_zeros, wscales=wscales, ascales=ascales,
                 w8=deq.reshape(N, K).to(torch.int8))
+
+
+def rope_table_state(base):
+    """(occupied RoPE table slots of the current device, rows of the longest table of exactly this base; 0 = none):
+    include/qserve_amd.h qs_debug_rope_table_state."""
+    import ctypes
+    from qserve_amd._lib import check, lib
+    slots, longest = ctypes.c_int(-1), ctypes.c_int(-1)
+    check(lib.qs_debug_rope_table_state(float(base), ctypes.byref(slots), ctypes.byref(longest)), "qs_debug_rope_table_state")
+    return slots.value, longest.value
