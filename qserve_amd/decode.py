@@ -283,10 +283,23 @@ class DecodeEngine:
         self._len_bound = prompt_len
         self._tree_cache = {}            # parent tuple -> the per-tree device constants of the device-walk verify_tree
         self._layer_tables = None        # append.layer_table_pointers(self.tables), built on first use
-        self.verify_graph = None
-        self.speculate_graph = None
-        self.sampling = None             # set_sampling: {"seed"} while the head samples; the parameters live in device tensors
+        self.last_verify_logits = None   # verify_tree: the logits [B, n, V] of its last call
+        # capture_verify / capture_speculate: the graph, the tree's n, the persistent result triple, and every tensor the graph touches
+        # that was allocated outside the capture (it stays referenced as long as the graph does); _verify_draft: run_verify's input
+        self.verify_graph = self._verify_n = self._verify_result = self._verify_keep = self._verify_draft = None
+        self.speculate_graph = self._speculate_n = self._speculate_result = self._speculate_keep = None
+        self.sampling = None             # set_sampling: {"seed"} while the head samples; the parameters live in device tensors:
+        self._samp_t = self._samp_k = self._samp_p = self._samp_ids = None      # temperature, top-k, top-p per row; arange(B)
         self.penalties = None            # set_penalties: the (repetition, frequency, presence) device tensors while the heads penalise
+        self._pen_values = None          # ... and while they do not: the same tensors, created by the first set_penalties
+        # enable_drafting: the text of every sequence int32 [B, max_len], where its generated part begins int32 [B], the constants of
+        # step()'s history_append, and (max_ngram, min_match, pad_token)
+        self.history = self.prompt_lens = self._step_record = self._draft_params = None
+
+    def _single_gpu(self, what):
+        """What every entry behind the un-cut fp16 lm_head asks for (sampling, penalties, shared prefixes, tree verification, drafting):
+        under tensor parallelism the vocabulary-parallel greedy head stays the only one."""
+        assert self.with_lm_head and not self.vocab_parallel and self.tp_world == 1, f"{what}: single GPU, with the lm_head"
 
     # ---- the sampling head (qserve_amd.sampling, csrc/sample_rows.hip) --------------------------------------------------------
     def set_sampling(self, temperature, top_k=0, top_p=1.0, seed=0):
@@ -301,9 +314,9 @@ class DecodeEngine:
         if temperature is None:
             self.sampling = None
             return
-        assert self.with_lm_head and not self.vocab_parallel and self.tp_world == 1, "set_sampling: single GPU, with the lm_head"
+        self._single_gpu("set_sampling")
         from .append import MAX_TREE
-        if getattr(self, "_samp_t", None) is None:
+        if self._samp_t is None:
             rows = self.B * MAX_TREE                      # (verify_tree samples B * n rows, n <= MAX_TREE)
             self._samp_t = torch.empty((rows,), dtype=torch.float32, device=self.dev)
             self._samp_k = torch.empty((rows,), dtype=torch.int32, device=self.dev)
@@ -323,6 +336,21 @@ class DecodeEngine:
     def _step_keys(self):
         """The keys of the tokens the head is about to draw: (b, lengths[b]) - the position the new token will hold."""
         return samplingmod.position_keys(self._samp_ids, self.lengths)
+
+    def _head(self, final, out, keys=None, draft=()):
+        """The head of every path but the vocabulary-parallel one: the un-quantised fp16 lm_head on the normed rows `final`
+        (llama_w4a8_unpad.py:392,476), the penalty launch while set_penalties is on (`draft`: the drafted tokens and the tree of a
+        verification; a step's context is the text alone; the prefill entries and the host-walk verify_tree refuse to run while penalties
+        are on, so their heads never penalise), then out[r] = the arg-max of row r or, with `keys`, the token drawn under the
+        Philox keys keys() - computed behind the logits, from the lengths as they stand then.  -> the logits (penalised, while on)."""
+        logits = torch.matmul(final, self.lm_head.t())
+        if self.penalties is not None:
+            self._penalize(logits, *draft)
+        if keys is not None:
+            self._sample(logits, out, keys())
+        else:
+            argmax_rows_(logits, out)                                # greedy sampler
+        return logits
 
     # ---- fill the cache for positions [0, prompt_len) through the prefill writer (random K/V source) ----------
     def prefill_cache(self, prompt_len, chunk=8):
@@ -353,44 +381,70 @@ class DecodeEngine:
             gate_up=torch.empty((T, 2 * self.inter), dtype=f16, device=dev),
             mlp_act=torch.empty((T, self.inter), dtype=f16, device=dev))
 
-    def _prompt_layers(self, h, bufs, attend):
-        """The layer stack of the is_prompt path, in place on h (fp16 [T, hid]); `bufs`: _prompt_buffers of >= T rows.
-        attend(li, qkv) -> fp16 [T, H * 128]: cache write + attention of layer li on its packed qkv rows (prefill: writer + flash
-        over the call's own k / v; prefill_chunked: append attention over the pages + the chunk)."""
-        cfg, T = self.cfg, h.size(0)
+    def _quant(self, out, x, q_sum, q_scale):
+        """out / q_scale (/ q_sum: per-channel weights only) = the per-token int8 quantisation of the fp16 rows x."""
+        if self.group_size == -1:
+            fused_kernels.invoke_quant_fuse_sum(out, x, q_sum, q_scale)
+        else:
+            fused_kernels.invoke_quant(out, x, q_scale)
+
+    def _layer_stack(self, h, bufs, attention, planes):
+        """THE transformer layer body (llama_w4a8_unpad.py:330-361 per layer), in place on the fp16 rows h - every path of the engine
+        runs this one generator.  `bufs`: the activation buffers under the keys of _prompt_buffers, of exactly h's rows, plus "proj_res",
+        where the sum of the row-parallel partial "proj" over the ranks is read from (the same tensor unless a collective writes
+        elsewhere).  attention(li, qkv): cache write + attention of layer li on its packed qkv rows, leaving the QUANTISED output in
+        bufs["qo"] / ["q_scale"] / ["q_sum"].  `planes`: name -> K-slice plane buffer of the row-parallel projections that run as
+        planes (the decode step's; empty elsewhere).  Yields the partial wherever tensor parallelism needs its sum all-reduce (2 per
+        layer; nothing at world size 1), so that the caller decides how the collective is issued."""
+        eps = self.cfg["eps"]
         fuse_sum, fuse = self.group_size == -1, self.fuse_pairs
-        qa, qo, q_mlp, q_scale, q_sum, qkv, proj, gate_up, mlp_act = (
-            bufs[k][:T] for k in ("qa", "qo", "q_mlp", "q_scale", "q_sum", "qkv", "proj", "gate_up", "mlp_act"))
+        qa, qo, q_mlp, q_scale, q_sum, qkv, proj, proj_res, gate_up, mlp_act = (
+            bufs[k] for k in ("qa", "qo", "q_mlp", "q_scale", "q_sum", "qkv", "proj", "proj_res", "gate_up", "mlp_act"))
         sums = q_sum if fuse_sum else None
 
         def norm_quant(x, w):
             if fuse_sum:
-                layernorm_ops.rms_norm_general_fuse_sum(qa, x, w, q_sum, q_scale, cfg["eps"], True)
+                layernorm_ops.rms_norm_general_fuse_sum(qa, x, w, q_sum, q_scale, eps, True)
             else:
-                layernorm_ops.rms_norm_general(qa, x, w, q_scale, cfg["eps"], True)
+                layernorm_ops.rms_norm_general(qa, x, w, q_scale, eps, True)
 
         def add_norm_quant(x, delta, w):
             if fuse:
-                fusedmod.add_residual_rms_norm_general(qa, x, delta, w, q_scale, cfg["eps"], sums)
+                fusedmod.add_residual_rms_norm_general(qa, x, delta, w, q_scale, eps, sums)
             else:
                 residual_add_(x, delta)
                 norm_quant(x, w)
+
+        # (row-parallel GEMM, add + norm + quant) as K-slice planes: the GEMM leaves int32 partial sums per K slice, the row
+        # kernel that follows sums them and applies the GEMM's epilogue (bit-identical pair fusion; single GPU only - under
+        # tensor parallelism the all-reduce sits between the two)
+        def proj_add_norm_quant(lin, name, xq, x, w):
+            pl = planes.get(name) if fuse and self.tp_world == 1 else None
+            if pl is not None:
+                lin.planes(xq, pl)
+                lin.add_norm_quant_planes(qa, x, pl, q_scale, q_sum, w, q_scale, eps, sums)
+                return True
+            return False
+
+        def row_parallel(lin, xq):
+            """lin(xq) -> the rows to add to h: the projection's output or, under tensor parallelism, its sum over the ranks."""
+            lin(xq, q_scale, q_sum, proj)
+            if self.tp_world == 1:
+                return proj
+            yield proj
+            if lin.defer_bias and lin.bias is not None:
+                proj_res.add_(lin.bias)                              # once, after the reduce (SURVEY 8e)
+            return proj_res
 
         nl = len(self.layers)
         for li, L in enumerate(self.layers):
             if li == 0:
                 norm_quant(h, L["ln1"])
             L["qkv"](qa, q_scale, q_sum, qkv)
-            attn = attend(li, qkv)
-            if fuse_sum:
-                fused_kernels.invoke_quant_fuse_sum(qo, attn, q_sum, q_scale)
-            else:
-                fused_kernels.invoke_quant(qo, attn, q_scale)
-            L["o"](qo, q_scale, q_sum, proj)
-            tpmod.all_reduce_sum_(proj)
-            if L["o"].defer_bias and L["o"].bias is not None:
-                proj += L["o"].bias
-            add_norm_quant(h, proj, L["ln2"])
+            attention(li, qkv)
+            if not proj_add_norm_quant(L["o"], "o", qo, h, L["ln2"]):
+                res = yield from row_parallel(L["o"], qo)
+                add_norm_quant(h, res, L["ln2"])
             if fuse and L["gate_up"].bias is None:     # gate_up GEMM with the silu * mul epilogue, then the quantiser
                 L["gate_up"].silu_mul(qa, q_scale, q_sum, mlp_act, gate_up)
             else:
@@ -400,18 +454,28 @@ class DecodeEngine:
             else:
                 if not fuse:
                     activation_ops.silu_and_mul(mlp_act, gate_up)
-                if fuse_sum:
-                    fused_kernels.invoke_quant_fuse_sum(q_mlp, mlp_act, q_sum, q_scale)
-                else:
-                    fused_kernels.invoke_quant(q_mlp, mlp_act, q_scale)
-            L["down"](q_mlp, q_scale, q_sum, proj)
-            tpmod.all_reduce_sum_(proj)
-            if L["down"].defer_bias and L["down"].bias is not None:
-                proj += L["down"].bias
+                self._quant(q_mlp, mlp_act, q_sum, q_scale)
+            if li + 1 < nl and proj_add_norm_quant(L["down"], "down", q_mlp, h, self.layers[li + 1]["ln1"]):
+                continue                                             # (next layer's input norm done from the planes)
+            res = yield from row_parallel(L["down"], q_mlp)
             if li + 1 < nl:
-                add_norm_quant(h, proj, self.layers[li + 1]["ln1"])
+                add_norm_quant(h, res, self.layers[li + 1]["ln1"])   # next layer's input norm
             else:
-                residual_add_(h, proj)
+                residual_add_(h, res)
+
+    def _prompt_layers(self, h, bufs, attend):
+        """The layer stack of the is_prompt path, in place on h (fp16 [T, hid]); `bufs`: _prompt_buffers of >= T rows.
+        attend(li, qkv) -> fp16 [T, H * 128]: cache write + attention of layer li on its packed qkv rows (prefill: writer + flash
+        over the call's own k / v; prefill_chunked: append attention over the pages + the chunk).  The row-parallel partials are
+        summed through the process group, in place."""
+        b = {k: v[:h.size(0)] for k, v in bufs.items()}
+        b["proj_res"] = b["proj"]
+
+        def attention(li, qkv):
+            self._quant(b["qo"], attend(li, qkv), b["q_sum"], b["q_scale"])
+
+        for partial in self._layer_stack(h, b, attention, {}):
+            tpmod.all_reduce_sum_(partial)
 
     def _prefill_entry(self, what):
         """What every prefill entry refuses BEFORE it touches the cache: penalties on - the head of a prefill draws its token before
@@ -428,12 +492,11 @@ class DecodeEngine:
             tpmod.all_reduce_sum_(self._head_local())                # in place, through the process group
             self._head_finish(self.head_cand)
         else:
-            logits = torch.matmul(self.final, self.lm_head.t())
-            if self.sampling is not None:
+            def keys():
                 self.lengths.fill_(prompt_len)                       # the first new token will hold position prompt_len
-                self._sample(logits, self.tokens, self._step_keys())
-            else:
-                argmax_rows_(logits, self.tokens)
+                return self._step_keys()
+
+            self._head(self.final, self.tokens, keys if self.sampling is not None else None)
         self.lengths.fill_(prompt_len + 1)
         self._len_bound = prompt_len + 1
 
@@ -483,22 +546,27 @@ class DecodeEngine:
         if tokens is None:
             tokens = torch.randint(0, cfg["vocab"], (B * prompt_len,), device=dev,
                                    generator=torch.Generator(device=dev).manual_seed(7))
-        tokens = tokens.view(B, prompt_len)
         chunk = min(chunk, prompt_len)
-        bufs = self._prompt_buffers(B * chunk)
-        h = None
-        for c0 in range(0, prompt_len, chunk):
-            n = min(chunk, prompt_len - c0)
-            h = torch.index_select(self.embed, 0, tokens[:, c0:c0 + n].reshape(-1))
-            cu = torch.arange(0, B + 1, device=dev, dtype=torch.int32) * n
-            past = torch.full((B,), c0, dtype=torch.int32, device=dev)
 
-            def attend(li, qkv):
-                return appendmod.append(qkv, cu, past, self.tables[li], self.H, self.Hkv, self.size_per_token,
-                                        cfg["rope_theta"], self.int4, max_seqlen_q=n, max_past=c0).reshape(B * n, -1)
+        def attend(li, qkv, cu, past, n, c0):
+            return appendmod.append(qkv, cu, past, self.tables[li], self.H, self.Hkv, self.size_per_token, cfg["rope_theta"], self.int4,
+                                    max_seqlen_q=n, max_past=c0)
 
-            self._prompt_layers(h, bufs, attend)
+        h = self._prompt_chunks(tokens.view(B, prompt_len), chunk, self._prompt_buffers(B * chunk), 0, attend)
         self._prompt_head(h.view(B, -1, self.hid)[:, -1], prompt_len)
+
+    def _prompt_chunks(self, tokens, chunk, bufs, base, attend):
+        """The layer stack over `tokens` [rows, L], `chunk` columns per pass (the last pass may be shorter), sequence `r` of a pass being
+        tokens[r, c0 : c0 + n] behind a past of base + c0.  attend(li, qkv, cu_seqlens, past_lens, n, c0) -> fp16 [rows * n, H, 128]:
+        the append attention of layer li.  -> the hidden rows of the last pass, [rows * n, hid] sequence-major."""
+        rows, dev, h = tokens.size(0), self.dev, None
+        for c0 in range(0, tokens.size(1), chunk):
+            n = min(chunk, tokens.size(1) - c0)
+            h = torch.index_select(self.embed, 0, tokens[:, c0:c0 + n].reshape(-1))
+            cu = torch.arange(0, rows + 1, device=dev, dtype=torch.int32) * n
+            past = torch.full((rows,), base + c0, dtype=torch.int32, device=dev)
+            self._prompt_layers(h, bufs, lambda li, qkv: attend(li, qkv, cu, past, n, c0).reshape(rows * n, -1))
+        return h
 
     def prefill_shared(self, prefix_tokens, suffix_tokens, chunk=None):
         """`prefill_chunked` for B prompts that begin with the SAME `prefix_tokens` [P] and go on with their own `suffix_tokens`
@@ -513,7 +581,7 @@ class DecodeEngine:
         from . import append as appendmod
         self._prefill_entry("prefill_shared")
         cfg, B, dev = self.cfg, self.B, self.dev
-        assert self.with_lm_head and not self.vocab_parallel and self.tp_world == 1, "prefill_shared: single GPU, with the lm_head"
+        self._single_gpu("prefill_shared")
         prefix_tokens, suffix_tokens = prefix_tokens.to(dev), suffix_tokens.to(dev)
         assert prefix_tokens.dim() == 1 and suffix_tokens.dim() == 2 and suffix_tokens.size(0) == B and suffix_tokens.size(1) >= 1, \
             "prefill_shared: prefix_tokens [P], suffix_tokens [B, S] with S >= 1"
@@ -525,35 +593,22 @@ class DecodeEngine:
         chunk = max(P64, R) if chunk is None else min(chunk, max(P64, R))
         bufs = self._prompt_buffers(max(B * min(chunk, R), min(chunk, P64)))
         # 1. the whole pages of the prefix, once, through row 0 of the tables
-        for c0 in range(0, P64, chunk):
-            n = min(chunk, P64 - c0)
-            h = torch.index_select(self.embed, 0, prefix_tokens[c0:c0 + n])
-            cu1 = torch.tensor([0, n], dtype=torch.int32, device=dev)
-            past = torch.full((1,), c0, dtype=torch.int32, device=dev)
+        def attend_prefix(li, qkv, cu, past, n, c0):
+            return appendmod.append(qkv, cu, past, self.tables[li][0:1], self.H, self.Hkv, self.size_per_token, cfg["rope_theta"],
+                                    self.int4, max_seqlen_q=n, max_past=c0)
 
-            def attend(li, qkv):
-                return appendmod.append(qkv, cu1, past, self.tables[li][0:1], self.H, self.Hkv, self.size_per_token,
-                                        cfg["rope_theta"], self.int4, max_seqlen_q=n, max_past=c0).reshape(n, -1)
-
-            self._prompt_layers(h, bufs, attend)
+        self._prompt_chunks(prefix_tokens[:P64].unsqueeze(0), chunk, bufs, 0, attend_prefix)
         # 2. every sequence names sequence 0's prefix pages
         for t in self.tables:
             t[:, :, :P64 // 64] = t[0:1, :, :P64 // 64]
         # 3. the rest of every prompt, the shared pages read once for the batch
         groups = appendmod.shared_prefix_groups([B], [P64], dev, batch=B)
-        h = None
-        for c0 in range(0, R, chunk):
-            n = min(chunk, R - c0)
-            h = torch.index_select(self.embed, 0, own[:, c0:c0 + n].reshape(-1))
-            cu = torch.arange(0, B + 1, device=dev, dtype=torch.int32) * n
-            past = torch.full((B,), P64 + c0, dtype=torch.int32, device=dev)
 
-            def attend(li, qkv):
-                return appendmod.append_shared(qkv, cu, past, self.tables[li], self.H, self.Hkv, self.size_per_token, cfg["rope_theta"],
-                                               self.int4, groups, max_seqlen_q=n, max_group_tokens=B * n, max_prefix=P64,
-                                               max_suffix_past=c0).reshape(B * n, -1)
+        def attend_own(li, qkv, cu, past, n, c0):
+            return appendmod.append_shared(qkv, cu, past, self.tables[li], self.H, self.Hkv, self.size_per_token, cfg["rope_theta"],
+                                           self.int4, groups, max_seqlen_q=n, max_group_tokens=B * n, max_prefix=P64, max_suffix_past=c0)
 
-            self._prompt_layers(h, bufs, attend)
+        h = self._prompt_chunks(own, chunk, bufs, P64, attend_own)
         self._prompt_head(h.view(B, -1, self.hid)[:, -1], P + S)
 
     # ---- verification of a draft tree (no reference counterpart; qserve_amd.append, csrc/append_tree.hip) ---------------------
@@ -587,12 +642,9 @@ class DecodeEngine:
         token drawn at its parent, else that token is the bonus token.  (Siblings' subtrees share keys at equal depth; one path is
         walked.)  Commit, `tokens`, `lengths` as above; the third element of the triple is the sampled tokens."""
         from . import append as appendmod
-        cfg, B, dev = self.cfg, self.B, self.dev
-        par = [int(p) for p in (parents.tolist() if hasattr(parents, "tolist") else parents)]
+        B, dev = self.B, self.dev
+        par = self._tree_arg(parents, "verify_tree", drafting=False)
         n = len(par)
-        assert self.with_lm_head and not self.vocab_parallel and self.tp_world == 1, "verify_tree: single GPU, with the lm_head"
-        assert 1 <= n <= appendmod.MAX_TREE and par[0] == -1 and all(0 <= p < i for i, p in enumerate(par) if i), \
-            "verify_tree: parents[0] = -1 (the root), every other node hangs off an earlier one; at most 64 nodes"
         assert tuple(draft_tokens.shape) == (B, n) and draft_tokens.dtype == torch.int64
         assert not sampled or self.sampling is not None, "verify_tree(sampled=True): set_sampling first"
         if device_walk:
@@ -600,26 +652,7 @@ class DecodeEngine:
         assert self.penalties is None, "verify_tree: penalties (set_penalties) need device_walk=True - the host walk does not penalise"
         max_past = int(self.lengths.max()) - 1
         assert max_past + n <= self.mb * 64, "verify_tree: the tree does not fit the sequences' page tables"
-        toks = draft_tokens.to(dev).clone()
-        toks[:, 0] = self.tokens
-        cu = torch.arange(0, B + 1, device=dev, dtype=torch.int32) * n
-        past = (self.lengths - 1).to(torch.int32)
-        masks = appendmod.tree_masks_from_parents(par * B, [i * n for i in range(B + 1)]).to(dev)
-        h = torch.index_select(self.embed, 0, toks.reshape(-1))
-
-        def attend(li, qkv):
-            return appendmod.append_tree(qkv, cu, past, self.tables[li], masks, self.H, self.Hkv, self.size_per_token,
-                                         cfg["rope_theta"], self.int4, max_seqlen_q=n, max_past=max_past).reshape(B * n, -1)
-
-        self._prompt_layers(h, self._prompt_buffers(B * n), attend)
-        final = torch.empty_like(h)
-        layernorm_ops.rms_norm(final, h, self.norm_w, cfg["eps"])
-        logits = torch.matmul(final, self.lm_head.t())
-        am = torch.empty((B * n,), dtype=torch.int64, device=dev)
-        if sampled:
-            self._sample(logits, am, self._node_keys(torch.tensor(_tree_depths(par), dtype=torch.int32, device=dev)))
-        else:
-            argmax_rows_(logits, am)
+        _, toks, past, h, final, logits, am = self._verify_forward(draft_tokens, par, max_past, sampled)
         am = am.view(B, n)
         # the greedy walk, on the host (n <= 64 nodes per sequence)
         am_h, tok_h = am.cpu().tolist(), toks.cpu().tolist()
@@ -655,7 +688,7 @@ class DecodeEngine:
         return self._len_bound
 
     def _tree_constants(self, par):
-        """The device tensors a device-walk verify needs for the tree `par` (built on the host once, then served from the cache)."""
+        """The device tensors a verification or a drafter needs for the tree `par` (built on the host once, then served from the cache)."""
         from . import append as appendmod
         key = tuple(par)
         c = self._tree_cache.get(key)
@@ -678,14 +711,14 @@ class DecodeEngine:
         n = depth.numel()
         return samplingmod.position_keys(self._samp_ids.view(-1, 1).expand(self.B, n), self.lengths.view(-1, 1) + depth.view(1, -1)).reshape(-1)
 
-    def _verify_tree_device(self, draft_tokens, par, max_past=None, out=None, sampled=False):
-        """verify_tree(device_walk=True) behind its argument checks.  `max_past`: the planner hint (None: the host-side bound);
-        `out`: accept_greedy's four output tensors (None: fresh ones)."""
+    def _verify_forward(self, draft_tokens, par, max_past, sampled):
+        """The forward pass of a verification, the same for both walks: the roots take the place of column 0 of the draft, the B * n
+        rows run through the layer stack with `append_tree` at past = lengths - 1 (`max_past`: the planner hint), then norm and head
+        (penalised while set_penalties is on - the lengths have not advanced yet -, sampled under the node keys with `sampled`).
+        Nothing leaves the device.  -> (the tree's constants, tokens [B, n], past, hidden rows, normed rows, logits, the head's tokens
+        [B * n])."""
         from . import append as appendmod
         cfg, B, dev, n = self.cfg, self.B, self.dev, len(par)
-        assert self._len_bound - 1 + n <= self.mb * 64, \
-            "verify_tree: the tree does not fit the sequences' page tables (by the host-side bound of the lengths: sync_length_bound())"
-        hint = self._len_bound - 1 if max_past is None else int(max_past)
         c = self._tree_constants(par)
         cu, masks = c["cu"], c["masks"]
         toks = draft_tokens.to(dev).clone(memory_format=torch.contiguous_format)
@@ -695,20 +728,25 @@ class DecodeEngine:
 
         def attend(li, qkv):
             return appendmod.append_tree(qkv, cu, past, self.tables[li], masks, self.H, self.Hkv, self.size_per_token,
-                                         cfg["rope_theta"], self.int4, max_seqlen_q=n, max_past=hint).reshape(B * n, -1)
+                                         cfg["rope_theta"], self.int4, max_seqlen_q=n, max_past=max_past).reshape(B * n, -1)
 
         self._prompt_layers(h, self._prompt_buffers(B * n), attend)
         final = torch.empty_like(h)
         layernorm_ops.rms_norm(final, h, self.norm_w, cfg["eps"])
-        logits = torch.matmul(final, self.lm_head.t())
         am = torch.empty((B * n,), dtype=torch.int64, device=dev)
-        if self.penalties is not None:                                      # (the lengths have not advanced yet)
-            self._penalize(logits, toks, c["tree"])
-        if sampled:
-            self._sample(logits, am, self._node_keys(c["depth"]))
-        else:
-            argmax_rows_(logits, am)
-        accept_idx, accept_lens, last, nxt = appendmod.accept_greedy(toks.view(-1), am, c["parents"], cu, max_accept=n, out=out)
+        logits = self._head(final, am, (lambda: self._node_keys(c["depth"])) if sampled else None, draft=(toks, c["tree"]))
+        return c, toks, past, h, final, logits, am
+
+    def _verify_tree_device(self, draft_tokens, par, max_past=None, out=None, sampled=False):
+        """verify_tree(device_walk=True) behind its argument checks.  `max_past`: the planner hint (None: the host-side bound);
+        `out`: accept_greedy's four output tensors (None: fresh ones)."""
+        from . import append as appendmod
+        B, n = self.B, len(par)
+        assert self._len_bound - 1 + n <= self.mb * 64, \
+            "verify_tree: the tree does not fit the sequences' page tables (by the host-side bound of the lengths: sync_length_bound())"
+        hint = self._len_bound - 1 if max_past is None else int(max_past)
+        c, toks, past, h, final, logits, am = self._verify_forward(draft_tokens, par, hint, sampled)
+        accept_idx, accept_lens, last, nxt = appendmod.accept_greedy(toks.view(-1), am, c["parents"], c["cu"], max_accept=n, out=out)
         appendmod.commit_path_layers(c["layer_tables"], past, accept_idx, accept_lens, self.mb, self.Hkv, self.size_per_token, self.int4)
         self.hidden.copy_(torch.index_select(h, 0, last))
         self.final.copy_(torch.index_select(final, 0, last))
@@ -718,38 +756,29 @@ class DecodeEngine:
         self.last_verify_logits = logits.view(B, n, -1)                     # (penalised, while set_penalties is on)
         return accept_idx, accept_lens, am.view(B, n)
 
+    def _walk_outputs(self, n):
+        """Persistent (accept_idx, accept_lens, last_row, next_token) tensors for the device walk of a captured n-node verification."""
+        B, dev = self.B, self.dev
+        return (torch.zeros((B, n), dtype=torch.int32, device=dev), torch.zeros((B,), dtype=torch.int32, device=dev),
+                torch.zeros((B,), dtype=torch.int64, device=dev), torch.zeros((B,), dtype=torch.int64, device=dev))
+
     def capture_verify(self, parents, max_past=None, sampled=False):
-        """Capture one device-walk verify_tree of the tree `parents` in a hipGraph, the way capture() captures step(): a warm-up call on
-        a side stream first (allocator, lazy initialisation, the split-KV workspace - whose first use must not fall inside a capture),
-        then the capture over a persistent [B, n] draft buffer.  run_verify(draft_tokens) replays it.  `max_past`: the hint the split
+        """Capture one device-walk verify_tree of the tree `parents` in a hipGraph, the way capture() captures step() (`_capture`: a
+        warm-up call first), over a persistent [B, n] draft buffer.  run_verify(draft_tokens) replays it.  `max_past`: the hint the split
         plan is frozen with (default: the engine's capacity, prompt_len + max_new); results never depend on it.  The warm-up is a real
         verification of an all-zero draft: it advances `tokens`, `lengths` and the cache like any other, so capture on a state you
         restore or do not care about - what capture() implies for step().  `sampled=True` captures verify_tree(sampled=True) (after
         set_sampling).  Single GPU, with the lm_head."""
-        from . import append as appendmod
-        par = [int(p) for p in (parents.tolist() if hasattr(parents, "tolist") else parents)]
+        par = self._tree_arg(parents, "capture_verify", drafting=False)
         n, B, dev = len(par), self.B, self.dev
-        assert self.with_lm_head and not self.vocab_parallel and self.tp_world == 1, "capture_verify: single GPU, with the lm_head"
-        assert 1 <= n <= appendmod.MAX_TREE and par[0] == -1 and all(0 <= p < i for i, p in enumerate(par) if i), \
-            "capture_verify: parents[0] = -1 (the root), every other node hangs off an earlier one; at most 64 nodes"
         assert not sampled or self.sampling is not None, "capture_verify(sampled=True): set_sampling first"
         hint = self.max_len if max_past is None else int(max_past)
         self._verify_draft = torch.zeros((B, n), dtype=torch.int64, device=dev)
-        out = (torch.zeros((B, n), dtype=torch.int32, device=dev), torch.zeros((B,), dtype=torch.int32, device=dev),
-               torch.zeros((B,), dtype=torch.int64, device=dev), torch.zeros((B,), dtype=torch.int64, device=dev))
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            self._verify_tree_device(self._verify_draft, par, max_past=hint, out=out, sampled=sampled)     # warm-up outside capture
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            res = self._verify_tree_device(self._verify_draft, par, max_past=hint, out=out, sampled=sampled)
-        self._len_bound -= n                       # (the captured call has not run: only replays advance the lengths)
+        out = self._walk_outputs(n)
+        g, res = self._capture(lambda: self._verify_tree_device(self._verify_draft, par, max_past=hint, out=out, sampled=sampled), n)
         # every tensor the graph touches and that was allocated outside the capture stays referenced as long as the graph does: the
         # four outputs of the walk (two of them are not part of the result) and the tree's constants (the cache may evict them)
-        self._verify_keep = (out, self._tree_constants(par), self.penalties, getattr(self, "prompt_lens", None))
+        self._verify_keep = (out, self._tree_constants(par), self.penalties, self.prompt_lens)
         self.verify_graph, self._verify_n, self._verify_result = g, n, res
         return g
 
@@ -780,7 +809,7 @@ class DecodeEngine:
         second call (after another prefill) refills the SAME buffers in place: graphs captured since the first call stay valid.
         `prompt_lens` int32 [B] holds P, where the generated text begins (what set_penalties counts as generated); refilled as well.
         Single GPU, with the lm_head."""
-        assert self.with_lm_head and not self.vocab_parallel and self.tp_world == 1, "enable_drafting: single GPU, with the lm_head"
+        self._single_gpu("enable_drafting")
         assert 1 <= int(min_match) <= int(max_ngram) <= draftingmod.MAX_NGRAM, \
             f"enable_drafting: 1 <= min_match <= max_ngram <= {draftingmod.MAX_NGRAM}"
         assert 0 <= int(pad_token) < self.cfg["vocab"], \
@@ -790,7 +819,7 @@ class DecodeEngine:
         P = prompt.size(1)
         assert P + 1 <= self.max_len and bool((self.lengths == P + 1).all()), \
             "enable_drafting: call it right after a prefill of these prompt tokens (every sequence holds P + 1 tokens)"
-        if getattr(self, "history", None) is None:
+        if self.history is None:
             self.history = torch.zeros((B, self.max_len), dtype=torch.int32, device=dev)
             # what history_append needs to record ONE token per sequence (a path of the root alone): constants of step()'s record,
             # and the buffer its `past` is computed into
@@ -820,13 +849,13 @@ class DecodeEngine:
         if repetition is None:
             self.penalties = None
             return
-        assert self.with_lm_head and not self.vocab_parallel and self.tp_world == 1, "set_penalties: single GPU, with the lm_head"
-        assert getattr(self, "history", None) is not None, "set_penalties: enable_drafting first (the penalties read `history`)"
+        self._single_gpu("set_penalties")
+        assert self.history is not None, "set_penalties: enable_drafting first (the penalties read `history`)"
         assert self.history.size(1) <= penaltiesmod.MAX_CAP, \
             f"set_penalties: the history holds {self.history.size(1)} tokens per sequence, the penalty counts at most {penaltiesmod.MAX_CAP}"
         assert self.cfg["vocab"] >= 8 and self.cfg["vocab"] % 8 == 0, "set_penalties: the logit rows need a vocabulary that is a multiple of 8"
         assert float(repetition) > 0.0, f"set_penalties: repetition={float(repetition)} must be > 0"
-        if getattr(self, "_pen_values", None) is None:
+        if self._pen_values is None:
             self._pen_values = tuple(torch.empty((self.B,), dtype=torch.float32, device=self.dev) for _ in range(3))
         for t, v in zip(self._pen_values, (repetition, frequency, presence)):
             t.fill_(float(v))
@@ -844,13 +873,14 @@ class DecodeEngine:
         torch.sub(self.lengths, 2, out=past)
         draftingmod.history_append(self.history, past, nodes, idx, ones, self.tokens)
 
-    def _tree_arg(self, parents, what):
+    def _tree_arg(self, parents, what, drafting=True):
+        """`parents` of the entry `what` as a list, checked: a tree, on a single GPU, `drafting`: with a history to draft from."""
         from . import append as appendmod
         par = [int(p) for p in (parents.tolist() if hasattr(parents, "tolist") else parents)]
-        assert self.with_lm_head and not self.vocab_parallel and self.tp_world == 1, f"{what}: single GPU, with the lm_head"
+        self._single_gpu(what)
         assert 1 <= len(par) <= appendmod.MAX_TREE and par[0] == -1 and all(0 <= p < i for i, p in enumerate(par) if i), \
             f"{what}: parents[0] = -1 (the root), every other node hangs off an earlier one; at most 64 nodes"
-        assert getattr(self, "history", None) is not None, f"{what}: enable_drafting first"
+        assert not drafting or self.history is not None, f"{what}: enable_drafting first"
         return par
 
     def draft_tree(self, parents, out=None):
@@ -878,9 +908,8 @@ class DecodeEngine:
         return res
 
     def capture_speculate(self, parents, max_past=None, sampled=False):
-        """Capture one speculate() round of the tree `parents` in ONE hipGraph, the way capture_verify captures a verification: a
-        warm-up round on a side stream first (allocator, lazy initialisation, the split-KV workspace - whose first use must not fall
-        inside a capture), then the capture on one stream over persistent draft and output buffers.  run_speculate() replays it.
+        """Capture one speculate() round of the tree `parents` in ONE hipGraph, the way capture_verify captures a verification
+        (`_capture`: a warm-up round first), on one stream over persistent draft and output buffers.  run_speculate() replays it.
         `max_past`: the hint the split plan is frozen with (default: the engine's capacity, prompt_len + max_new); results never depend
         on it.  The warm-up is a real round: it advances `tokens`, `lengths`, the cache and `history` like any other.  `sampled=True`
         captures speculate(sampled=True) (after set_sampling).  Single GPU, with the lm_head, after enable_drafting."""
@@ -889,18 +918,8 @@ class DecodeEngine:
         assert not sampled or self.sampling is not None, "capture_speculate(sampled=True): set_sampling first"
         hint = self.max_len if max_past is None else int(max_past)
         draft = torch.zeros((B, n), dtype=torch.int64, device=dev)
-        out = (torch.zeros((B, n), dtype=torch.int32, device=dev), torch.zeros((B,), dtype=torch.int32, device=dev),
-               torch.zeros((B,), dtype=torch.int64, device=dev), torch.zeros((B,), dtype=torch.int64, device=dev))
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            self._speculate(par, max_past=hint, out=out, draft=draft, sampled=sampled)      # warm-up outside capture
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            res = self._speculate(par, max_past=hint, out=out, draft=draft, sampled=sampled)
-        self._len_bound -= n                       # (the captured round has not run: only replays advance the lengths)
+        out = self._walk_outputs(n)
+        g, res = self._capture(lambda: self._speculate(par, max_past=hint, out=out, draft=draft, sampled=sampled), n)
         # every tensor the graph touches and that was allocated outside the capture stays referenced as long as the graph does: the
         # draft buffer, the four outputs of the walk, the tree's constants (the cache may evict them), step()'s record constants
         self._speculate_keep = (draft, out, self._tree_constants(par), self._step_record, self.history, self.penalties, self.prompt_lens)
@@ -923,111 +942,35 @@ class DecodeEngine:
         """The step as a generator: yields the row-parallel partial output wherever tensor parallelism needs its sum
         all-reduce (2 per layer), so that the caller decides how the collective is issued (eagerly between hipGraph
         pieces, inside one graph, or not at all at world size 1)."""
-        cfg, B = self.cfg, self.B
-        fuse_sum = self.group_size == -1
         if self.with_lm_head:
             torch.index_select(self.embed, 0, self.tokens, out=self.hidden)
-        h = self.hidden
-        qa, qo = self.q_act, self.q_attn
-        fuse = self.fuse_pairs
-        sums = self.q_sum if fuse_sum else None
-
-        def norm_quant(x, w):
-            if fuse_sum:
-                layernorm_ops.rms_norm_general_fuse_sum(qa, x, w, self.q_sum, self.q_scale, cfg["eps"], True)
-            else:
-                layernorm_ops.rms_norm_general(qa, x, w, self.q_scale, cfg["eps"], True)
-
-        def add_norm_quant(x, delta, w):
-            if fuse:
-                fusedmod.add_residual_rms_norm_general(qa, x, delta, w, self.q_scale, cfg["eps"], sums)
-            else:
-                residual_add_(x, delta)
-                norm_quant(x, w)
-
-        # (row-parallel GEMM, add + norm + quant) as K-slice planes: the GEMM leaves int32 partial sums per K slice, the row
-        # kernel that follows sums them and applies the GEMM's epilogue (bit-identical pair fusion; single GPU only - under
-        # tensor parallelism the all-reduce sits between the two)
-        def proj_add_norm_quant(lin, name, xq, x, w):
-            pl = self.planes.get(name) if fuse and self.tp_world == 1 else None
-            if pl is not None:
-                lin.planes(xq, pl)
-                lin.add_norm_quant_planes(qa, x, pl, self.q_scale, self.q_sum, w, self.q_scale, cfg["eps"], sums)
-                return True
-            return False
-
-        nl = len(self.layers)
-        for li, L in enumerate(self.layers):
-            if li == 0:
-                norm_quant(h, L["ln1"])
-            L["qkv"](qa, self.q_scale, self.q_sum, self.qkv_buf)
-            q, k, v = self.qkv_buf.split([self.H * 128, self.Hkv * 128, self.Hkv * 128], dim=-1)
-            if fuse:         # attention + invoke_quant(_fuse_sum) of its output in one call (bit-identical pair fusion)
-                fusedmod.single_query_attention_quant(
-                    q.reshape(B, self.H, 128), k.reshape(B, self.Hkv, 128), v.reshape(B, self.Hkv, 128), self.tables[li],
-                    self.lengths, qo, self.q_scale, 8192, 64, self.size_per_token, self.max_len, 128, cfg["rope_theta"],
-                    True, self.int4, True, quant_sum=sums)
-            else:
-                attn = fused_attention.single_query_attention(
-                    q.reshape(B, self.H, 128), k.reshape(B, self.Hkv, 128), v.reshape(B, self.Hkv, 128), self.tables[li],
-                    self.lengths, None, 8192, 64, self.size_per_token, self.max_len, 128, cfg["rope_theta"], True,
-                    self.int4, True)
-                attn = attn.reshape(B, -1)
-                if fuse_sum:
-                    fused_kernels.invoke_quant_fuse_sum(qo, attn, self.q_sum, self.q_scale)
-                else:
-                    fused_kernels.invoke_quant(qo, attn, self.q_scale)
-            if not proj_add_norm_quant(L["o"], "o", qo, h, L["ln2"]):
-                L["o"](qo, self.q_scale, self.q_sum, self.proj_out)
-                res = self.proj_out
-                if self.tp_world > 1:
-                    yield self.proj_out
-                    res = self.proj_res
-                    if L["o"].defer_bias and L["o"].bias is not None:
-                        res += L["o"].bias                    # once, after the reduce (SURVEY 8e)
-                add_norm_quant(h, res, L["ln2"])
-            if fuse and L["gate_up"].bias is None:     # gate_up GEMM with the silu * mul epilogue, then the quantiser
-                L["gate_up"].silu_mul(qa, self.q_scale, self.q_sum, self.mlp_act, self.gate_up_buf)
-            else:
-                L["gate_up"](qa, self.q_scale, self.q_sum, self.gate_up_buf)
-            if fuse and L["gate_up"].bias is not None:
-                fusedmod.silu_and_mul_quant(self.q_mlp, self.gate_up_buf, self.q_scale, sums)
-            else:
-                if not fuse:
-                    activation_ops.silu_and_mul(self.mlp_act, self.gate_up_buf)
-                if fuse_sum:
-                    fused_kernels.invoke_quant_fuse_sum(self.q_mlp, self.mlp_act, self.q_sum, self.q_scale)
-                else:
-                    fused_kernels.invoke_quant(self.q_mlp, self.mlp_act, self.q_scale)
-            if li + 1 < nl and proj_add_norm_quant(L["down"], "down", self.q_mlp, h, self.layers[li + 1]["ln1"]):
-                continue                                             # (next layer's input norm done from the planes)
-            L["down"](self.q_mlp, self.q_scale, self.q_sum, self.proj_out)
-            res = self.proj_out
-            if self.tp_world > 1:
-                yield self.proj_out
-                res = self.proj_res
-                if L["down"].defer_bias and L["down"].bias is not None:
-                    res += L["down"].bias
-            if li + 1 < nl:
-                add_norm_quant(h, res, self.layers[li + 1]["ln1"])   # next layer's input norm
-            else:
-                residual_add_(h, res)
-        layernorm_ops.rms_norm(self.final, h, self.norm_w, cfg["eps"])
+        bufs = dict(qa=self.q_act, qo=self.q_attn, q_mlp=self.q_mlp, q_scale=self.q_scale, q_sum=self.q_sum, qkv=self.qkv_buf,
+                    proj=self.proj_out, proj_res=self.proj_res, gate_up=self.gate_up_buf, mlp_act=self.mlp_act)
+        yield from self._layer_stack(self.hidden, bufs, self._step_attention, self.planes)
+        layernorm_ops.rms_norm(self.final, self.hidden, self.norm_w, self.cfg["eps"])
         if self.with_lm_head and self.vocab_parallel:
             yield self._head_local()                                 # candidates of the ranks meet in the sum all-reduce
             self._head_finish(self.head_cand_res)
-        elif self.with_lm_head:
-            logits = torch.matmul(self.final, self.lm_head.t())      # un-quantised fp16 lm_head (:392,476)
-            if self.penalties is not None:                           # context: history[b, :lengths[b]], the text so far
-                self._penalize(logits)
-            if self.sampling is not None:
-                self._sample(logits, self.tokens, self._step_keys())
-            else:
-                argmax_rows_(logits, self.tokens)                    # greedy sampler
+        elif self.with_lm_head:                                      # (penalty context: history[b, :lengths[b]], the text so far)
+            self._head(self.final, self.tokens, self._step_keys if self.sampling is not None else None)
         self.lengths.add_(1)
-        if getattr(self, "history", None) is not None:               # enable_drafting: the new token joins the text
+        if self.history is not None:                                 # enable_drafting: the new token joins the text
             self._record_step()
 
+    def _step_attention(self, li, qkv):
+        """single_query_attention of layer li on the step's qkv rows -> q_attn / q_scale / q_sum, quantised."""
+        cfg, B = self.cfg, self.B
+        q, k, v = qkv.split([self.H * 128, self.Hkv * 128, self.Hkv * 128], dim=-1)
+        q, k, v = q.reshape(B, self.H, 128), k.reshape(B, self.Hkv, 128), v.reshape(B, self.Hkv, 128)
+        if self.fuse_pairs:  # attention + invoke_quant(_fuse_sum) of its output in one call (bit-identical pair fusion)
+            fusedmod.single_query_attention_quant(
+                q, k, v, self.tables[li], self.lengths, self.q_attn, self.q_scale, 8192, 64, self.size_per_token, self.max_len, 128,
+                cfg["rope_theta"], True, self.int4, True, quant_sum=self.q_sum if self.group_size == -1 else None)
+        else:
+            attn = fused_attention.single_query_attention(
+                q, k, v, self.tables[li], self.lengths, None, 8192, 64, self.size_per_token, self.max_len, 128, cfg["rope_theta"], True,
+                self.int4, True)
+            self._quant(self.q_attn, attn.reshape(B, -1), self.q_sum, self.q_scale)
 
     def _head_local(self):
         """This rank's greedy candidate per sequence -> its slot of `head_cand` (the other slots zero)."""
@@ -1061,6 +1004,29 @@ class DecodeEngine:
             self._reduce(partial)
         self._len_bound += 1
 
+    def _warm_up(self, fn):
+        """fn() once on a side stream, outside any capture (allocator, lazy initialisation, the split-KV workspace - whose first use
+        must not fall inside a capture), joined and synchronised.  A real call: it advances the engine like any other."""
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            fn()
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+
+    def _capture(self, fn, advance):
+        """Warm fn up, then capture it in one hipGraph -> (the graph, what the captured call returned: tensors the replays overwrite).
+        `advance`: what one call of fn adds to `_len_bound` - taken back for the captured call, which has not run: only replays advance
+        the lengths.  Frozen into the graph: which launches exist (sampling or arg-max and its seed, penalties, the history record)
+        and the planner hints; read at replay: every persistent device tensor, the parameters of set_sampling / set_penalties among
+        them."""
+        self._warm_up(fn)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            res = fn()
+        self._len_bound -= advance
+        return g, res
+
     def capture(self, piecewise=None):
         """Capture one step in hipGraph(s) (removes ~400 launches of host overhead per step).
 
@@ -1070,20 +1036,11 @@ class DecodeEngine:
         `piecewise=False` captures the collectives too (needs a capturable backend)."""
         if piecewise is None:
             piecewise = self.tp_world > 1 and self.ar is None   # the direct all-reduce is an ordinary kernel: one graph
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            self.step()                       # warm-up outside capture (allocator, lazy init)
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
         self.pieces = None
         if not piecewise:
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self.step()
-            self._len_bound -= 1              # (the captured step has not run)
-            self.graph = g
-            return g
+            self.graph, _ = self._capture(self.step, 1)
+            return self.graph
+        self._warm_up(self.step)
         pool = torch.cuda.graph_pool_handle()
         pieces, gen = [], self._segments()
         while True:
@@ -1117,7 +1074,7 @@ class DecodeEngine:
                                "qserve_amd._lib.lib.qs_device_reset() before the next step")
 
     def run(self):
-        if getattr(self, "pieces", None):
+        if self.pieces:
             for g, partial in self.pieces:
                 g.replay()
                 if partial is not None:

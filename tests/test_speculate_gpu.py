@@ -73,7 +73,7 @@ def test_step_records_its_token_only_with_drafting_enabled(gpu):
     import _speculate_engine as S
     toks = E.prompt(gpu)
     plain, e = E.engine(toks), S.drafting_engine(toks)
-    assert not hasattr(plain, "history")
+    assert plain.history is None
     before = e.history.clone()
     for k in range(1, 3):
         plain.step()
@@ -97,7 +97,7 @@ def test_enable_drafting_checks_the_pad_token_and_refills_in_place(gpu):
     for bad in (-1, TINY["vocab"], 1 << 40):
         with pytest.raises(AssertionError, match="pad_token"):
             e.enable_drafting(toks, pad_token=bad)
-    assert not hasattr(e, "history")
+    assert e.history is None                                 # (declared by the engine, created by the first call that is accepted)
     e.enable_drafting(toks, **S.NGRAM)
     first, where = e.history.clone(), (e.history.data_ptr(), [t.data_ptr() for t in e._step_record])
     e.history.fill_(7)
