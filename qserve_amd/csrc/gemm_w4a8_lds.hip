@@ -14,9 +14,9 @@
 //   * the activation image is XOR-swizzled through the DMA SOURCE address (LDS destination stays lane-linear) so that
 //     the 16-row x 16-byte operand reads are conflict-free;
 //   * the two K-halves are summed exactly (int32) through LDS; fused fp32 epilogue as before.
-#include "common.h"
+// Host side (below the kernel): launch_pair launches one instantiation, qs_launch_gemm_pair (gemm_w4a8.h) picks it.
+#include "gemm_w4a8.h"
 
-extern qs_flag g_tiled_dbg;   // gemm_w4a8_tiled.hip: qs_set_gemm_variant(3100 + bits) timing experiments
 namespace {
 
 constexpr int NS = 4;                 // ring depth (k-steps)
@@ -270,9 +270,7 @@ __global__ __launch_bounds__(256, 1) void w4a8_gemm_pair(const int8_t* __restric
 }
 
 template <int MT, int MODE, int OUTK, int DBG = 0>
-int launch_pair(const int8_t* A, const uint8_t* W, const int8_t* zeros, const int8_t* scales8, const void* wscales,
-                const void* ascales, const void* wszs, const void* assums, void* out, int M, int N, int K,
-                hipStream_t stream) {
+int launch_pair(const GemmArgs& a) {
     auto kern = w4a8_gemm_pair<MT, MODE, OUTK, DBG>;
     const size_t smem = (size_t)2 * NS * (16 * MT * 128) + 4 * NS * WBYTES + 4 * NS * 256;
     static bool lds_reserved[QS_MAX_DEVICES] = {};   // per instantiation (= kernel) and device
@@ -280,40 +278,26 @@ int launch_pair(const int8_t* A, const uint8_t* W, const int8_t* zeros, const in
         qs_set_error("w4a8 gemm (lds): cannot reserve %zu bytes of LDS: %s", smem, hipGetErrorString(e));
         return (int)e;
     }
-    dim3 grid(N / 128, (M + 16 * MT - 1) / (16 * MT));
-    hipLaunchKernelGGL(kern, grid, dim3(256), smem, stream, A, W, zeros, scales8,
-                       reinterpret_cast<const __half*>(wscales), reinterpret_cast<const __half*>(ascales),
-                       reinterpret_cast<const __half*>(wszs), reinterpret_cast<const __half*>(assums), out, M, N, K, g_epi_fma);
+    dim3 grid(a.N / 128, (a.M + 16 * MT - 1) / (16 * MT));
+    hipLaunchKernelGGL(kern, grid, dim3(256), smem, a.stream, a.A, a.W, a.zeros, a.scales8, a.wscales, a.ascales, a.wszs, a.assums,
+                       a.out, a.M, a.N, a.K, g_epi_fma);
     return qs_launch_status("w4a8 gemm (lds)");
 }
 
 }  // namespace
 
-// Entry used by the dispatcher in gemm_w4a8.hip.  Preconditions (checked there): N % 128 == 0, K % 128 == 0, K >= 256.
-int qs_launch_gemm_pair(int mode, int outk, const int8_t* A, const uint8_t* W, const int8_t* zeros,
-                        const int8_t* scales8, const void* wscales, const void* ascales, const void* wszs,
-                        const void* assums, void* out, int M, int N, int K, hipStream_t stream) {
-    const int mtile = M <= 16 ? 1 : M <= 32 ? 2 : M <= 48 ? 3 : 4;
+// Entry used by the dispatcher (gemm_w4a8.h).  Preconditions (gemm_plan.h): N % 128 == 0, K % 128 == 0, K >= 256.
+int qs_launch_gemm_pair(int mode, int outk, const GemmArgs& a) {
+    const int mtile = a.M <= 16 ? 1 : a.M <= 32 ? 2 : a.M <= 48 ? 3 : 4;
 #ifdef QS_TIMING   // timing experiments (results are wrong by design): not in the shipped library
-    if (mode == 0 && outk == 0 && mtile == 4 && g_tiled_dbg) {
-        if (g_tiled_dbg == 1) return launch_pair<4, 0, 0, 1>(A, W, zeros, scales8, wscales, ascales, wszs, assums, out, M, N, K, stream);
-        if (g_tiled_dbg == 2) return launch_pair<4, 0, 0, 2>(A, W, zeros, scales8, wscales, ascales, wszs, assums, out, M, N, K, stream);
-        if (g_tiled_dbg == 3) return launch_pair<4, 0, 0, 3>(A, W, zeros, scales8, wscales, ascales, wszs, assums, out, M, N, K, stream);
-    }
+#define QS_D(D) if (mode == 0 && outk == 0 && mtile == 4 && g_tiled_dbg == D) return launch_pair<4, 0, 0, D>(a);
+    QS_D(1) QS_D(2) QS_D(3)
+#undef QS_D
 #endif
-#define QS_P(MTV, MODEV, OUTV) \
-    return launch_pair<MTV, MODEV, OUTV>(A, W, zeros, scales8, wscales, ascales, wszs, assums, out, M, N, K, stream)
-#define QS_PM(MODEV, OUTV)        \
-    do {                          \
-        if (mtile == 1) QS_P(1, MODEV, OUTV); \
-        if (mtile == 2) QS_P(2, MODEV, OUTV); \
-        if (mtile == 3) QS_P(3, MODEV, OUTV); \
-        QS_P(4, MODEV, OUTV);     \
-    } while (0)
-    if (mode == 0 && outk == 0) QS_PM(0, 0);
-    if (mode == 0 && outk == 1) QS_PM(0, 1);
-    if (mode == 1 && outk == 0) QS_PM(1, 0);
-    QS_PM(1, 1);
-#undef QS_PM
+#define QS_P(MTV, MODEV, OUTV) if (mtile == MTV && mode == MODEV && outk == OUTV) return launch_pair<MTV, MODEV, OUTV>(a);
+    QS_P(1, 0, 0) QS_P(2, 0, 0) QS_P(3, 0, 0) QS_P(4, 0, 0) QS_P(1, 0, 1) QS_P(2, 0, 1) QS_P(3, 0, 1) QS_P(4, 0, 1)
+    QS_P(1, 1, 0) QS_P(2, 1, 0) QS_P(3, 1, 0) QS_P(4, 1, 0) QS_P(1, 1, 1) QS_P(2, 1, 1) QS_P(3, 1, 1) QS_P(4, 1, 1)
 #undef QS_P
+    qs_set_error("w4a8 gemm (lds): unsupported mode=%d output kind=%d", mode, outk);
+    return QS_ENOSUP;
 }

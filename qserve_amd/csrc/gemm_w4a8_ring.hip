@@ -20,7 +20,9 @@
 //   * LDS images are bank-conflict free (permutation applied on the DMA source side, as in gemm_w4a8_tiled.hip);
 //   * the KG partial int32 tiles are summed exactly through LDS, the fp32 epilogue is fused, its scale operands are
 //     requested before the reduction, and the fp16 tile leaves through LDS as whole 128-byte rows.
-#include "common.h"
+// Host side (below the kernel): launch_ring sizes the ring and launches one instantiation, qs_launch_gemm_ring (gemm_w4a8.h)
+// picks it from (mode, output kind, geometry); which geometry serves a problem is gemm_plan.h's business.
+#include "gemm_w4a8.h"
 #include <type_traits>
 
 // A/B switches (qs_set_gemm_variant(5000 + bits); every setting computes the same results):
@@ -773,9 +775,8 @@ __global__ __launch_bounds__(512, 1) void w4a8_gemm_ring(const int8_t* __restric
 }
 
 template <int MT, int WN, int MODE, int OUTK, bool KSPLIT>
-int launch_ring(const int8_t* A, const uint8_t* W, const int8_t* zeros, const int8_t* scales8, const void* wscales,
-                const void* ascales, const void* wszs, const void* assums, void* out, int M, int N, int K,
-                int mblocks, int ksplit, int* slabs, unsigned* counters, hipStream_t stream) {
+int launch_ring(const GemmArgs& a, int mblocks, int ksplit, int* slabs, unsigned* counters) {
+    const int N = a.N, K = a.K;
     auto kern = w4a8_gemm_ring<MT, WN, MODE, OUTK, KSPLIT>;
     constexpr int KG = 8 / WN;
     constexpr int GSTAGE = ring_gstage<MT, WN, MODE>();
@@ -804,16 +805,10 @@ int launch_ring(const int8_t* A, const uint8_t* W, const int8_t* zeros, const in
         return QS_EINVAL;
     }
     smem = 160 * 1024;                                 // the epilogue operands sit in the top SC_BYTES of the window
-    static size_t configured_dev[QS_MAX_DEVICES] = {};   // per instantiation and device
-    size_t& configured = configured_dev[qs_device_slot()];
-    if (configured < smem) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
-        if (e != hipSuccess) {
-            qs_set_error("w4a8 gemm (ring): cannot reserve LDS: %s", hipGetErrorString(e));
-            return (int)e;
-        }
-        configured = 160 * 1024;
+    static bool lds_reserved[QS_MAX_DEVICES] = {};   // per instantiation (= kernel) and device
+    if (const hipError_t e = qs_reserve_lds({reinterpret_cast<const void*>(kern)}, (int)smem, lds_reserved); e != hipSuccess) {
+        qs_set_error("w4a8 gemm (ring): cannot reserve LDS: %s", hipGetErrorString(e));
+        return (int)e;
     }
     dim3 grid((N / (64 * WN)) * mblocks * ksplit);
     // K slices across the XCDs (ring_coords): always for the planes form (no finisher); for the seam form with TWO slices only -
@@ -824,13 +819,11 @@ int launch_ring(const int8_t* A, const uint8_t* W, const int8_t* zeros, const in
                       (N / (64 * WN)) % (8 / ksplit) == 0 && !(g_ring_flags & 4096);
     int inject = 0;
     if (KSPLIT && OUTK != 3 && ksplit > 1) {
-        counters = qs_gemm_error_word(qs_scratch_slot(stream));   // the kernel's `counters` is the error word of the seam's bounded wait
+        counters = qs_gemm_error_word(qs_scratch_slot(a.stream));   // the kernel's `counters` is the error word of the seam's bounded wait
         if (g_inject_fault & 1) inject = 128, g_inject_fault &= ~1;
     }
-    hipLaunchKernelGGL(kern, grid, dim3(512), smem, stream, A, W, zeros, scales8,
-                       reinterpret_cast<const __half*>(wscales), reinterpret_cast<const __half*>(ascales),
-                       reinterpret_cast<const __half*>(wszs), reinterpret_cast<const __half*>(assums), out, M, N, K,
-                       mblocks, ns, ksplit, slabs, counters,
+    hipLaunchKernelGGL(kern, grid, dim3(512), smem, a.stream, a.A, a.W, a.zeros, a.scales8, a.wscales, a.ascales, a.wszs, a.assums,
+                       a.out, a.M, a.N, a.K, mblocks, ns, ksplit, slabs, counters,
                        (g_ring_flags & ~(3 | 16 | 128 | 2048 | 4096)) | inject | (g_epi_fma ? 16 : 0) | (kxcd ? 2048 : 0) |
                            ((g_ring_flags & 1) || (mblocks > 1 && N <= 8192 && !(g_ring_flags & 2)) ? 1 : 0));
     return qs_launch_status("w4a8 gemm (ring)");
@@ -847,69 +840,41 @@ extern "C" int qs_debug_ring_trace(void* buf) {
 
 namespace {
 template <int MT, int WN, int MODE, int OUTK>
-int ring_go(bool ks, const int8_t* A, const uint8_t* W, const int8_t* zeros, const int8_t* scales8, const void* wscales,
-            const void* ascales, const void* wszs, const void* assums, void* out, int M, int N, int K, int mblocks,
-            int ksplit, int* slabs, unsigned* counters, hipStream_t stream) {
+int ring_go(const GemmArgs& a, int mblocks, int ksplit, int* slabs, unsigned* counters) {
     if constexpr (OUTK == 3) {                        // planes exist in the K-sliced instantiation only (one slice = OUTK 1)
-        return launch_ring<MT, WN, MODE, OUTK, true>(A, W, zeros, scales8, wscales, ascales, wszs, assums, out, M, N, K, mblocks,
-                                                     ksplit, nullptr, nullptr, stream);
+        return launch_ring<MT, WN, MODE, OUTK, true>(a, mblocks, ksplit, nullptr, nullptr);
     } else {
         if constexpr (OUTK != 2) {
-            if (ks)
-                return launch_ring<MT, WN, MODE, OUTK, true>(A, W, zeros, scales8, wscales, ascales, wszs, assums, out, M, N, K,
-                                                             mblocks, ksplit, slabs, counters, stream);
+            if (ksplit > 1) return launch_ring<MT, WN, MODE, OUTK, true>(a, mblocks, ksplit, slabs, counters);
         }
-        return launch_ring<MT, WN, MODE, OUTK, false>(A, W, zeros, scales8, wscales, ascales, wszs, assums, out, M, N, K,
-                                                      mblocks, 1, nullptr, nullptr, stream);
+        return launch_ring<MT, WN, MODE, OUTK, false>(a, mblocks, 1, nullptr, nullptr);
     }
 }
 }  // namespace
 
-// Entry used by the dispatcher in gemm_w4a8.hip.  mt = m-tiles per workgroup (1, 2, 4), wn = units per workgroup
-// (1, 2, 4); ksplit = K slices (1 = none; > 1 needs the slab / counter workspace: (N/64) * mblocks * ksplit * mt KiB * 4 and
-// (N/64) * mblocks counters); preconditions (checked there): N % (64*wn) == 0, (K/64/ksplit) % (8/wn) == 0,
-// M*K and N*K/2 below 4 GiB.
-int qs_launch_gemm_ring(int mode, int outk, int mt, int wn, const int8_t* A, const uint8_t* W, const int8_t* zeros,
-                        const int8_t* scales8, const void* wscales, const void* ascales, const void* wszs,
-                        const void* assums, void* out, int M, int N, int K, int mblocks, int ksplit, int* slabs,
-                        unsigned* counters, hipStream_t stream) {
+// Entry used by the dispatcher (gemm_w4a8.h).  ksplit > 1 with a finished output needs the slab / counter workspace
+// (gemm_w4a8.hip ring_workspace_fits); preconditions (gemm_plan.h: ring_fits, offsets_fit): N % (64*wn) == 0,
+// (K/64/ksplit) % (8/wn) == 0, M*K and N*K/2 below 4 GiB.
+int qs_launch_gemm_ring(int mode, int outk, int mt, int wn, const GemmArgs& a, int mblocks, int ksplit, int* slabs,
+                        unsigned* counters) {
     if (outk == 2 && ksplit > 1) {
         qs_set_error("w4a8 gemm (ring): the activation epilogue has no K-sliced form");
         return QS_ENOSUP;
     }
-    if ((outk == 0 || outk == 2) && ((reinterpret_cast<uintptr_t>(wscales) & 3) || (mode == 0 && (reinterpret_cast<uintptr_t>(wszs) & 3)))) {
+    if ((outk == 0 || outk == 2) && ((reinterpret_cast<uintptr_t>(a.wscales) & 3) || (mode == 0 && (reinterpret_cast<uintptr_t>(a.wszs) & 3)))) {
         // (the reference reads them as half2, gemm_cuda.cu:581-582: the same requirement)
         qs_set_error("w4a8 gemm: wscales / w_szs must be 4-byte aligned");
         return QS_EINVAL;
     }
-    const bool ks = ksplit > 1;
-#define QS_R(MTV, WNV, MODEV, OUTV)                                                                                  \
-    return ring_go<MTV, WNV, MODEV, OUTV>(ks, A, W, zeros, scales8, wscales, ascales, wszs, assums, out, M, N, K, \
-                                          mblocks, ksplit, slabs, counters, stream)
-#define QS_RM(MODEV, OUTV)                              \
-    do {                                                \
-        if (wn == 4) {                                  \
-            if (mt == 4) QS_R(4, 4, MODEV, OUTV);       \
-        } else if (wn == 2) {                           \
-            if (mt == 8) QS_R(8, 2, MODEV, OUTV);       \
-            if (mt == 4) QS_R(4, 2, MODEV, OUTV);       \
-            if (mt == 2) QS_R(2, 2, MODEV, OUTV);       \
-        } else {                                        \
-            if (mt == 4) QS_R(4, 1, MODEV, OUTV);       \
-            if (mt == 2) QS_R(2, 1, MODEV, OUTV);       \
-            if (mt == 1) QS_R(1, 1, MODEV, OUTV);       \
-        }                                               \
-    } while (0)
-    if (mode == 0 && outk == 0) QS_RM(0, 0);
-    if (mode == 0 && outk == 1) QS_RM(0, 1);
-    if (mode == 0 && outk == 2) QS_RM(0, 2);
-    if (mode == 1 && outk == 0) QS_RM(1, 0);
-    if (mode == 1 && outk == 1) QS_RM(1, 1);
-    if (mode == 1 && outk == 2) QS_RM(1, 2);
-    if (mode == 0 && outk == 3) QS_RM(0, 3);
-    if (mode == 1 && outk == 3) QS_RM(1, 3);
+#define QS_R(MTV, WNV, MODEV, OUTV) \
+    if (mt == MTV && wn == WNV) return ring_go<MTV, WNV, MODEV, OUTV>(a, mblocks, ksplit, slabs, counters);
+#define QS_RM(M_, O_)                                                                                               \
+    if (mode == M_ && outk == O_) {                                                                                 \
+        QS_R(4, 4, M_, O_) QS_R(8, 2, M_, O_) QS_R(4, 2, M_, O_) QS_R(2, 2, M_, O_) QS_R(4, 1, M_, O_) QS_R(2, 1, M_, O_) QS_R(1, 1, M_, O_) \
+    }
+    QS_RM(0, 0) QS_RM(0, 1) QS_RM(0, 2) QS_RM(1, 0) QS_RM(1, 1) QS_RM(1, 2) QS_RM(0, 3) QS_RM(1, 3)
 #undef QS_RM
 #undef QS_R
-    qs_set_error("w4a8 gemm (ring): unsupported geometry mt=%d wn=%d", mt, wn);
+    qs_set_error("w4a8 gemm (ring): unsupported geometry mt=%d wn=%d", mt, wn);   // (or an output kind: none but 0 .. 3 exists)
     return QS_ENOSUP;
 }

@@ -19,7 +19,8 @@
 //   * LDS images are bank-conflict free by construction: the DMA writes lane-linear, so the permutation is applied to
 //     the per-lane SOURCE address (activations: see "pair image" below; weights: [tile][chunk e][k32 ^ tile][c]).
 //   * per-group: level-2 dequant in registers exactly as in the decode kernels (bit-faithful to the reference).
-#include "common.h"
+// Host side (below the kernel): launch_tiled launches one instantiation, qs_launch_gemm_tiled (gemm_w4a8.h) picks it.
+#include "gemm_w4a8.h"
 #include <type_traits>
 
 qs_flag g_tiled_dbg = 0;   // qs_set_gemm_variant(3100 + bits): 1 no MFMA, 2 no DMA, 4 no operand reads, 8 no barrier
@@ -600,9 +601,7 @@ __global__ __launch_bounds__(512, 1) void w4a8_gemm_tiled(const int8_t* __restri
 }
 
 template <int MT, int MODE, int OUTK, int DBG = 0>
-int launch_tiled(const int8_t* A, const uint8_t* W, const int8_t* zeros, const int8_t* scales8, const void* wscales,
-                 const void* ascales, const void* wszs, const void* assums, void* out, int M, int N, int K,
-                 hipStream_t stream) {
+int launch_tiled(const GemmArgs& a) {
     auto kern = w4a8_gemm_tiled<MT, MODE, OUTK, DBG>;
     constexpr int BM = 32 * MT;
     const size_t smem = (size_t)NS * (BM * 64 + WSTAGE + 512) + 3072;   // rings + the staged epilogue operands (the epilogue's 18 KiB of staging rows alias the rings)
@@ -611,45 +610,32 @@ int launch_tiled(const int8_t* A, const uint8_t* W, const int8_t* zeros, const i
         qs_set_error("w4a8 gemm (tiled): cannot reserve %zu bytes of LDS: %s", smem, hipGetErrorString(e));
         return (int)e;
     }
-    const int nbm = (M + BM - 1) / BM;
-    const int ntiles = nbm * (N / BN);
+    const int nbm = (a.M + BM - 1) / BM;
+    const int ntiles = nbm * (a.N / BN);
     constexpr bool persist = MT == 8 && OUTK != 1 && !(DBG & 2);
     const int cus = qs_num_cus();
     const int pmode = g_tiled_order / 10;             // 0: one workgroup per CU, 1: one per tile, 2: three (tests)
     dim3 grid(persist && pmode != 1 && ntiles > (pmode == 2 ? 3 : cus) ? (pmode == 2 ? 3 : cus) : ntiles);
-    hipLaunchKernelGGL(kern, grid, dim3(512), smem, stream, A, W, zeros, scales8,
-                       reinterpret_cast<const __half*>(wscales), reinterpret_cast<const __half*>(ascales),
-                       reinterpret_cast<const __half*>(wszs), reinterpret_cast<const __half*>(assums), out, M, N, K,
+    hipLaunchKernelGGL(kern, grid, dim3(512), smem, a.stream, a.A, a.W, a.zeros, a.scales8, a.wscales, a.ascales, a.wszs, a.assums,
+                       a.out, a.M, a.N, a.K,
                        nbm, g_tiled_order % 10, g_epi_fma, grid.x <= (unsigned)g_gemm_clk_cap ? g_gemm_clk : nullptr);
     return qs_launch_status("w4a8 gemm (tiled)");
 }
 
 }  // namespace
 
-// Entry used by the dispatcher in gemm_w4a8.hip.  Preconditions (checked there): N % 256 == 0, K % 128 == 0, K >= 256.
+// Entry used by the dispatcher (gemm_w4a8.h).  Preconditions (gemm_plan.h): N % 256 == 0, K % 128 == 0, K >= 256.
 // mtile = m-tiles per wave: 8 = 256-token tile, 4 = 128-token tile.
-int qs_launch_gemm_tiled(int mode, int outk, const int8_t* A, const uint8_t* W, const int8_t* zeros,
-                         const int8_t* scales8, const void* wscales, const void* ascales, const void* wszs,
-                         const void* assums, void* out, int M, int N, int K, int mtile, hipStream_t stream) {
-#define QS_T(MTV, MODEV, OUTV) \
-    return launch_tiled<MTV, MODEV, OUTV>(A, W, zeros, scales8, wscales, ascales, wszs, assums, out, M, N, K, stream)
-    const bool big = mtile == 8;
+int qs_launch_gemm_tiled(int mode, int outk, const GemmArgs& a, int mtile) {
 #ifdef QS_TIMING   // timing experiments (results are wrong by design): not in the shipped library
-    if (mode == 0 && outk == 0 && big && g_tiled_dbg) {
-#define QS_D(D) case D: return launch_tiled<8, 0, 0, D>(A, W, zeros, scales8, wscales, ascales, wszs, assums, out, M, N, K, stream)
-        switch (g_tiled_dbg) {
-            QS_D(1); QS_D(2); QS_D(3); QS_D(4); QS_D(6); QS_D(8); QS_D(10); QS_D(14);
-        default: break;
-        }
+#define QS_D(D) if (mode == 0 && outk == 0 && mtile == 8 && g_tiled_dbg == D) return launch_tiled<8, 0, 0, D>(a);
+    QS_D(1) QS_D(2) QS_D(3) QS_D(4) QS_D(6) QS_D(8) QS_D(10) QS_D(14)
 #undef QS_D
-    }
 #endif
-    if (mode == 0 && outk == 2) { if (big) QS_T(8, 0, 2); QS_T(4, 0, 2); }
-    if (mode == 1 && outk == 2) { if (big) QS_T(8, 1, 2); QS_T(4, 1, 2); }
-    if (mode == 0 && outk == 0) { if (big) QS_T(8, 0, 0); QS_T(4, 0, 0); }
-    if (mode == 0 && outk == 1) { if (big) QS_T(8, 0, 1); QS_T(4, 0, 1); }
-    if (mode == 1 && outk == 0) { if (big) QS_T(8, 1, 0); QS_T(4, 1, 0); }
-    if (big) QS_T(8, 1, 1);
-    QS_T(4, 1, 1);
+#define QS_T(MTV, MODEV, OUTV) if (mtile == MTV && mode == MODEV && outk == OUTV) return launch_tiled<MTV, MODEV, OUTV>(a);
+    QS_T(8, 0, 2) QS_T(4, 0, 2) QS_T(8, 1, 2) QS_T(4, 1, 2) QS_T(8, 0, 0) QS_T(4, 0, 0)
+    QS_T(8, 0, 1) QS_T(4, 0, 1) QS_T(8, 1, 0) QS_T(4, 1, 0) QS_T(8, 1, 1) QS_T(4, 1, 1)
 #undef QS_T
+    qs_set_error("w4a8 gemm (tiled): unsupported mode=%d output kind=%d m-tiles=%d", mode, outk, mtile);
+    return QS_ENOSUP;
 }

@@ -19,7 +19,8 @@
 // Everything else - 6-deep weight ring / 3-deep activation pair ring filled by LDS-DMA in whole 128-byte lines, counted vmcnt,
 // one raw barrier per stage, 16 x 16 super-tile walk, next tile's fill issued before the epilogue, LDS-staged fp16 rows - is
 // the tiled kernel's, re-derived for 256 threads (4 KiB per all-thread DMA instruction instead of 8).
-#include "common.h"
+// Host side (below the kernel): launch_wide launches one instantiation, qs_launch_gemm_wide (gemm_w4a8.h) picks it.
+#include "gemm_w4a8.h"
 #include <type_traits>
 #include <utility>
 
@@ -574,9 +575,7 @@ __global__ __launch_bounds__(256, 1) void w4a8_gemm_wide(const int8_t* __restric
 }
 
 template <int MODE, int OUTK, int DBG = 0>
-int launch_wide(const int8_t* A, const uint8_t* W, const int8_t* zeros, const int8_t* scales8, const void* wscales,
-                const void* ascales, const void* wszs, const void* assums, void* out, int M, int N, int K, int persist_mode,
-                hipStream_t stream) {
+int launch_wide(const GemmArgs& a, int persist_mode) {
     auto kern = w4a8_gemm_wide<MODE, OUTK, DBG>;
     const size_t smem = (size_t)NS * (BM * 64 + WSTAGE + 512);   // (the epilogue's staging rows alias activation pair slot 2)
     static bool lds_reserved[QS_MAX_DEVICES] = {};   // per instantiation (= kernel) and device
@@ -584,44 +583,32 @@ int launch_wide(const int8_t* A, const uint8_t* W, const int8_t* zeros, const in
         qs_set_error("w4a8 gemm (wide): cannot reserve %zu bytes of LDS: %s", smem, hipGetErrorString(e));
         return (int)e;
     }
-    const int nbm = (M + BM - 1) / BM;
-    const int ntiles = nbm * (N / BN);
+    const int nbm = (a.M + BM - 1) / BM;
+    const int ntiles = nbm * (a.N / BN);
     const int cus = qs_num_cus();
     // persist_mode 0: one workgroup per CU walks the tile list, 1: one per tile, 2: three workgroups walk all tiles (tests of
     // the tile-to-tile hand-over); the int32-output form has no hand-over (one workgroup per tile)
     const int walkers = persist_mode == 2 ? 3 : cus;
     dim3 grid(OUTK != 1 && persist_mode != 1 && ntiles > walkers ? walkers : ntiles);
-    hipLaunchKernelGGL(kern, grid, dim3(256), smem, stream, A, W, zeros, scales8,
-                       reinterpret_cast<const __half*>(wscales), reinterpret_cast<const __half*>(ascales),
-                       reinterpret_cast<const __half*>(wszs), reinterpret_cast<const __half*>(assums), out, M, N, K,
+    hipLaunchKernelGGL(kern, grid, dim3(256), smem, a.stream, a.A, a.W, a.zeros, a.scales8, a.wscales, a.ascales, a.wszs, a.assums,
+                       a.out, a.M, a.N, a.K,
                        nbm, g_wide_order, g_epi_fma, grid.x <= (unsigned)g_gemm_clk_cap ? g_gemm_clk : nullptr);
     return qs_launch_status("w4a8 gemm (wide)");
 }
 
 }  // namespace
 
-// Entry used by the dispatcher in gemm_w4a8.hip.  Preconditions (checked there): N % 256 == 0, K % 128 == 0, K >= 256,
+// Entry used by the dispatcher (gemm_w4a8.h).  Preconditions (gemm_plan.h): N % 256 == 0, K % 128 == 0, K >= 256,
 // M * K and N * K / 2 below 4 GiB.
-int qs_launch_gemm_wide(int mode, int outk, const int8_t* A, const uint8_t* W, const int8_t* zeros,
-                        const int8_t* scales8, const void* wscales, const void* ascales, const void* wszs,
-                        const void* assums, void* out, int M, int N, int K, int persist_mode, hipStream_t stream) {
-#define QS_T(MODEV, OUTV) \
-    return launch_wide<MODEV, OUTV>(A, W, zeros, scales8, wscales, ascales, wszs, assums, out, M, N, K, persist_mode, stream)
+int qs_launch_gemm_wide(int mode, int outk, const GemmArgs& a, int persist_mode) {
 #ifdef QS_TIMING   // timing experiments (results are wrong by design): not in the shipped library
-    if (mode == 0 && outk == 0 && g_wide_dbg) {
-#define QS_D(D) case D: return launch_wide<0, 0, D>(A, W, zeros, scales8, wscales, ascales, wszs, assums, out, M, N, K, persist_mode, stream)
-        switch (g_wide_dbg) {
-            QS_D(1); QS_D(2); QS_D(4); QS_D(8); QS_D(16); QS_D(20); QS_D(6); QS_D(22); QS_D(30);
-        default: break;
-        }
+#define QS_D(D) if (mode == 0 && outk == 0 && g_wide_dbg == D) return launch_wide<0, 0, D>(a, persist_mode);
+    QS_D(1) QS_D(2) QS_D(4) QS_D(8) QS_D(16) QS_D(20) QS_D(6) QS_D(22) QS_D(30)
 #undef QS_D
-    }
 #endif
-    if (mode == 0 && outk == 2) QS_T(0, 2);
-    if (mode == 1 && outk == 2) QS_T(1, 2);
-    if (mode == 0 && outk == 0) QS_T(0, 0);
-    if (mode == 0 && outk == 1) QS_T(0, 1);
-    if (mode == 1 && outk == 0) QS_T(1, 0);
-    QS_T(1, 1);
+#define QS_T(MODEV, OUTV) if (mode == MODEV && outk == OUTV) return launch_wide<MODEV, OUTV>(a, persist_mode);
+    QS_T(0, 2) QS_T(1, 2) QS_T(0, 0) QS_T(0, 1) QS_T(1, 0) QS_T(1, 1)
 #undef QS_T
+    qs_set_error("w4a8 gemm (wide): unsupported mode=%d output kind=%d", mode, outk);
+    return QS_ENOSUP;
 }
