@@ -696,6 +696,49 @@ int qs_history_append(int32_t* history, int64_t hist_stride, int cap, const int3
                       int batch, int n, int max_accept, qs_stream_t stream);
 int qs_ngram_draft_lds_tokens(void);   /* history tokens the drafter stages in LDS (a compile-time constant of the library) */
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Stop conditions (no reference counterpart: its stop checks are host Python).  qs_stop_update clips what one round - a decode step or a
+ * tree verification - is about to emit at the first stop: a stop sequence completed in the generated text, or a length limit reached.
+ * It runs between the walk and the commit, over the walk's own outputs, so that the launches behind it (qs_kv_cache_commit_path_layers,
+ * the advance of the lengths, qs_history_append) commit, count and record the clipped path without knowing of it.  Capturable, nothing
+ * allocated, everything integer: bit-identical run to run and eager against graph replay.
+ *
+ * Per sequence b.  L = min(max(lengths[b], 0), cap): the text length from BEFORE the round advances it; the text is history[b, 0 .. L)
+ * (int32 [batch, cap], row stride hist_stride >= cap) followed by the emitted tokens e_1 .. e_m:
+ *     m   = accept_lens[b] cut to 0 .. min(max_accept, 64); accept_lens null: m = 1; node_tokens or accept_idx null: m is cut to 0 .. 1;
+ *     e_j = node_tokens[b, clamp(accept_idx[b, j], 0, n-1)]  for 1 <= j < m      (node_tokens int64 [batch, n], accept_idx int32 [batch, max_accept]);
+ *     e_m = next_token[b]                                                          (int64 [batch]);
+ * text position L - 1 + j holds e_j, the convention of qs_history_append; index j = 0 stands for the current token at position L - 1.
+ * The token at text position p is history[b, p] for p < L and e_(p-L+1) otherwise; a position p < max(prompt_lens[b], 0) (int32 [batch]
+ * or null = 0) or p >= cap holds NO token: it matches nothing.  Tokens compare as 64-bit integers.
+ *
+ * Stop table: stop_seqs int32 [num_stops, stop_width], stop_lens int32 [num_stops], 0 <= num_stops <= 32, 1 <= stop_width <= 8.  Row s is
+ * stop_seqs[s, 0 .. stop_lens[s]); a row whose length is outside 1 .. stop_width, or that has a negative id in its used part, is off.
+ * limit_lens int32 [batch] or null (no limit): the largest text length, prompt included.  finished int32 [batch], in and out: 0 = live,
+ * 1 = stopped by a stop sequence, 2 = stopped by the length limit.
+ *
+ *     hit(j), 0 <= j <= m:  (a) limit_lens given and L + j >= limit_lens[b],  or
+ *                           (b) j >= (check_root ? 0 : 1) and some row s that is on has, with l = stop_lens[s],
+ *                               token(L - 1 + j - (l-1) + t) == stop_seqs[s, t] for all 0 <= t < l.
+ *     k = the smallest j with hit(j); no hit: k = m and finished[b] stays 0.  On a hit finished[b] = 1 if (b) holds at k, else 2.
+ *     finished[b] != 0 on entry: k = 0 and finished[b] is not written.
+ *
+ * Outputs.  accept_lens[b] = k in place (out_lens[b] = k where accept_lens is null).  next_token[b]: k == m - not written; 1 <= k < m -
+ * e_k; k == 0 < m - history[b, L-1], the frozen token (not written if L == 0).  last_row[b] (int64 [batch] or null) =
+ * b * n + clamp(accept_idx[b, k-1], 0, n-1) for 1 <= k < m, else not written.  Nothing else is written.  check_root = 1 is for the one
+ * launch (with m = 0) that looks at the token a prefill drew.
+ *
+ * QS_EINVAL before any device call: history, lengths, next_token or finished null; accept_lens and out_lens both null; n or max_accept
+ * outside 1 .. 64; num_stops outside 0 .. 32 or stop_width outside 1 .. 8; num_stops > 0 without stop_seqs / stop_lens; node_tokens null
+ * with n > 1; accept_idx null with max_accept > 1; cap < 1; hist_stride < cap; check_root not 0 / 1; batch < 0; an int32 array not 4-byte
+ * or an int64 array not 8-byte aligned.  batch == 0: QS_OK, no launch.  One wave64 per sequence.
+ * ---------------------------------------------------------------------------------------------------------- */
+int qs_stop_update(const int32_t* history, int64_t hist_stride, int cap, const int32_t* lengths, const int32_t* prompt_lens,
+                   const int64_t* node_tokens, const int32_t* accept_idx, int32_t* accept_lens, int32_t* out_lens,
+                   int64_t* next_token, int64_t* last_row, const int32_t* stop_seqs, const int32_t* stop_lens,
+                   const int32_t* limit_lens, int32_t* finished, int batch, int n, int max_accept, int num_stops, int stop_width,
+                   int check_root, qs_stream_t stream);
+
 /* Timing tool (scripts/trace_attn.py): device-to-device copy of the first `bytes` of the split-KV workspace, where the
  * trace instantiation of the KV4 decode attention (qs_set_attention_variant(232)) leaves its s_memtime stamps.
  * (A library built with -DQS_RING_TRACE additionally exports qs_debug_ring_trace(void* buf) for scripts/trace_gemm.py;

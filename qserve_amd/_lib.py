@@ -90,6 +90,7 @@ SIGNATURES = {
     "qs_ngram_draft_tree": (_i, [_vp, _i64, _i, _vp, _vp, _i, _i, _i, _i, _i64, _vp, _vp]),
     "qs_history_append": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "qs_ngram_draft_lds_tokens": (_i, []),
+    "qs_stop_update": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
 }
 
 

@@ -31,6 +31,7 @@ from . import drafting as draftingmod
 from . import fused as fusedmod
 from . import penalties as penaltiesmod
 from . import sampling as samplingmod
+from . import stopping as stoppingmod
 from . import tp as tpmod
 from ._lib import device_status as _device_status
 from .backend._util import check as _check, lib as _lib, stream
@@ -277,6 +278,7 @@ class DecodeEngine:
             self.head_cand_res = self.proj_res.view(-1)[:n].view(tp_world, B, 8)  # the sum over the ranks
         self.graph = None
         self.pieces = None
+        self._graph_stops = False
         # an integer upper bound of `lengths`, kept on the host: set by the prefill entries, + 1 per step() / run(), + n per device-walk
         # verify_tree (which cannot know how many nodes were accepted without reading the device).  A planner hint and the "does it fit
         # the page tables" bound only - no result depends on it.  sync_length_bound() makes it exact again, at the price of one read-back.
@@ -287,14 +289,19 @@ class DecodeEngine:
         # capture_verify / capture_speculate: the graph, the tree's n, the persistent result triple, and every tensor the graph touches
         # that was allocated outside the capture (it stays referenced as long as the graph does); _verify_draft: run_verify's input
         self.verify_graph = self._verify_n = self._verify_result = self._verify_keep = self._verify_draft = None
-        self.speculate_graph = self._speculate_n = self._speculate_result = self._speculate_keep = None
+        self.speculate_graph = self._speculate_n = self._speculate_result = self._speculate_keep = self._speculate_tree = None
         self.sampling = None             # set_sampling: {"seed"} while the head samples; the parameters live in device tensors:
         self._samp_t = self._samp_k = self._samp_p = self._samp_ids = None      # temperature, top-k, top-p per row; arange(B)
         self.penalties = None            # set_penalties: the (repetition, frequency, presence) device tensors while the heads penalise
         self._pen_values = None          # ... and while they do not: the same tensors, created by the first set_penalties
         # enable_drafting: the text of every sequence int32 [B, max_len], where its generated part begins int32 [B], the constants of
         # step()'s history_append, and (max_ngram, min_match, pad_token)
-        self.history = self.prompt_lens = self._step_record = self._draft_params = None
+        self.history = self.prompt_lens = self._step_record = self._draft_params = self._prompt_len = None
+        # set_stopping: True while the stop rule runs behind the heads; its persistent device tensors (created by the first call):
+        # why each sequence ended int32 [B] (stopping.LIVE / STOPPED / LENGTH), the largest text length int32 [B], the stop table, and
+        # the per-step k of step()
+        self.stopping = None
+        self.finished = self.limit_lens = self._stop_seqs = self._stop_lens = self._stop_k = None
 
     def _single_gpu(self, what):
         """What every entry behind the un-cut fp16 lm_head asks for (sampling, penalties, shared prefixes, tree verification, drafting):
@@ -483,6 +490,9 @@ class DecodeEngine:
         assert self.penalties is None, \
             f"{what}: the prefill head does not penalise (the history of the new prompt does not exist yet) - set_penalties(None), " \
             "prefill, enable_drafting, then set_penalties again"
+        assert self.stopping is None, \
+            f"{what}: the stop rule reads the history of the prompt it was switched on for - set_stopping(None), prefill, " \
+            "enable_drafting, then set_stopping again"
 
     def _prompt_head(self, last_rows, prompt_len):
         """Last-token states -> `hidden`, first sampled token -> `tokens`, lengths = prompt_len + 1."""
@@ -650,6 +660,7 @@ class DecodeEngine:
         if device_walk:
             return self._verify_tree_device(draft_tokens, par, sampled=sampled)
         assert self.penalties is None, "verify_tree: penalties (set_penalties) need device_walk=True - the host walk does not penalise"
+        assert self.stopping is None, "verify_tree: stopping (set_stopping) needs device_walk=True - the host walk does not clip its path"
         max_past = int(self.lengths.max()) - 1
         assert max_past + n <= self.mb * 64, "verify_tree: the tree does not fit the sequences' page tables"
         _, toks, past, h, final, logits, am = self._verify_forward(draft_tokens, par, max_past, sampled)
@@ -747,6 +758,8 @@ class DecodeEngine:
         hint = self._len_bound - 1 if max_past is None else int(max_past)
         c, toks, past, h, final, logits, am = self._verify_forward(draft_tokens, par, hint, sampled)
         accept_idx, accept_lens, last, nxt = appendmod.accept_greedy(toks.view(-1), am, c["parents"], c["cu"], max_accept=n, out=out)
+        if self.stopping is not None:                                       # clip the path at the first stop; a finished row accepts nothing
+            self._stop_update(nxt, node_tokens=toks, accept_idx=accept_idx, accept_lens=accept_lens, last_row=last)
         appendmod.commit_path_layers(c["layer_tables"], past, accept_idx, accept_lens, self.mb, self.Hkv, self.size_per_token, self.int4)
         self.hidden.copy_(torch.index_select(h, 0, last))
         self.final.copy_(torch.index_select(final, 0, last))
@@ -778,7 +791,7 @@ class DecodeEngine:
         g, res = self._capture(lambda: self._verify_tree_device(self._verify_draft, par, max_past=hint, out=out, sampled=sampled), n)
         # every tensor the graph touches and that was allocated outside the capture stays referenced as long as the graph does: the
         # four outputs of the walk (two of them are not part of the result) and the tree's constants (the cache may evict them)
-        self._verify_keep = (out, self._tree_constants(par), self.penalties, self.prompt_lens)
+        self._verify_keep = (out, self._tree_constants(par), self.penalties, self.prompt_lens, self._stop_tensors())
         self.verify_graph, self._verify_n, self._verify_result = g, n, res
         return g
 
@@ -828,6 +841,7 @@ class DecodeEngine:
             self.prompt_lens = torch.zeros((B,), dtype=torch.int32, device=dev)   # P: where the generated text begins (set_penalties)
         self.history.zero_()
         self.prompt_lens.fill_(P)
+        self._prompt_len = P                                                  # (the same value on the host, for set_stopping's limits)
         self.history[:, :P] = prompt
         self.history[:, P] = self.tokens
         self._draft_params = (int(max_ngram), int(min_match), int(pad_token))
@@ -866,12 +880,113 @@ class DecodeEngine:
         rep, freq, pres = self.penalties
         penaltiesmod.penalize_rows(logits, self.history, self.lengths, self.prompt_lens, node_tokens, tree, rep, freq, pres)
 
-    def _record_step(self):
+    # ---- stop conditions (qserve_amd.stopping, csrc/stop_update.hip) -----------------------------------------------------------
+    def set_stopping(self, stop=(), max_new_tokens=None):
+        """End sequences on the device (after enable_drafting: the rule reads `history` and `prompt_lens`): one `stopping.stop_update`
+        launch behind the head of step() (hence capture() / run()) and between the walk and the commit of verify_tree(device_walk=True)
+        (hence capture_verify, speculate, capture_speculate).  `stop`: token ids and / or sequences of ids (at most 32 of at most 8 tokens);
+        a sequence ends with the token that completes one of them INSIDE its generated text (a match may not begin in the prompt).
+        `max_new_tokens`: an int, or one per sequence - a sequence ends when its text holds prompt + max_new_tokens tokens; None: the
+        history's capacity (prompt_len + max_new of the engine), which an explicit value must not exceed.  A round's path is clipped at
+        the first stop, so a sequence's text is the text of an engine without stopping, cut there - and nothing of another sequence changes.
+        `finished` int32 [B] holds why: 0 live, 1 a stop sequence, 2 the length.
+
+        A finished sequence is FROZEN, inside the fixed batch: its `tokens`, `lengths` and `history[b, :lengths[b]]` never change again;
+        its page slots < lengths[b] keep their bytes (a frozen step() rewrites slot lengths[b] - 1 with the same token at the same
+        position, a frozen verification parks its nodes in slots >= lengths[b] - 1 and commits none); its rows of `hidden` and `final`
+        are unspecified.  Its row still runs through every GEMM - the batch is fixed under a graph and is not compacted.
+
+        Table, limits and `finished` live in persistent device tensors that are filled in place: a captured graph sees a later
+        set_stopping(...) with new values; whether the launch exists at all is frozen into a capture - capture after switching.  The
+        call clears `finished` and looks at the current token once (the token a prefill head drew): a sequence whose first token is
+        already a stop, or that is already at its limit, is finished at once.  set_stopping(None) switches it off: every path launches
+        exactly what it launches without this call.  The prefill entries and the host-walk verify_tree(device_walk=False) refuse to run
+        while it is on.  Single GPU, with the lm_head."""
+        if stop is None:
+            self.stopping = None
+            return
+        self._single_gpu("set_stopping")
+        assert self.history is not None, "set_stopping: enable_drafting first (the stop rule reads `history`)"
+        B, dev, cap = self.B, self.dev, self.history.size(1)
+        seqs, lens = stoppingmod.stop_table(stop, num_rows=stoppingmod.MAX_STOPS, width=stoppingmod.MAX_STOP_LEN)
+        if max_new_tokens is None:
+            limits = [cap] * B
+        else:
+            new = [int(max_new_tokens)] * B if isinstance(max_new_tokens, int) else [int(v) for v in max_new_tokens]
+            assert len(new) == B and min(new) >= 0, f"set_stopping: max_new_tokens is one non-negative int, or one per sequence ({B})"
+            limits = [self._prompt_len + v for v in new]
+            assert max(limits) <= cap, \
+                f"set_stopping: prompt {self._prompt_len} + max_new_tokens {max(new)} is beyond the history's capacity {cap}"
+        if self.finished is None:
+            self.finished = torch.zeros((B,), dtype=torch.int32, device=dev)
+            self.limit_lens = torch.zeros((B,), dtype=torch.int32, device=dev)
+            self._stop_seqs, self._stop_lens = torch.empty_like(seqs, device=dev), torch.empty_like(lens, device=dev)
+            self._stop_k = torch.zeros((B,), dtype=torch.int32, device=dev)
+        self._stop_seqs.copy_(seqs)
+        self._stop_lens.copy_(lens)
+        self.limit_lens.copy_(torch.tensor(limits, dtype=torch.int32))
+        self.finished.zero_()
+        self.stopping = True
+        self._stop_k.zero_()                                                # m = 0: nothing is emitted, the current token is looked at
+        self._stop_update(self.tokens, accept_lens=self._stop_k, check_root=True)
+
+    def _stop_tensors(self):
+        """What a captured graph with the stop launch reads (None while stopping is off)."""
+        return None if self.stopping is None else (self.finished, self.limit_lens, self._stop_seqs, self._stop_lens, self._stop_k)
+
+    def _stop_update(self, next_token, **path):
+        """The launch of set_stopping's rule on what a round is about to emit, from `history` and the lengths as they stand (not yet
+        advanced) -> k int32 [B]."""
+        return stoppingmod.stop_update(self.history, self.lengths, next_token, self.finished, self._stop_seqs, self._stop_lens, self.limit_lens,
+                                       self.prompt_lens, **path)
+
+    def generate(self, max_rounds, parents=None, poll_every=8, sampled=False):
+        """Decode until every sequence has finished (after set_stopping), with the host looking at the device once per burst: replay
+        the captured step graph - or, with `parents`, the captured speculate graph of that tree - `poll_every` times, then read
+        (`finished`, `lengths`) back in one copy; that is the only host <-> device traffic of the loop.  `_len_bound` is set from it.
+        Ends when no sequence is live, when `max_rounds` rounds are done, or when another round would not fit the page tables by the
+        bound (a burst is shortened to what fits).  A graph that does not exist yet, or that was captured without the stop launch (for
+        speculation also: of another tree or head), is captured first - the warm-up of capture() / capture_speculate() is a real round
+        that is not counted.
+        -> (texts: per sequence the list of generated tokens history[b, prompt_lens[b] : lengths[b]], the first token of the prefill
+        included; reasons: `finished` as a list; rounds; read_backs) - the texts are read once, after the loop."""
+        assert self.stopping is not None, "generate: set_stopping first (nothing else ends the loop)"
+        assert max_rounds >= 0 and poll_every >= 1
+        if parents is None:
+            if self.graph is None or not self._graph_stops:
+                self.capture(piecewise=False)
+            advance, run = 1, self.run
+        else:
+            par = self._tree_arg(parents, "generate")
+            if self.speculate_graph is None or self._speculate_tree != (tuple(par), bool(sampled), True):
+                self.capture_speculate(par, sampled=sampled)
+            advance, run = len(par), self.run_speculate
+        rounds = reads = 0
+        while rounds < max_rounds:
+            # a round writes slots up to _len_bound - 1 + advance - 1: how many rounds fit the page tables by the bound
+            fit = (self.mb * 64 - (self._len_bound - 1)) // advance
+            burst = min(poll_every, max_rounds - rounds, fit)
+            if burst < 1:
+                break
+            for _ in range(burst):
+                run()
+            rounds += burst
+            state = torch.stack((self.finished, self.lengths)).cpu()         # the one read-back of the burst
+            reads += 1
+            self._len_bound = int(state[1].max())
+            if bool((state[0] != 0).all()):
+                break
+        hist, lens, fin = self.history.cpu(), self.lengths.cpu().tolist(), self.finished.cpu().tolist()
+        texts = [hist[b, self._prompt_len:lens[b]].tolist() for b in range(self.B)]
+        return texts, fin, rounds, reads
+
+    def _record_step(self, emitted=None):
         """history[b, lengths[b] - 1] = tokens[b], after step() advanced the lengths: history_append with a path of the root alone at
-        past = lengths - 2 (its bonus token lands at past + 1).  A sequence that has outgrown `history` records nothing."""
+        past = lengths - 2 (its bonus token lands at past + 1).  A sequence that has outgrown `history` records nothing.  `emitted`:
+        the k of set_stopping's rule (int32 [B], 0 / 1) in place of the constant ones - a sequence that emitted nothing records nothing."""
         nodes, idx, ones, past = self._step_record
         torch.sub(self.lengths, 2, out=past)
-        draftingmod.history_append(self.history, past, nodes, idx, ones, self.tokens)
+        draftingmod.history_append(self.history, past, nodes, idx, ones if emitted is None else emitted, self.tokens)
 
     def _tree_arg(self, parents, what, drafting=True):
         """`parents` of the entry `what` as a list, checked: a tree, on a single GPU, `drafting`: with a history to draft from."""
@@ -922,8 +1037,11 @@ class DecodeEngine:
         g, res = self._capture(lambda: self._speculate(par, max_past=hint, out=out, draft=draft, sampled=sampled), n)
         # every tensor the graph touches and that was allocated outside the capture stays referenced as long as the graph does: the
         # draft buffer, the four outputs of the walk, the tree's constants (the cache may evict them), step()'s record constants
-        self._speculate_keep = (draft, out, self._tree_constants(par), self._step_record, self.history, self.penalties, self.prompt_lens)
+        self._speculate_keep = (draft, out, self._tree_constants(par), self._step_record, self.history, self.penalties, self.prompt_lens,
+                                self._stop_tensors())
         self.speculate_graph, self._speculate_n, self._speculate_result = g, n, res
+        # (generate: is the captured round the one it was asked for - this tree, this head, the stop launch in it?)
+        self._speculate_tree = (tuple(par), bool(sampled), self.stopping is not None)
         return g
 
     def run_speculate(self):
@@ -953,6 +1071,11 @@ class DecodeEngine:
             self._head_finish(self.head_cand_res)
         elif self.with_lm_head:                                      # (penalty context: history[b, :lengths[b]], the text so far)
             self._head(self.final, self.tokens, self._step_keys if self.sampling is not None else None)
+        if self.stopping is not None:                                # set_stopping: k = 0 (a stop before the new token, or a frozen row) / 1
+            k = self._stop_update(self.tokens, out_lens=self._stop_k)
+            self.lengths.add_(k)
+            self._record_step(k)
+            return
         self.lengths.add_(1)
         if self.history is not None:                                 # enable_drafting: the new token joins the text
             self._record_step()
@@ -1039,6 +1162,7 @@ class DecodeEngine:
         self.pieces = None
         if not piecewise:
             self.graph, _ = self._capture(self.step, 1)
+            self._graph_stops = self.stopping is not None    # (generate: does the captured step hold the stop launch?)
             return self.graph
         self._warm_up(self.step)
         pool = torch.cuda.graph_pool_handle()
