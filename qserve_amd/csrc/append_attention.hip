@@ -75,9 +75,15 @@ extern "C" int qs_append_attention_plan(int batch, int max_seqlen_q, int num_hea
         return QS_ENOSUP;
     }
     if (batch == 0 || max_seqlen_q == 0) return QS_OK;
-    const AppendPlan p = plan_append(max_seqlen_q, num_heads, num_kv_heads);
+    const AppendPlan p = attn_plan::plan_append(max_seqlen_q, num_heads, num_kv_heads);
     plan3[0] = p.tile_tokens, plan3[1] = p.q_tiles, plan3[2] = p.waves;
     return QS_OK;
+}
+
+int qs_append_launch(const AppendArgs& a, const AppendPlan& p) {
+    return launch_kernel_pair<append_attention_kernel<true>, append_attention_kernel<false>>(
+        "append_attention", "append_attention", a.int4, dim3(a.num_kv_heads, p.q_tiles, a.batch), dim3(64 * p.waves), a.stream, a.qkv, a.out,
+        a.cu_seqlens_q, a.past_lens, a.kv_pointers, a.num_heads, a.num_kv_heads, a.max_blocks, p.tile_tokens, a.qkv_stride0, a.out_stride0);
 }
 
 extern "C" int qs_append_attention(const void* qkv, void* out, const int32_t* cu_seqlens_q, const int32_t* past_lens,
@@ -85,30 +91,13 @@ extern "C" int qs_append_attention(const void* qkv, void* out, const int32_t* cu
                                    int num_heads, int num_kv_heads, int head_dim, int64_t qkv_stride0, int64_t out_stride0,
                                    int tokens_per_block, int size_per_token, int int4_kv_cache, int kv_cache_with_zeros,
                                    qs_stream_t stream) {
+    AppendArgs a;
     if (const int bad = check_append_args(qkv, out, cu_seqlens_q, past_lens, kv_pointers, num_tokens, batch, max_seqlen_q, max_blocks, num_heads,
                                           num_kv_heads, head_dim, qkv_stride0, out_stride0, tokens_per_block, size_per_token, int4_kv_cache,
-                                          kv_cache_with_zeros); bad != QS_OK)
+                                          kv_cache_with_zeros, stream, &a); bad != QS_OK)
         return bad;
     int plan3[3];
     const int rc = qs_append_attention_plan(batch, max_seqlen_q, num_heads, num_kv_heads, plan3);
-    if (rc != QS_OK) return rc;
-    if (batch == 0 || max_seqlen_q == 0 || num_tokens == 0) return QS_OK;
-    constexpr int SMEM = 2 * KS_BYTES + 2 * VT_BYTES;
-    static bool lds_reserved[QS_MAX_DEVICES] = {};
-    if (const hipError_t e = qs_reserve_lds({reinterpret_cast<const void*>(append_attention_kernel<true>), reinterpret_cast<const void*>(append_attention_kernel<false>)},
-                                            SMEM, lds_reserved); e != hipSuccess) {
-        qs_set_error("append_attention: cannot reserve %d bytes of LDS", SMEM);
-        return (int)e;
-    }
-    const float scale_log2 = 0.08838834764831845f * 1.4426950408889634f;   // 1/sqrt(128) * log2(e)
-    const dim3 grid(num_kv_heads, plan3[1], batch), block(64 * plan3[2]);
-    if (int4_kv_cache)
-        hipLaunchKernelGGL(append_attention_kernel<true>, grid, block, SMEM, (hipStream_t)stream, (const _Float16*)qkv, (_Float16*)out,
-                           cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, max_blocks, plan3[0], qkv_stride0,
-                           out_stride0, scale_log2);
-    else
-        hipLaunchKernelGGL(append_attention_kernel<false>, grid, block, SMEM, (hipStream_t)stream, (const _Float16*)qkv, (_Float16*)out,
-                           cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, max_blocks, plan3[0], qkv_stride0,
-                           out_stride0, scale_log2);
-    return qs_launch_status("append_attention");
+    if (rc != QS_OK || a.empty()) return rc;
+    return qs_append_launch(a, {plan3[0], plan3[1], plan3[2]});
 }

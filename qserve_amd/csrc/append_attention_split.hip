@@ -30,39 +30,10 @@
 // allocated on the first eager use, never during a capture); without it - or with one split - the entry runs the un-split launcher.
 #include "append_walk.h"
 
-float* qs_split_workspace(size_t bytes, hipStream_t st);     // attention_mfma.hip
-size_t qs_split_workspace_capacity();
-
 namespace {
 
 using namespace qs_flash;
 using namespace qs_append;      // REC_FLOATS, MAX_SPLITS, the walk and the record's store: append_walk.h
-
-// ---- the planner's rule (pure; qs_append_attention_split_plan) -------------------------------------------------------------
-// "Fill the CUs once" (the decode chooser's form): the un-split grid has base = batch * Hkv * q_tiles workgroups and the
-// chip holds FILL of them at a time (256 CUs x two 64 KiB workgroups); below that, split until the chip is full, but never below
-// MIN_PAGES pages per split (a split pays its own Q load, pipeline fill, 65 KiB of partial records and its share of the merge) and
-// never for a past of fewer than 128 tokens.
-// Fitted to scripts/bench_append_split.py -> profiles/append_split.txt (MI355X, Llama-3-8B heads):
-//   FILL = 512       B = 8, past 4096, n = 4 (base 64): 4 splits 44 us, 7 splits (what the workspace holds of 512 / 64 = 8) 40 us -
-//                    filling both workgroup slots of every CU still pays; no correction to the starting form.
-//   MIN_PAGES = 8    B = 1, past 8192, n = 8: 16 splits (8 pages each) 33.6 us KV4 / 35.1 us KV8, 32 splits (4 pages each) 34.0 /
-//                    37.8 us - below 8 pages per split the merge and the per-split set-up cost what the shorter chain saves.
-//                    At short pasts it is too high (B = 1, n = 8, past 1024: 2 splits 25.9 us, 8 splits 18.0 us; past 2048: 4 splits
-//                    26.8 us, 8 splits 21.6 us - still ahead of un-split, 37.0 / 65.2 us): the regret is in the profile and DESIGN 10.
-constexpr int FILL = 512;
-constexpr int MIN_PAGES = 8;
-int plan_splits(int batch, int q_tiles, int num_kv_heads, int max_past) {
-    const long base = (long)batch * num_kv_heads * q_tiles;
-    if (base <= 0 || base >= FILL || max_past < 2 * BN) return 1;
-    const int pages = (max_past + BN - 1) / BN;
-    long s = FILL / base;
-    if (s > pages / MIN_PAGES) s = pages / MIN_PAGES;
-    const long cap = (long)(qs_split_workspace_capacity() / ((size_t)base * NWV * REC_FLOATS * sizeof(float)));
-    if (s > cap) s = cap;
-    if (s > MAX_SPLITS) s = MAX_SPLITS;
-    return s < 1 ? 1 : (int)s;
-}
 
 template <bool INT4>
 __global__ __launch_bounds__(64 * NWV, 2) void append_attention_split_kernel(const _Float16* __restrict__ qkv, float* __restrict__ ws,
@@ -151,23 +122,28 @@ __global__ __launch_bounds__(256) void append_attention_merge_kernel(const float
 
 }  // namespace
 
-// What every split-KV append launcher needs besides its own kernel (declared in append_walk.h; append_tree.hip is the other user).
-// qs_append_split_resolve: the effective split count for a wanted one - at most 64 and what the workspace holds - and the workspace
-// for it; 1 and *ws = nullptr where the call has to run un-split (one split, or no workspace: its first use inside a capture).
-int qs_append_split_resolve(int wanted, int batch, int num_kv_heads, int q_tiles, hipStream_t stream, float** ws) {
-    int splits = wanted;
-    const size_t per_split = (size_t)batch * num_kv_heads * q_tiles * NWV * REC_FLOATS * sizeof(float);
-    if (splits > MAX_SPLITS) splits = MAX_SPLITS;
-    if (per_split * splits > qs_split_workspace_capacity()) splits = (int)(qs_split_workspace_capacity() / per_split);
-    *ws = splits > 1 ? qs_split_workspace(per_split * splits, stream) : nullptr;
+// What every split-KV append launcher needs besides its own kernel (attn_host.h; append_tree.hip is the other user).
+int qs_append_split_resolve(int wanted, const AppendArgs& a, const AppendPlan& p, float** ws) {
+    const size_t per_split = attn_plan::append_split_bytes((size_t)a.batch * a.num_kv_heads * p.q_tiles);
+    const int splits = attn_plan::fit_splits(wanted, per_split, qs_split_workspace_capacity(), MAX_SPLITS);
+    *ws = splits > 1 ? qs_split_workspace(per_split * splits, a.stream) : nullptr;
     return *ws ? splits : 1;
 }
-// qs_append_merge_launch: the merge of the partial records (mask-agnostic: it sees maxima, sums and O only).
-int qs_append_merge_launch(const float* ws, void* out, const int32_t* cu_seqlens_q, const int32_t* past_lens, int batch, int num_heads,
-                           int num_kv_heads, int max_blocks, int tq, int q_tiles, int splits, int64_t out_stride0, hipStream_t stream) {
-    hipLaunchKernelGGL(append_attention_merge_kernel, dim3(num_kv_heads, q_tiles * NWV, batch), dim3(256), 0, stream, ws, (_Float16*)out,
-                       cu_seqlens_q, past_lens, num_heads, num_kv_heads, max_blocks, tq, q_tiles, splits, out_stride0);
+int qs_append_merge_launch(const float* ws, const AppendArgs& a, const AppendPlan& p, int splits) {
+    hipLaunchKernelGGL(append_attention_merge_kernel, dim3(a.num_kv_heads, p.q_tiles * NWV, a.batch), dim3(256), 0, a.stream, ws, a.out,
+                       a.cu_seqlens_q, a.past_lens, a.num_heads, a.num_kv_heads, a.max_blocks, p.tile_tokens, p.q_tiles, splits, a.out_stride0);
     return qs_launch_status("append_attention_merge");
+}
+
+int qs_append_split_launch(const AppendArgs& a, const AppendPlan& p, int wanted_splits) {
+    float* ws = nullptr;
+    const int splits = qs_append_split_resolve(wanted_splits, a, p, &ws);
+    if (!ws) return qs_append_launch(a, p);      // one split, or no workspace (first use inside a capture): bit for bit qs_append_attention
+    const int lrc = launch_kernel_pair<append_attention_split_kernel<true>, append_attention_split_kernel<false>>(
+        "append_attention_split", "append_attention_split", a.int4, dim3(a.num_kv_heads, p.q_tiles * splits, a.batch), dim3(64 * p.waves), a.stream,
+        a.qkv, ws, a.cu_seqlens_q, a.past_lens, a.kv_pointers, a.num_heads, a.num_kv_heads, a.max_blocks, p.tile_tokens, p.q_tiles, splits,
+        a.qkv_stride0);
+    return lrc != QS_OK ? lrc : qs_append_merge_launch(ws, a, p, splits);
 }
 
 extern "C" int qs_append_attention_split_plan(int batch, int max_seqlen_q, int max_past, int num_heads, int num_kv_heads,
@@ -178,10 +154,10 @@ extern "C" int qs_append_attention_split_plan(int batch, int max_seqlen_q, int m
     const int rc = qs_append_attention_plan(batch, max_seqlen_q, num_heads, num_kv_heads, plan5);   // (checks the rest, fills 0 .. 2)
     if (rc != QS_OK || plan5[1] == 0) return rc;
     (void)int4_kv_cache;                                 // both cache types walk 64-token pages: one rule
-    const int splits = plan_splits(batch, plan5[1], num_kv_heads, max_past);
+    const int splits = attn_plan::plan_splits(batch, plan5[1], num_kv_heads, max_past, qs_split_workspace_capacity());
     plan5[3] = splits;
     // KiB of partial records (a record block is 16 640 B, four per workgroup: 65 KiB); 0 for the un-split launch, which has none
-    plan5[4] = splits > 1 ? (int)((size_t)batch * num_kv_heads * plan5[1] * splits * (NWV * REC_FLOATS * sizeof(float) / 1024)) : 0;
+    plan5[4] = splits > 1 ? (int)(attn_plan::append_split_bytes((size_t)batch * num_kv_heads * plan5[1]) * splits / 1024) : 0;
     return QS_OK;
 }
 
@@ -190,40 +166,14 @@ extern "C" int qs_append_attention_split(const void* qkv, void* out, const int32
                                          int num_heads, int num_kv_heads, int head_dim, int64_t qkv_stride0, int64_t out_stride0,
                                          int tokens_per_block, int size_per_token, int int4_kv_cache, int kv_cache_with_zeros,
                                          int max_past, int num_splits, qs_stream_t stream) {
+    AppendArgs a;
     if (const int bad = check_append_args(qkv, out, cu_seqlens_q, past_lens, kv_pointers, num_tokens, batch, max_seqlen_q, max_blocks, num_heads,
                                           num_kv_heads, head_dim, qkv_stride0, out_stride0, tokens_per_block, size_per_token, int4_kv_cache,
-                                          kv_cache_with_zeros); bad != QS_OK)
+                                          kv_cache_with_zeros, stream, &a); bad != QS_OK)
         return bad;
     QS_REQUIRE(num_splits >= 0, "append_attention_split: num_splits=%d (0 = ask the planner, >= 1 = forced)", num_splits);
     int plan5[5];
-    const int hint = max_past < 0 || max_past > max_blocks * BN ? max_blocks * BN : max_past;   // (a past is cut to the table anyway)
-    const int rc = qs_append_attention_split_plan(batch, max_seqlen_q, hint, num_heads, num_kv_heads, int4_kv_cache, plan5);
-    if (rc != QS_OK) return rc;
-    if (batch == 0 || max_seqlen_q == 0 || num_tokens == 0) return QS_OK;
-    float* ws = nullptr;
-    const int splits = qs_append_split_resolve(num_splits > 0 ? num_splits : plan5[3], batch, num_kv_heads, plan5[1], (hipStream_t)stream, &ws);
-    if (!ws)      // one split, or no workspace (first use inside a capture): the un-split launch, bit for bit qs_append_attention
-        return qs_append_attention(qkv, out, cu_seqlens_q, past_lens, kv_pointers, num_tokens, batch, max_seqlen_q, max_blocks, num_heads,
-                                   num_kv_heads, head_dim, qkv_stride0, out_stride0, tokens_per_block, size_per_token, int4_kv_cache,
-                                   kv_cache_with_zeros, stream);
-    constexpr int SMEM = 2 * KS_BYTES + 2 * VT_BYTES;
-    static bool lds_reserved[QS_MAX_DEVICES] = {};
-    if (const hipError_t e = qs_reserve_lds({reinterpret_cast<const void*>(append_attention_split_kernel<true>),
-                                             reinterpret_cast<const void*>(append_attention_split_kernel<false>)},
-                                            SMEM, lds_reserved); e != hipSuccess) {
-        qs_set_error("append_attention_split: cannot reserve %d bytes of LDS", SMEM);
-        return (int)e;
-    }
-    const float scale_log2 = 0.08838834764831845f * 1.4426950408889634f;   // 1/sqrt(128) * log2(e)
-    const int tq = plan5[0], q_tiles = plan5[1];
-    const dim3 grid(num_kv_heads, q_tiles * splits, batch), block(64 * plan5[2]);
-    if (int4_kv_cache)
-        hipLaunchKernelGGL(append_attention_split_kernel<true>, grid, block, SMEM, (hipStream_t)stream, (const _Float16*)qkv, ws, cu_seqlens_q,
-                           past_lens, kv_pointers, num_heads, num_kv_heads, max_blocks, tq, q_tiles, splits, qkv_stride0, scale_log2);
-    else
-        hipLaunchKernelGGL(append_attention_split_kernel<false>, grid, block, SMEM, (hipStream_t)stream, (const _Float16*)qkv, ws, cu_seqlens_q,
-                           past_lens, kv_pointers, num_heads, num_kv_heads, max_blocks, tq, q_tiles, splits, qkv_stride0, scale_log2);
-    if (const int lrc = qs_launch_status("append_attention_split"); lrc != QS_OK) return lrc;
-    return qs_append_merge_launch(ws, out, cu_seqlens_q, past_lens, batch, num_heads, num_kv_heads, max_blocks, tq, q_tiles, splits, out_stride0,
-                                  (hipStream_t)stream);
+    const int rc = qs_append_attention_split_plan(batch, max_seqlen_q, table_hint(max_past, max_blocks), num_heads, num_kv_heads, int4_kv_cache, plan5);
+    if (rc != QS_OK || a.empty()) return rc;
+    return qs_append_split_launch(a, {plan5[0], plan5[1], plan5[2]}, num_splits > 0 ? num_splits : plan5[3]);
 }

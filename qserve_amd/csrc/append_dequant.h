@@ -1,7 +1,7 @@
 // append_dequant.h -- the leaves the append attention kernels (append_attention.hip, append_attention_split.hip, append_tree.hip)
-// share: the exact KV4 / KV8 -> fp16 de-quantisation of 8 consecutive dims of a cached token (the decode kernels' values), the scalar
-// form of a page address for the LDS-DMA's base operand, the launch geometry and the argument checks.  The page staging and the key
-// loop built from these leaves are append_walk.h.
+// share: the exact KV4 / KV8 -> fp16 de-quantisation of 8 consecutive dims of a cached token (the decode kernels' values) and the
+// scalar form of a page address for the LDS-DMA's base operand.  The page staging and the key loop built from these leaves are
+// append_walk.h; the launch geometry is attn_plan.h's, the argument checks attn_host.h's.
 #pragma once
 #include "flash_tile.h"
 
@@ -54,43 +54,6 @@ __device__ __forceinline__ h8 dequant8(u32 w0, u32 w1, _Float16 sc, _Float16 zr)
         o[4 + j] = (_Float16)(scf * ((float)((w1 >> (8 * j)) & 0xFFu) - zrf));
     }
     return o;
-}
-
-// Geometry of a launch - the ONE statement of it (the plan entries and the launchers all ask here).
-struct AppendPlan {
-    int tile_tokens, q_tiles, waves;
-};
-inline AppendPlan plan_append(int max_seqlen_q, int num_heads, int num_kv_heads) {
-    const int G = num_heads / num_kv_heads;
-    AppendPlan p;
-    p.waves = NWV;
-    p.tile_tokens = BM / G;          // rows = (token, head-in-group): every head of the group rides on the same staged tiles
-    p.q_tiles = (max_seqlen_q + p.tile_tokens - 1) / p.tile_tokens;
-    return p;
-}
-
-// The layout contract of the attention entries (include/qserve_amd.h), checked before any device call - the ONE statement of it
-// (qs_append_attention and qs_append_attention_split both ask here; the group size is checked by the plan entries).
-inline int check_append_args(const void* qkv, const void* out, const int32_t* cu_seqlens_q, const int32_t* past_lens,
-                             const int64_t* kv_pointers, int num_tokens, int batch, int max_seqlen_q, int max_blocks, int num_heads,
-                             int num_kv_heads, int head_dim, int64_t qkv_stride0, int64_t out_stride0, int tokens_per_block,
-                             int size_per_token, int int4_kv_cache, int kv_cache_with_zeros) {
-    QS_REQUIRE(qkv && out && cu_seqlens_q && past_lens && kv_pointers, "append_attention: null pointer");
-    QS_REQUIRE(num_tokens >= 0 && batch >= 0 && max_seqlen_q >= 0 && max_blocks > 0, "append_attention: bad sizes");
-    QS_REQUIRE(num_heads > 0 && num_kv_heads > 0 && num_heads % num_kv_heads == 0,
-               "append_attention: bad head counts H=%d Hkv=%d", num_heads, num_kv_heads);
-    if (head_dim != DH || tokens_per_block != BN || !kv_cache_with_zeros) {
-        qs_set_error("append_attention: only head_dim=128, tokens_per_block=64 and zero-point KV caches are supported");
-        return QS_ENOSUP;
-    }
-    QS_REQUIRE(size_per_token == num_kv_heads * (int4_kv_cache ? DH / 2 : DH), "append_attention: size_per_token=%d, expected %d",
-               size_per_token, num_kv_heads * (int4_kv_cache ? DH / 2 : DH));
-    QS_REQUIRE(qkv_stride0 >= (int64_t)(num_heads + 2 * num_kv_heads) * DH && qkv_stride0 % 8 == 0 && qkv_stride0 < (1 << 24) &&
-                   out_stride0 >= (int64_t)num_heads * DH && out_stride0 % 8 == 0,
-               "append_attention: token strides must hold a row and keep 16-byte alignment");
-    QS_REQUIRE((reinterpret_cast<uintptr_t>(qkv) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0,
-               "append_attention: qkv and out must be 16-byte aligned");
-    return QS_OK;
 }
 
 }  // namespace qs_append

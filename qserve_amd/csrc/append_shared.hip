@@ -27,80 +27,12 @@
 // split entry's constant 4, B = 64 x 8 KV heads would need 33 MB for ONE set of suffix records, more than the 32 MiB workspace.
 #include "append_walk.h"
 
-float* qs_split_workspace(size_t bytes, hipStream_t st);     // attention_mfma.hip
-size_t qs_split_workspace_capacity();
-
 namespace {
 
 using namespace qs_flash;
 using namespace qs_append;
 
-// ---- the planner's rule (pure; qs_append_shared_plan) -----------------------------------------------------------------------
-// The split planner's form (append_attention_split.hip: "fill the CUs once", the chip holds FILL = 512 workgroups) with the two roles'
-// base grids counted TOGETHER - they share the launch.  Their chains differ by an order of magnitude (B = 64, prefix 1 024, own past
-// 64: 64 prefix workgroups of 16 pages next to 512 suffix workgroups of 2 tiles), so a workgroup counts with its chain length: the
-// launch holds  tiles = base_prefix * prefix pages + base_suffix * (suffix pages + 1)  tile walks, a slot of the chip gets tiles / FILL
-// of them, and a role with `pages` pages is cut into  pages / (tiles / FILL)  ranges.  With one role this is the split planner's
-// FILL / base; counting the workgroups unweighted would give FILL / 576 = 0 -> P = 1 at the shape above, one serial walk of 16 pages.
-// Then: never below a minimum of pages per split and role, at most 64 splits, and cut to what the workspace holds (the suffix role
-// keeps one set of records; the prefix role gives way first, down to P = 0 = "do not share").
-//   MIN_PAGES_SUFFIX = 8   the split planner's constant (the suffix role IS its workgroup).
-//   MIN_PAGES_PREFIX = 2   the prefix role's own; the STARTING value - the sweep of scripts/bench_append_shared.py that is to fix it (lowest
-//                          worst regret over its table) has not been run on an MI355X yet: not measured.
-constexpr int FILL = 512;
-constexpr int MIN_PAGES_SUFFIX = 8;
-constexpr int MIN_PAGES_PREFIX = 2;
-
-struct SharedPlan {
-    int tq, q_tiles, waves, S, gq_tiles, P, rw_suffix, rw_prefix;
-    size_t bytes;
-};
-inline int rec_waves(int tq, int max_tokens, int G) {
-    const int rows = (max_tokens < tq ? max_tokens : tq) * G;
-    const int w = (rows + 31) / 32;
-    return w < 1 ? 1 : w > NWV ? NWV : w;
-}
-constexpr size_t REC_BYTES = REC_FLOATS * sizeof(float);
-// bytes of one set (one split) of a role's records
-inline size_t set_bytes(long wgs, int rw) { return (size_t)wgs * rw * REC_BYTES; }
-// cut (P, S) to the workspace: S first gives way down to 1, then P down to 0
-inline void fit_workspace(int& P, int& S, size_t per_p, size_t per_s) {
-    const size_t cap = qs_split_workspace_capacity();
-    if (per_s > cap) {      // not even one set of suffix records
-        P = 0;
-        return;
-    }
-    if (P > (int)((cap - per_s) / per_p)) P = (int)((cap - per_s) / per_p);
-    if (S > (int)((cap - (size_t)P * per_p) / per_s)) S = (int)((cap - (size_t)P * per_p) / per_s);
-}
-inline int splits_for(int pages, long tiles, int min_pages) {
-    long s = (long)pages * FILL / tiles;
-    if (s > pages / min_pages) s = pages / min_pages;
-    if (s > MAX_SPLITS) s = MAX_SPLITS;
-    return s < 1 ? 1 : (int)s;
-}
-// force_p / force_s: 0 = choose, >= 1 = that count (cut to 64 and the workspace), force_p = -1 = do not share
-SharedPlan plan_shared(int batch, int max_seqlen_q, int num_groups, int max_group_tokens, int max_prefix, int max_suffix_past, int num_heads,
-                       int num_kv_heads, int force_p, int force_s) {
-    const int G = num_heads / num_kv_heads;
-    const AppendPlan ap = plan_append(max_seqlen_q, num_heads, num_kv_heads);
-    SharedPlan p = {};
-    p.tq = ap.tile_tokens, p.q_tiles = ap.q_tiles, p.waves = ap.waves;
-    p.gq_tiles = (max_group_tokens + p.tq - 1) / p.tq;
-    p.rw_suffix = rec_waves(p.tq, max_seqlen_q, G), p.rw_prefix = rec_waves(p.tq, max_group_tokens, G);
-    const long base_p = (long)num_groups * p.gq_tiles * num_kv_heads, base_s = (long)batch * p.q_tiles * num_kv_heads;
-    const int pages_p = max_prefix / BN, pages_s = (max_suffix_past + BN - 1) / BN;
-    const long tiles = base_p * pages_p + base_s * (pages_s + 1);
-    const bool share = force_p >= 0 && (force_p > 0 || (num_groups < batch && max_prefix >= BN));
-    if (share) {
-        p.P = force_p > 0 ? (force_p > MAX_SPLITS ? MAX_SPLITS : force_p) : splits_for(pages_p, tiles, MIN_PAGES_PREFIX);
-        p.S = force_s > 0 ? (force_s > MAX_SPLITS ? MAX_SPLITS : force_s) : splits_for(pages_s, tiles, MIN_PAGES_SUFFIX);
-        fit_workspace(p.P, p.S, set_bytes(base_p, p.rw_prefix), set_bytes(base_s, p.rw_suffix));
-        p.bytes = (size_t)p.P * set_bytes(base_p, p.rw_prefix) + (size_t)p.S * set_bytes(base_s, p.rw_suffix);
-    }
-    if (p.P == 0) p.S = 0, p.bytes = 0, p.rw_prefix = 0, p.rw_suffix = NWV;      // the split entry's launch: the caller asks its planner
-    return p;
-}
+using attn_plan::SharedPlan;      // the planner's rule: attn_plan.h plan_shared (qs_append_shared_plan reports it)
 
 struct SharedGeom {
     int num_heads, num_kv_heads, max_blocks, batch, num_groups;
@@ -252,6 +184,29 @@ int check_shared_sizes(int batch, int max_seqlen_q, int num_groups, int max_grou
     return QS_OK;
 }
 
+// the shared launch and its merge; no workspace (its first use inside a capture): the un-split launch - correct because the members'
+// prefix entries are equal
+int shared_launch(const AppendArgs& a, const int32_t* group_offsets, const int32_t* prefix_lens, const int32_t* seq_group, int num_groups,
+                  const SharedPlan& p) {
+    const AppendPlan ap = {p.tq, p.q_tiles, p.waves};
+    float* const ws = qs_split_workspace(p.bytes, a.stream);
+    if (!ws) return qs_append_launch(a, ap);
+    SharedGeom ge;
+    ge.num_heads = a.num_heads, ge.num_kv_heads = a.num_kv_heads, ge.max_blocks = a.max_blocks, ge.batch = a.batch, ge.num_groups = num_groups;
+    ge.tq = p.tq, ge.q_tiles = p.q_tiles, ge.gq_tiles = p.gq_tiles, ge.P = p.P, ge.S = p.S, ge.rw_prefix = p.rw_prefix, ge.rw_suffix = p.rw_suffix;
+    ge.suffix_off = (long)num_groups * p.gq_tiles * a.num_kv_heads * p.P * p.rw_prefix;
+    const int ny = p.gq_tiles * p.P > p.q_tiles * p.S ? p.gq_tiles * p.P : p.q_tiles * p.S;
+    QS_REQUIRE(ny <= 65535 && num_groups + a.batch <= 65535, "append_attention_shared: the grid (%d, %d) exceeds the launch limits", ny,
+               num_groups + a.batch);
+    const int lrc = launch_kernel_pair<append_shared_kernel<true>, append_shared_kernel<false>>(
+        "append_attention_shared", "append_attention_shared", a.int4, dim3(a.num_kv_heads, ny, num_groups + a.batch), dim3(64 * p.waves), a.stream,
+        a.qkv, ws, a.cu_seqlens_q, a.past_lens, a.kv_pointers, group_offsets, prefix_lens, seq_group, ge, a.qkv_stride0);
+    if (lrc != QS_OK) return lrc;
+    hipLaunchKernelGGL(append_shared_merge_kernel, dim3(a.num_kv_heads, p.q_tiles * NWV, a.batch), dim3(256), 0, a.stream, ws, a.out, a.cu_seqlens_q,
+                       a.past_lens, group_offsets, prefix_lens, seq_group, ge, a.out_stride0);
+    return qs_launch_status("append_shared_merge");
+}
+
 }  // namespace
 
 extern "C" int qs_append_shared_plan(int batch, int max_seqlen_q, int num_groups, int max_group_tokens, int max_prefix, int max_suffix_past,
@@ -261,7 +216,8 @@ extern "C" int qs_append_shared_plan(int batch, int max_seqlen_q, int num_groups
     if (const int rc = check_shared_sizes(batch, max_seqlen_q, num_groups, max_group_tokens, num_heads, num_kv_heads); rc != QS_OK) return rc;
     QS_REQUIRE(max_prefix >= 0 && max_suffix_past >= 0, "append_attention_shared: negative max_prefix / max_suffix_past");
     if (batch == 0 || max_seqlen_q == 0 || max_group_tokens == 0) return QS_OK;
-    const SharedPlan p = plan_shared(batch, max_seqlen_q, num_groups, max_group_tokens, max_prefix, max_suffix_past, num_heads, num_kv_heads, 0, 0);
+    const SharedPlan p = attn_plan::plan_shared(batch, max_seqlen_q, num_groups, max_group_tokens, max_prefix, max_suffix_past, num_heads,
+                                                num_kv_heads, 0, 0, qs_split_workspace_capacity());
     plan8[0] = p.tq, plan8[1] = p.q_tiles, plan8[2] = p.waves, plan8[4] = p.gq_tiles, plan8[5] = p.P;
     if (p.P == 0) {                                      // the split entry's launch over the whole past
         int plan5[5];
@@ -285,56 +241,23 @@ extern "C" int qs_append_attention_shared(const void* qkv, void* out, const int3
                                           int64_t qkv_stride0, int64_t out_stride0, int tokens_per_block, int size_per_token, int int4_kv_cache,
                                           int kv_cache_with_zeros, int max_prefix, int max_suffix_past, int num_prefix_splits,
                                           int num_suffix_splits, qs_stream_t stream) {
+    AppendArgs a;
     if (const int bad = check_append_args(qkv, out, cu_seqlens_q, past_lens, kv_pointers, num_tokens, batch, max_seqlen_q, max_blocks, num_heads,
                                           num_kv_heads, head_dim, qkv_stride0, out_stride0, tokens_per_block, size_per_token, int4_kv_cache,
-                                          kv_cache_with_zeros); bad != QS_OK)
+                                          kv_cache_with_zeros, stream, &a); bad != QS_OK)
         return bad;
     QS_REQUIRE(group_offsets && prefix_lens && seq_group, "append_attention_shared: null group array");
     if (const int rc = check_shared_sizes(batch, max_seqlen_q, num_groups, max_group_tokens, num_heads, num_kv_heads); rc != QS_OK) return rc;
     QS_REQUIRE(num_prefix_splits >= -1, "append_attention_shared: num_prefix_splits=%d (0 = ask the planner, >= 1 = forced, -1 = do not share)",
                num_prefix_splits);
     QS_REQUIRE(num_suffix_splits >= 0, "append_attention_shared: num_suffix_splits=%d (0 = ask the planner, >= 1 = forced)", num_suffix_splits);
-    if (batch == 0 || max_seqlen_q == 0 || num_tokens == 0 || max_group_tokens == 0) return QS_OK;
-    const int table = max_blocks * BN;                   // (a prefix and a past are cut to the table anyway)
-    const int hint_p = max_prefix < 0 || max_prefix > table ? table : max_prefix;
-    const int hint_s = max_suffix_past < 0 || max_suffix_past > table ? table : max_suffix_past;
-    const SharedPlan p = plan_shared(batch, max_seqlen_q, num_groups, max_group_tokens, hint_p, hint_s, num_heads, num_kv_heads, num_prefix_splits,
-                                     num_suffix_splits);
-    hipStream_t st = (hipStream_t)stream;
-    if (p.P == 0)                                        // do not share: the split entry over the whole past (its planner, or the forced count)
-        return qs_append_attention_split(qkv, out, cu_seqlens_q, past_lens, kv_pointers, num_tokens, batch, max_seqlen_q, max_blocks, num_heads,
-                                         num_kv_heads, head_dim, qkv_stride0, out_stride0, tokens_per_block, size_per_token, int4_kv_cache,
-                                         kv_cache_with_zeros, hint_p + hint_s > table ? table : hint_p + hint_s, num_suffix_splits, stream);
-    float* const ws = qs_split_workspace(p.bytes, st);
-    if (!ws)      // no workspace (its first use inside a capture): the un-split launch - correct because the members' prefix entries are equal
-        return qs_append_attention(qkv, out, cu_seqlens_q, past_lens, kv_pointers, num_tokens, batch, max_seqlen_q, max_blocks, num_heads,
-                                   num_kv_heads, head_dim, qkv_stride0, out_stride0, tokens_per_block, size_per_token, int4_kv_cache,
-                                   kv_cache_with_zeros, stream);
-    constexpr int SMEM = 2 * KS_BYTES + 2 * VT_BYTES;
-    static bool lds_reserved[QS_MAX_DEVICES] = {};
-    if (const hipError_t e = qs_reserve_lds({reinterpret_cast<const void*>(append_shared_kernel<true>),
-                                             reinterpret_cast<const void*>(append_shared_kernel<false>)},
-                                            SMEM, lds_reserved); e != hipSuccess) {
-        qs_set_error("append_attention_shared: cannot reserve %d bytes of LDS", SMEM);
-        return (int)e;
-    }
-    const float scale_log2 = 0.08838834764831845f * 1.4426950408889634f;   // 1/sqrt(128) * log2(e)
-    SharedGeom ge;
-    ge.num_heads = num_heads, ge.num_kv_heads = num_kv_heads, ge.max_blocks = max_blocks, ge.batch = batch, ge.num_groups = num_groups;
-    ge.tq = p.tq, ge.q_tiles = p.q_tiles, ge.gq_tiles = p.gq_tiles, ge.P = p.P, ge.S = p.S, ge.rw_prefix = p.rw_prefix, ge.rw_suffix = p.rw_suffix;
-    ge.suffix_off = (long)num_groups * p.gq_tiles * num_kv_heads * p.P * p.rw_prefix;
-    const int ny = p.gq_tiles * p.P > p.q_tiles * p.S ? p.gq_tiles * p.P : p.q_tiles * p.S;
-    QS_REQUIRE(ny <= 65535 && num_groups + batch <= 65535, "append_attention_shared: the grid (%d, %d) exceeds the launch limits", ny,
-               num_groups + batch);
-    const dim3 grid(num_kv_heads, ny, num_groups + batch), block(64 * p.waves);
-    if (int4_kv_cache)
-        hipLaunchKernelGGL(append_shared_kernel<true>, grid, block, SMEM, st, (const _Float16*)qkv, ws, cu_seqlens_q, past_lens, kv_pointers,
-                           group_offsets, prefix_lens, seq_group, ge, qkv_stride0, scale_log2);
-    else
-        hipLaunchKernelGGL(append_shared_kernel<false>, grid, block, SMEM, st, (const _Float16*)qkv, ws, cu_seqlens_q, past_lens, kv_pointers,
-                           group_offsets, prefix_lens, seq_group, ge, qkv_stride0, scale_log2);
-    if (const int lrc = qs_launch_status("append_attention_shared"); lrc != QS_OK) return lrc;
-    hipLaunchKernelGGL(append_shared_merge_kernel, dim3(num_kv_heads, p.q_tiles * NWV, batch), dim3(256), 0, st, ws, (_Float16*)out, cu_seqlens_q,
-                       past_lens, group_offsets, prefix_lens, seq_group, ge, out_stride0);
-    return qs_launch_status("append_shared_merge");
+    if (a.empty() || max_group_tokens == 0) return QS_OK;
+    const int hint_p = table_hint(max_prefix, max_blocks), hint_s = table_hint(max_suffix_past, max_blocks);
+    const size_t capacity = qs_split_workspace_capacity();
+    const SharedPlan p = attn_plan::plan_shared(batch, max_seqlen_q, num_groups, max_group_tokens, hint_p, hint_s, num_heads, num_kv_heads,
+                                                num_prefix_splits, num_suffix_splits, capacity);
+    if (p.P != 0) return shared_launch(a, group_offsets, prefix_lens, seq_group, num_groups, p);
+    // do not share: the split launch over the whole past (its planner, or the forced count)
+    const int planned = attn_plan::plan_splits(batch, p.q_tiles, num_kv_heads, table_hint(hint_p + hint_s, max_blocks), capacity);
+    return qs_append_split_launch(a, {p.tq, p.q_tiles, p.waves}, num_suffix_splits > 0 ? num_suffix_splits : planned);
 }

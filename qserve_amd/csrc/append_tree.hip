@@ -137,60 +137,48 @@ __global__ __launch_bounds__(256) void kv_commit_path_kernel(const int64_t* __re
 
 }  // namespace
 
+namespace {
+
+int tree_launch(const AppendArgs& a, const AppendPlan& p) {
+    return launch_kernel_pair<append_tree_attention_kernel<true>, append_tree_attention_kernel<false>>(
+        "append_tree_attention", "append_tree_attention", a.int4, dim3(a.num_kv_heads, p.q_tiles, a.batch), dim3(64 * p.waves), a.stream, a.qkv,
+        a.out, a.cu_seqlens_q, a.past_lens, a.kv_pointers, a.tree_mask, a.num_heads, a.num_kv_heads, a.max_blocks, p.tile_tokens, a.qkv_stride0,
+        a.out_stride0);
+}
+
+int tree_split_launch(const AppendArgs& a, const AppendPlan& p, int wanted_splits) {
+    float* ws = nullptr;
+    const int splits = qs_append_split_resolve(wanted_splits, a, p, &ws);
+    if (!ws) return tree_launch(a, p);           // one split, or no workspace (first use inside a capture): the un-split launch
+    const int lrc = launch_kernel_pair<append_tree_attention_split_kernel<true>, append_tree_attention_split_kernel<false>>(
+        "append_tree_attention", "append_tree_attention_split", a.int4, dim3(a.num_kv_heads, p.q_tiles * splits, a.batch), dim3(64 * p.waves),
+        a.stream, a.qkv, ws, a.cu_seqlens_q, a.past_lens, a.kv_pointers, a.tree_mask, a.num_heads, a.num_kv_heads, a.max_blocks, p.tile_tokens,
+        p.q_tiles, splits, a.qkv_stride0);
+    return lrc != QS_OK ? lrc : qs_append_merge_launch(ws, a, p, splits);
+}
+
+}  // namespace
+
 extern "C" int qs_append_tree_attention(const void* qkv, void* out, const int32_t* cu_seqlens_q, const int32_t* past_lens,
                                         const int64_t* kv_pointers, const uint64_t* tree_mask, int num_tokens, int batch, int max_seqlen_q,
                                         int max_blocks, int num_heads, int num_kv_heads, int head_dim, int64_t qkv_stride0,
                                         int64_t out_stride0, int tokens_per_block, int size_per_token, int int4_kv_cache,
                                         int kv_cache_with_zeros, int max_past, int num_splits, qs_stream_t stream) {
+    AppendArgs a;
     if (const int bad = check_append_args(qkv, out, cu_seqlens_q, past_lens, kv_pointers, num_tokens, batch, max_seqlen_q, max_blocks, num_heads,
                                           num_kv_heads, head_dim, qkv_stride0, out_stride0, tokens_per_block, size_per_token, int4_kv_cache,
-                                          kv_cache_with_zeros); bad != QS_OK)
+                                          kv_cache_with_zeros, stream, &a); bad != QS_OK)
         return bad;
     QS_REQUIRE(tree_mask, "append_tree_attention: null tree_mask");
     QS_REQUIRE((reinterpret_cast<uintptr_t>(tree_mask) & 7) == 0, "append_tree_attention: tree_mask must be 8-byte aligned");
     QS_REQUIRE(max_seqlen_q <= MAX_TREE, "append_tree_attention: max_seqlen_q=%d, a tree has at most %d nodes per sequence", max_seqlen_q,
                MAX_TREE);
     QS_REQUIRE(num_splits >= 0, "append_tree_attention: num_splits=%d (0 = ask the planner, >= 1 = forced)", num_splits);
+    a.tree_mask = tree_mask;
     int plan5[5];
-    const int hint = max_past < 0 || max_past > max_blocks * BN ? max_blocks * BN : max_past;
-    const int rc = qs_append_attention_split_plan(batch, max_seqlen_q, hint, num_heads, num_kv_heads, int4_kv_cache, plan5);
-    if (rc != QS_OK) return rc;
-    if (batch == 0 || max_seqlen_q == 0 || num_tokens == 0) return QS_OK;
-    float* ws = nullptr;
-    const int splits = qs_append_split_resolve(num_splits > 0 ? num_splits : plan5[3], batch, num_kv_heads, plan5[1], (hipStream_t)stream, &ws);
-    constexpr int SMEM = 2 * KS_BYTES + 2 * VT_BYTES;
-    static bool lds_reserved[QS_MAX_DEVICES] = {};
-    if (const hipError_t e = qs_reserve_lds({reinterpret_cast<const void*>(append_tree_attention_kernel<true>),
-                                             reinterpret_cast<const void*>(append_tree_attention_kernel<false>),
-                                             reinterpret_cast<const void*>(append_tree_attention_split_kernel<true>),
-                                             reinterpret_cast<const void*>(append_tree_attention_split_kernel<false>)},
-                                            SMEM, lds_reserved); e != hipSuccess) {
-        qs_set_error("append_tree_attention: cannot reserve %d bytes of LDS", SMEM);
-        return (int)e;
-    }
-    const float scale_log2 = 0.08838834764831845f * 1.4426950408889634f;   // 1/sqrt(128) * log2(e)
-    const int tq = plan5[0], q_tiles = plan5[1];
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 block(64 * plan5[2]);
-    if (!ws) {    // one split, or no workspace (first use inside a capture): the un-split launch
-        const dim3 grid(num_kv_heads, q_tiles, batch);
-        if (int4_kv_cache)
-            hipLaunchKernelGGL(append_tree_attention_kernel<true>, grid, block, SMEM, st, (const _Float16*)qkv, (_Float16*)out, cu_seqlens_q,
-                               past_lens, kv_pointers, tree_mask, num_heads, num_kv_heads, max_blocks, tq, qkv_stride0, out_stride0, scale_log2);
-        else
-            hipLaunchKernelGGL(append_tree_attention_kernel<false>, grid, block, SMEM, st, (const _Float16*)qkv, (_Float16*)out, cu_seqlens_q,
-                               past_lens, kv_pointers, tree_mask, num_heads, num_kv_heads, max_blocks, tq, qkv_stride0, out_stride0, scale_log2);
-        return qs_launch_status("append_tree_attention");
-    }
-    const dim3 grid(num_kv_heads, q_tiles * splits, batch);
-    if (int4_kv_cache)
-        hipLaunchKernelGGL(append_tree_attention_split_kernel<true>, grid, block, SMEM, st, (const _Float16*)qkv, ws, cu_seqlens_q, past_lens,
-                           kv_pointers, tree_mask, num_heads, num_kv_heads, max_blocks, tq, q_tiles, splits, qkv_stride0, scale_log2);
-    else
-        hipLaunchKernelGGL(append_tree_attention_split_kernel<false>, grid, block, SMEM, st, (const _Float16*)qkv, ws, cu_seqlens_q, past_lens,
-                           kv_pointers, tree_mask, num_heads, num_kv_heads, max_blocks, tq, q_tiles, splits, qkv_stride0, scale_log2);
-    if (const int lrc = qs_launch_status("append_tree_attention_split"); lrc != QS_OK) return lrc;
-    return qs_append_merge_launch(ws, out, cu_seqlens_q, past_lens, batch, num_heads, num_kv_heads, max_blocks, tq, q_tiles, splits, out_stride0, st);
+    const int rc = qs_append_attention_split_plan(batch, max_seqlen_q, table_hint(max_past, max_blocks), num_heads, num_kv_heads, int4_kv_cache, plan5);
+    if (rc != QS_OK || a.empty()) return rc;
+    return tree_split_launch(a, {plan5[0], plan5[1], plan5[2]}, num_splits > 0 ? num_splits : plan5[3]);
 }
 
 extern "C" int qs_kv_cache_commit_path(const int64_t* kv_pointers, const int32_t* past_lens, const int32_t* accept_idx,

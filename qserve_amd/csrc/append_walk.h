@@ -14,10 +14,16 @@
 // staging live here, once.
 #pragma once
 #include "append_dequant.h"
+#include "attn_host.h"
 
 namespace qs_append {
 
 using namespace qs_flash;
+using attn_plan::AppendPlan;
+using attn_plan::MAX_SPLITS;
+using attn_plan::REC_FLOATS;       // a wave's split-KV partial record (append_attention_split.hip has the layout)
+static_assert(attn_plan::PAGE == BN && attn_plan::DH == DH && attn_plan::APPEND_WAVES == NWV && attn_plan::APPEND_ROWS == BM,
+              "attn_plan.h plans for the tile geometry of flash_tile.h");
 
 // The causal rule of append attention: new token i sees new keys 0 .. i.
 struct CausalNewKeys {
@@ -32,10 +38,6 @@ struct CausalNewKeys {
         mask_keys_above(sacc, page ? page_limit : tok_ld - j0, hi);
     }
 };
-
-// Split-KV partial records (append_attention_split.hip has the layout): one block per (workgroup of the un-split grid, split, wave)
-constexpr int REC_FLOATS = 32 * (DH + 2);          // O^T [32 chunks][32 rows][4], m[32], l[32]
-constexpr int MAX_SPLITS = 64;
 
 // The walk.  Rows: row r = G * token + g of query tile tok0 .. tok0 + tq - 1 (wave w owns rows 32 w .. 32 w + 31); keys: pages
 // ktab[0 .. np) / vtab[0 .. np) holding `past` cached tokens counted from ktab[0] (past >= np * BN: no slot masked), then - with_new -
@@ -265,9 +267,23 @@ __device__ __forceinline__ int clamp_past(int past, int max_blocks) {      // ne
     return past < 0 ? 0 : past > max_blocks * BN ? max_blocks * BN : past;
 }
 
-}  // namespace qs_append
+// ---- the launch tail of every append attention kernel pair KERNEL<true> (KV4) / KERNEL<false> (KV8): the LDS reservation of the two
+// K and two V tile images (once per pair and device: the flags belong to the pair, a reservation is never skipped because another
+// kernel's was made), the softmax scale in log2 units - the kernels' LAST argument - and the choice of the instantiation.
+// `entry` words the reservation's error, `what` the launch's.
+template <auto KV4, auto KV8, class... Args>
+int launch_kernel_pair(const char* entry, const char* what, bool int4, dim3 grid, dim3 block, hipStream_t stream, Args... args) {
+    constexpr int SMEM = 2 * KS_BYTES + 2 * VT_BYTES;
+    static bool lds_reserved[QS_MAX_DEVICES] = {};
+    if (const hipError_t e = qs_reserve_lds({reinterpret_cast<const void*>(KV4), reinterpret_cast<const void*>(KV8)}, SMEM, lds_reserved);
+        e != hipSuccess) {
+        qs_set_error("%s: cannot reserve %d bytes of LDS", entry, SMEM);
+        return (int)e;
+    }
+    const float scale_log2 = 0.08838834764831845f * 1.4426950408889634f;   // 1/sqrt(128) * log2(e)
+    if (int4) hipLaunchKernelGGL(KV4, grid, block, SMEM, stream, args..., scale_log2);
+    else hipLaunchKernelGGL(KV8, grid, block, SMEM, stream, args..., scale_log2);
+    return qs_launch_status(what);
+}
 
-// host side of the split-KV launchers (append_attention_split.hip)
-int qs_append_split_resolve(int wanted, int batch, int num_kv_heads, int q_tiles, hipStream_t stream, float** ws);
-int qs_append_merge_launch(const float* ws, void* out, const int32_t* cu_seqlens_q, const int32_t* past_lens, int batch, int num_heads,
-                           int num_kv_heads, int max_blocks, int tq, int q_tiles, int splits, int64_t out_stride0, hipStream_t stream);
+}  // namespace qs_append

@@ -23,14 +23,17 @@
 //     tail of the last page gets p = 0); the reference's out-of-range reads do not exist.
 //   * numerics: KV4 dequantisation reproduces the reference bit for bit (exact nibble -> fp16, then one
 //     hfma2(h, half(scale), half(-scale*zero)), Utils.h:2190-2213); dot products and P.V accumulate in fp32.
-#include "common.h"
+#include "attn_host.h"
 #include "kv_quant.h"
 
 namespace {
 
+using attn_plan::AttnPlan;
 constexpr int TPB = 256;
 constexpr int PAGE_TOK = 64;
 constexpr int DH = 128;
+static_assert(PAGE_TOK == attn_plan::PAGE && DH == attn_plan::DH && TPB == 64 * attn_plan::DECODE_WAVES_VALU,
+              "attn_plan.h plans for this file's geometry");
 
 // exact uint4 -> fp16 for the 8 nibbles of x, in the order (e0,e4),(e1,e5),(e2,e6),(e3,e7) (Utils.h:2125-2188)
 __device__ __forceinline__ void nib8_to_h2(u32 x, h2 (&o)[4]) {
@@ -628,10 +631,10 @@ __global__ void padding_offsets_kernel(int* __restrict__ out, const int* __restr
     for (int i = threadIdx.x; i < end - beg; i += blockDim.x) out[beg + i] = off;
 }
 
+// family 3: the VALU kernel (no splits, no table: the plan has nothing to add)
 template <bool INT4>
-int launch_decode(int G, dim3 grid, hipStream_t st, const _Float16* q, const _Float16* k, const _Float16* v,
-                  const int64_t* kvp, const int* len, _Float16* out, int H, int Hkv, int64_t qs, int64_t kvs, int mb,
-                  int timestep, float base) {
+int launch_decode(const DecodeArgs& a, const AttnPlan&) {
+    QS_DECODE_LOCALS(a);
 #define QS_LAUNCH_G(GG)                                                                                            \
     hipLaunchKernelGGL((decode_attention_kernel<GG, INT4>), grid, dim3(TPB), 0, st, q, k, v, kvp, len, out, H, Hkv, \
                        qs, kvs, mb, timestep, base)
@@ -652,83 +655,17 @@ int launch_decode(int G, dim3 grid, hipStream_t st, const _Float16* q, const _Fl
     return qs_launch_status("single_query_attention");
 }
 
-}  // namespace
-
-// library-managed RoPE table (attention_mfma.hip)
-const float2* qs_rope_table(float base, int max_pos, hipStream_t st, int* len_out);
-// KV4 fast path on the matrix cores (attention_mfma.hip)
-int qs_launch_decode_mfma(int G, dim3 grid, hipStream_t st, const _Float16* q, const _Float16* k, const _Float16* v,
-                          const int64_t* kvp, const int* len, _Float16* out, int H, int Hkv, int64_t qs, int64_t kvs,
-                          int mb, int timestep, float base, int max_pos, int nsplit, int kflags, int exp_flags,
-                          const QsAttnQuant* quant, bool* fused);
-// KV8 twin (attention_mfma8.hip)
-int qs_launch_decode_mfma8(int G, dim3 grid, hipStream_t st, const _Float16* q, const _Float16* k, const _Float16* v,
-                           const int64_t* kvp, const int* len, _Float16* out, int H, int Hkv, int64_t qs, int64_t kvs,
-                           int mb, int timestep, float base, int max_pos, int nsplit);
-namespace {
-
 // 0 = MFMA kernel for KV4 with the split-KV heuristic (default), 1 = VALU kernel everywhere, 2 = prefill writer in its
 // per-lane form (no RoPE table), 3 = KV4 MFMA kernel whose service wave always owns pages (the round-2 form: A/B),
 // 100 + n = MFMA kernel with exactly n KV splits (A/B tests)
 qs_flag g_attn_variant = 0;
 
-// Split-KV factor of the matrix-core decode kernels (KV4: attention_mfma.hip, KV8: attention_mfma8.hip): the number of workgroups a
-// (sequence, KV head) pair's page range is cut into.  Cost model fitted to a sweep on the MI355X (profiles/round5_split_sweep*.txt:
-// 1 .. 48 sequences x 8 KV heads, 1 030 .. 7 700 tokens, 1 .. 32 splits; mean regret 0.7 %, worst 10 %, against the forced best;
-// the round-2 rule "aim at >= 512 workgroups" it replaces: 8 % / 39 %):
-//   time(n) = rounds * F + max(rounds * pages / n * t_cu,  blocks * pages * t_hbm) + merge(n)
-// rounds = ceil(blocks * n / 256): workgroups land on the 256 CUs round-robin and a CU streams at its own request budget whatever
-// the number of resident workgroups, so 320 workgroups take as long as 512; F = a workgroup's head + tail; t_cu = one CU's time
-// per page (64 tokens of K and V), t_hbm = the chip's; merge = the second launch (boundary + n partials per head).
-// ns / ps units, integer arithmetic (the plan is part of the ABI: tests/test_dispatch_plan.py pins it).
-int qs_attn_choose_splits(int blocks, int pages, int kv8, int fused_quant) {
-    if (blocks >= 512 || pages < 4) return 1;
-    const long F = kv8 ? 5000 : 4000, t_cu = kv8 ? 450 : 340, t_hbm_ps = kv8 ? 2540 : 1330;
-    long best = -1;
-    int best_n = 1;
-    // (n <= 8: within this kernel's range - page tables of <= 192 entries, 12 288 tokens; longer tables go to the VALU kernels -
-    //  more splits do not pay: 1 / 2 / 4 sequences at 8 191 and 12 200 tokens, forced 4 / 8 / 12 / 16 / 24 splits against this
-    //  choice, KV4 and KV8: the choice is the best or within 1 % of it everywhere except one sequence of 12 200 tokens over an INT8
-    //  cache, where 12 splits measure 20.4 against 21.7 us - profiles/round6_split_long.txt.  ADVICE r05 extrapolated the cost
-    //  formula to 512 pages, which this function is never asked about.)
-    for (int n = 1; n <= 8; ++n) {
-        if (n > 1 && pages / n < 2) break;
-        const long rounds = ((long)blocks * n + 255) / 256;
-        const long per_cu = rounds * pages * t_cu / n, chip = (long)blocks * pages * t_hbm_ps / 1000;
-        // (fused_quant: qs_single_query_attention_quant - only the un-split launch can finish the row itself; a split one is
-        // followed by the quantiser as a launch of its own, 3.2 us + boundary)
-        const long cost = rounds * F + (per_cu > chip ? per_cu : chip) + (n > 1 ? 2500 + 300 * n + (fused_quant ? 3500 : 0) : 0);
-        if (best < 0 || cost < best) best = cost, best_n = n;
-    }
-    return best_n;
-}
-// The decode attention kernel choice, from the problem and the selection hook `variant` alone (no device access, no global
-// state: qs_attention_plan reports it, single_query_attention launches it).  fused_quant: the attention + quant entry asks.
-// family 1 = matrix-core KV4, 2 = matrix-core KV8, 3 = VALU kernel, 0 = rejected (qs_last_error says why); nsplit = KV splits
-// (workgroups per sequence and KV head: the launchers cut it to what their workspace holds); waves per workgroup; kflags =
-// KV4 kernel switches (variants 5 and 7); exp_flags = KV4 ablation builds of the G = 4 kernel (200 + bits, QS_TIMING builds)
-struct AttnPlan {
-    int family, nsplit, waves, kflags, exp_flags;
-};
-AttnPlan plan_attention(int batch, int H, int Hkv, int max_blocks, int timestep, bool int4, bool fused_quant, int variant) {
-    const int G = H / Hkv;
-    if (G < 1 || G > 8) {
-        qs_set_error("single_query_attention: num_heads/num_kv_heads = %d not in 1..8", G);
-        return {0};
-    }
-    // the matrix-core kernel caches a sequence's page addresses in LDS (192 pages = 12288 tokens per sequence); longer
-    // page tables take the VALU kernel
-    if (variant == 1 || max_blocks > 192) return {3, 1, TPB / 64};
-    int force_split = variant >= 100 ? variant - 100 : 0, exp_flags = 0;
-    if (int4 && force_split >= 100) {
-        exp_flags = force_split - 100;
-        force_split = 0;
-    }
-    const int blocks = Hkv * batch;
-    const int pages_max = (timestep + PAGE_TOK - 1) / PAGE_TOK;
-    const int nsplit = force_split > 0 ? force_split : qs_attn_choose_splits(blocks, pages_max, int4 ? 0 : 1, int4 && fused_quant && H * DH <= 4096);
-    if (int4) return {1, nsplit, QS_ATTN_WAVES_KV4, variant == 5 ? 2 : variant == 7 ? 1024 : 0, exp_flags};
-    return {2, nsplit, QS_ATTN_WAVES_KV8};
+// The decode attention kernel choice: attn_plan.h's plan_attention under the selection hook, with its one rejection worded
+// (family 0: qs_last_error says why)
+AttnPlan plan_attention(int batch, int H, int Hkv, int max_blocks, int timestep, bool int4, bool fused_quant) {
+    const AttnPlan plan = attn_plan::plan_attention(batch, H, Hkv, max_blocks, timestep, int4, fused_quant, g_attn_variant);
+    if (!plan.family) qs_set_error("single_query_attention: num_heads/num_kv_heads = %d not in 1..8", H / Hkv);
+    return plan;
 }
 
 // qs_single_query_attention; quant (nullable): qs_single_query_attention_quant's request, *fused = whether the launch
@@ -763,26 +700,16 @@ int single_query_attention(const void* q, const void* k, const void* v, const in
                  reinterpret_cast<uintptr_t>(out)) & 15) == 0,
                "single_query_attention: q, k, v and out must be 16-byte aligned");
     if (batch == 0) return QS_OK;
-    const AttnPlan plan = plan_attention(batch, num_heads, num_kv_heads, max_blocks, timestep, int4_kv_cache, quant != nullptr,
-                                         g_attn_variant);
+    const AttnPlan plan = plan_attention(batch, num_heads, num_kv_heads, max_blocks, timestep, int4_kv_cache, quant != nullptr);
     if (!plan.family) return QS_ENOSUP;
-    dim3 grid(num_kv_heads, batch);
-    const int G = num_heads / num_kv_heads;
-    hipStream_t st = (hipStream_t)stream;
-    const _Float16 *q16 = (const _Float16*)q, *k16 = (const _Float16*)k, *v16 = (const _Float16*)v;
-    if (plan.family == 1)
-        return qs_launch_decode_mfma(G, grid, st, q16, k16, v16, kv_pointers, length_per_sample, (_Float16*)out, num_heads,
-                                     num_kv_heads, q_stride0, kv_stride0, max_blocks, timestep, rotary_base, memory_max_seqlen,
-                                     plan.nsplit, plan.kflags, plan.exp_flags, quant, fused);
-    if (plan.family == 2)
-        return qs_launch_decode_mfma8(G, grid, st, q16, k16, v16, kv_pointers, length_per_sample, (_Float16*)out, num_heads,
-                                      num_kv_heads, q_stride0, kv_stride0, max_blocks, timestep, rotary_base, memory_max_seqlen,
-                                      plan.nsplit);
-    if (int4_kv_cache)
-        return launch_decode<true>(G, grid, st, q16, k16, v16, kv_pointers, length_per_sample, (_Float16*)out, num_heads,
-                                   num_kv_heads, q_stride0, kv_stride0, max_blocks, timestep, rotary_base);
-    return launch_decode<false>(G, grid, st, q16, k16, v16, kv_pointers, length_per_sample, (_Float16*)out, num_heads,
-                                num_kv_heads, q_stride0, kv_stride0, max_blocks, timestep, rotary_base);
+    DecodeArgs a;
+    a.G = num_heads / num_kv_heads, a.grid = dim3(num_kv_heads, batch), a.st = (hipStream_t)stream;
+    a.q = (const _Float16*)q, a.k = (const _Float16*)k, a.v = (const _Float16*)v, a.kvp = kv_pointers, a.len = length_per_sample;
+    a.out = (_Float16*)out, a.H = num_heads, a.Hkv = num_kv_heads, a.qs = q_stride0, a.kvs = kv_stride0, a.mb = max_blocks;
+    a.timestep = timestep, a.base = rotary_base, a.max_pos = memory_max_seqlen, a.quant = quant, a.fused = fused;
+    if (plan.family == 1) return qs_launch_decode_mfma(a, plan);
+    if (plan.family == 2) return qs_launch_decode_mfma8(a, plan);
+    return int4_kv_cache ? launch_decode<true>(a, plan) : launch_decode<false>(a, plan);
 }
 
 }  // namespace
@@ -832,7 +759,7 @@ extern "C" int qs_attention_plan(int batch, int num_heads, int num_kv_heads, int
                "single_query_attention: bad head counts H=%d Hkv=%d", num_heads, num_kv_heads);
     QS_REQUIRE(max_blocks > 0, "single_query_attention: bad max_blocks / memory_max_seqlen");
     if (batch == 0) return QS_OK;
-    const AttnPlan plan = plan_attention(batch, num_heads, num_kv_heads, max_blocks, timestep, int4_kv_cache, false, g_attn_variant);
+    const AttnPlan plan = plan_attention(batch, num_heads, num_kv_heads, max_blocks, timestep, int4_kv_cache, false);
     if (!plan.family) return QS_ENOSUP;
     plan3[0] = plan.family, plan3[1] = plan.nsplit, plan3[2] = plan.waves;
     return QS_OK;

@@ -33,7 +33,7 @@
 //     offsets leave through sum(P') at the end.
 //   * cache integers are exact in fp16 and every accumulation is fp32: the result is the exact attention over the
 //     de-quantised cache up to fp16 rounding of q, P' and the output (parity bar 1e-3, tests/test_attention_gpu.py).
-#include "common.h"
+#include "attn_host.h"
 #include "kv_quant.h"
 #include <mutex>
 
@@ -44,7 +44,7 @@ constexpr int DH = 128;
 constexpr int DHB = 64;        // KV4 bytes per token per head
 constexpr int UT = 32;         // tokens per pipeline unit (half a page)
 constexpr int USB = UT * DHB;  // bytes of K (or V) data per unit and KV head
-constexpr int NW = QS_ATTN_WAVES_KV4;   // waves per workgroup; all of them may own units
+constexpr int NW = attn_plan::DECODE_WAVES_KV4;   // waves per workgroup; all of them may own units
 constexpr int NWT = NW;
 constexpr int QS_ATTNQ_CAP = 4096;   // sequences the attention + quant fusion can hand over (larger batches run the pair)
 constexpr int QS_ATTNQ_ROW = 4096;   // values per row at most (H x 128 <= 4096: quant_kernel's 256-thread mapping)
@@ -1195,20 +1195,18 @@ int qs_attn_reset_handoff() {
 
 // called from attention.hip's dispatcher for KV4 with its plan (nsplit, kflags, exp_flags); quant (nullable): the request of
 // qs_single_query_attention_quant, *fused = whether this launch finished the quantised row too
-int qs_launch_decode_mfma(int G, dim3 grid, hipStream_t st, const _Float16* q, const _Float16* k, const _Float16* v,
-                          const int64_t* kvp, const int* len, _Float16* out, int H, int Hkv, int64_t qs, int64_t kvs,
-                          int mb, int timestep, float base, int max_pos, int nsplit, int kflags, int exp_flags,
-                          const QsAttnQuant* quant, bool* fused) {
+int qs_launch_decode_mfma(const DecodeArgs& a, const attn_plan::AttnPlan& plan) {
+    QS_DECODE_LOCALS(a);
+    const QsAttnQuant* const quant = a.quant;
+    bool* const fused = a.fused;
+    int kflags = plan.kflags, exp_flags = plan.exp_flags;
     int tab_len = 0;
     const float2* tab = qs_rope_table(base, max_pos, st, &tab_len);
     const int blocks = (int)(grid.x * grid.y);
-    float* ws = nullptr;
-    if (nsplit > 1) {
-        const size_t per_split = (size_t)blocks * G * (DH + 2) * sizeof(float);
-        if (per_split * nsplit > qs_split_workspace_capacity()) nsplit = (int)(qs_split_workspace_capacity() / per_split);
-        ws = nsplit > 1 ? qs_split_workspace(per_split * nsplit, st) : nullptr;
-        if (!ws) nsplit = 1;
-    }
+    const size_t per_split = attn_plan::decode_split_bytes(blocks, G);
+    int nsplit = plan.nsplit > 1 ? attn_plan::fit_splits(plan.nsplit, per_split, qs_split_workspace_capacity(), attn_plan::NO_SPLIT_CAP) : 1;
+    float* ws = nsplit > 1 ? qs_split_workspace(per_split * nsplit, st) : nullptr;
+    if (!ws) nsplit = 1;
     grid.z = nsplit;
     // attention + invoke_quant fusion (qs_single_query_attention_quant): un-split launches over rows of <= 4096 values
     // (quant_kernel's 256-thread mapping is what the finishing workgroup reproduces bit for bit)

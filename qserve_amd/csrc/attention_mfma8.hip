@@ -12,7 +12,7 @@
 //   * LDS images are bank-conflict free by permuting on the DMA SOURCE side: K rows keep their place and the 16-byte
 //     chunk at position p of row r holds chunk p ^ ((r >> 1) & 7); V rows are stored in slot s = tok ^ ((tok >> 2) & 1)
 //     (the probabilities are packed in the same order, so the contraction is unchanged).
-#include "common.h"
+#include "attn_host.h"
 #include "kv_quant.h"
 
 namespace {
@@ -20,7 +20,7 @@ namespace {
 constexpr int PAGE_TOK = 64;
 constexpr int DH = 128;
 constexpr int DHB = 128;       // KV8 bytes per token per head
-constexpr int NW = QS_ATTN_WAVES_KV8;   // waves per workgroup
+constexpr int NW = attn_plan::DECODE_WAVES_KV8;   // waves per workgroup
 constexpr int MAXP = 192;      // page-table entries cached in LDS per sequence (dispatcher: max_blocks <= MAXP)
 constexpr int NVM = 9;         // VMEM instructions of one page-slice fetch (8 x 1 KiB + scales|zeros)
 
@@ -477,26 +477,16 @@ __global__ __launch_bounds__(NW * 64, 2) void decode_attention_mfma8_kernel(
 
 }  // namespace
 
-// shared with attention_mfma.hip
-const float2* qs_rope_table(float base, int max_pos, hipStream_t st, int* len_out);
-float* qs_split_workspace(size_t bytes, hipStream_t st);
-size_t qs_split_workspace_capacity();
-void qs_launch_attention_merge(const float* ws, _Float16* out, int H, int Hkv, int G, int nsplit, int batch, hipStream_t st);
-
 // called from attention.hip's dispatcher for KV8 with its plan (nsplit: fewer where the split workspace cannot hold them)
-int qs_launch_decode_mfma8(int G, dim3 grid, hipStream_t st, const _Float16* q, const _Float16* k, const _Float16* v,
-                           const int64_t* kvp, const int* len, _Float16* out, int H, int Hkv, int64_t qs, int64_t kvs,
-                           int mb, int timestep, float base, int max_pos, int nsplit) {
+int qs_launch_decode_mfma8(const DecodeArgs& a, const attn_plan::AttnPlan& plan) {
+    QS_DECODE_LOCALS(a);
     int tab_len = 0;
     const float2* tab = qs_rope_table(base, max_pos, st, &tab_len);
     const int blocks = (int)(grid.x * grid.y);
-    float* ws = nullptr;
-    if (nsplit > 1) {
-        const size_t per_split = (size_t)blocks * G * (DH + 2) * sizeof(float);
-        if (per_split * nsplit > qs_split_workspace_capacity()) nsplit = (int)(qs_split_workspace_capacity() / per_split);
-        ws = nsplit > 1 ? qs_split_workspace(per_split * nsplit, st) : nullptr;
-        if (!ws) nsplit = 1;
-    }
+    const size_t per_split = attn_plan::decode_split_bytes(blocks, G);
+    int nsplit = plan.nsplit > 1 ? attn_plan::fit_splits(plan.nsplit, per_split, qs_split_workspace_capacity(), attn_plan::NO_SPLIT_CAP) : 1;
+    float* ws = nsplit > 1 ? qs_split_workspace(per_split * nsplit, st) : nullptr;
+    if (!ws) nsplit = 1;
     grid.z = nsplit;
 #define QS_LAUNCH_G(GG)                                                                                              \
     hipLaunchKernelGGL((decode_attention_mfma8_kernel<GG>), grid, dim3(NW * 64), 0, st, q, k, v, kvp, len, out, H, Hkv, \

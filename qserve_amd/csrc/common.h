@@ -252,9 +252,6 @@ unsigned* qs_attn_error_word(int slot);       // attention_mfma.hip: nullptr unt
 int qs_gemm_reset_handoff();                  // gemm_w4a8.hip: sentinel-fill the K-slice slabs, clear the error word
 int qs_attn_reset_handoff();                  // attention_mfma.hip: zero generation words / exchange rows, clear the error word
 
-// waves per workgroup of the matrix-core decode attention kernels (attention_mfma.hip, attention_mfma8.hip; qs_attention_plan)
-constexpr int QS_ATTN_WAVES_KV4 = 8;
-constexpr int QS_ATTN_WAVES_KV8 = 4;
 // request of qs_single_query_attention_quant to the KV4 launcher: fuse invoke_quant(_fuse_sum) of the output into the
 // kernel when it can (the launcher reports whether it did); otherwise the entry point runs the row kernel itself
 struct QsAttnQuant {

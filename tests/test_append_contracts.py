@@ -49,9 +49,12 @@ def test_products_run_on_the_fp16_matrix_cores(asm):
 
 
 def test_two_workgroups_fit_one_cu(asm):
-    # the tile buffers are dynamic LDS: 2 x (K image + V image) of 64 keys x 128 dims fp16, requested by the launcher
-    src = open(SRC).read()
-    assert re.search(r"constexpr int SMEM = 2 \* KS_BYTES \+ 2 \* VT_BYTES;", src)
+    # the tile buffers are dynamic LDS: 2 x (K image + V image) of 64 keys x 128 dims fp16, requested by the launcher - through the
+    # one launch tail of the append kernel pairs (append_walk.h launch_kernel_pair)
+    assert re.search(r"return launch_kernel_pair<append_attention_kernel<true>, append_attention_kernel<false>>\(", open(SRC).read())
+    tail = open(os.path.join(os.path.dirname(SRC), "append_walk.h")).read()
+    assert re.search(r"constexpr int SMEM = 2 \* KS_BYTES \+ 2 \* VT_BYTES;", tail)
+    assert re.search(r"hipLaunchKernelGGL\(KV4, grid, block, SMEM,", tail) and re.search(r"hipLaunchKernelGGL\(KV8, grid, block, SMEM,", tail)
     smem = 2 * (64 * 128 * 2) + 2 * (64 * 128 * 2)
     static = [int(x) for x in re.findall(r"; LDSByteSize: (\d+)", asm)]
     vgprs = [int(x) for x in re.findall(r"; NumVgprs: (\d+)", asm)]

@@ -4,6 +4,9 @@ composition of the existing oracles on the ALIASED tables (tests/_append_cases.p
 tests/test_append_gpu.py, nothing shared = the split entry bit for bit, decoy pages behind the members' own prefix entries, planted
 keys that single out one record's weight in the merge, stale workspace contents, and the engine."""
 import functools
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -143,6 +146,65 @@ def test_prefix_pages_are_read_through_the_first_members_table(gpu, int4, P):
     far = np.abs(got - c["ref_own"]).max(axis=(1, 2))
     print(f"distance from the oracle on the decoy tables: {far.max():.3e}; rows beyond the bar: {(far > TOL).sum()} of {len(far)}")
     assert (far > TOL).any(), "the result follows the members' own prefix entries"
+
+
+# ---- 3b. no workspace yet: the un-split launch ------------------------------------------------------------------------------------------
+_CHILD = r"""
+import sys
+sys.path[:0] = [sys.argv[1], sys.argv[2]]
+import numpy as np, torch
+import _shared_cases as SC
+from _append_cases import expected, host_pool
+from _helpers import DevPools, dev
+from qserve_amd import append as A
+from qserve_backend import fused_attention as fa
+gpu = torch.device("cuda:0")
+H, Hkv, int4, BASE = 8, 2, True, 1e4
+sizes, prefixes, extras, ns = (2,), (128,), (72, 72), (3, 3)      # one group of two, prefix 128 of past 200 (4 pages), n = 3
+spt = Hkv * 64
+r = np.random.default_rng(7)
+W = (H + 2 * Hkv) * 128
+lay = SC.layout(sizes, prefixes, extras, ns)
+pasts, cu_np = lay["pasts"], lay["cu_q"]
+own, aliased, nblocks, mb = SC.tables_for(r, lay, ns)
+pools = DevPools(nblocks, Hkv, int4, gpu)
+lens = [int(p) for p in pasts]
+ctx = dev(r.standard_normal((sum(lens), W)).astype(np.float16))
+cu_ctx = dev(np.concatenate([[0], np.cumsum(lens)]).astype(np.int32))
+fa.apply_bias_rope_update_kv_cache(ctx, dev(np.asarray(lens, np.int32)), fa.compute_padding_offsets(cu_ctx, max(lens), sum(lens)),
+                                   pools.pointers(own), H, Hkv, max(lens), 64, spt, 128, BASE, 8192, True, int4, True)
+kvp = pools.pointers(aliased)
+qkv = dev(r.standard_normal((sum(ns), W)).astype(np.float16))
+cu_q, past = dev(cu_np), dev(pasts)
+A.append_rope_update_kv_cache(qkv, cu_q, past, kvp, H, Hkv, spt, BASE, int4)
+groups = A.shared_prefix_groups(sizes, prefixes, gpu, batch=len(ns))
+out = torch.zeros((sum(ns), H, 128), dtype=torch.float16, device=gpu)
+torch.cuda.synchronize()
+g = torch.cuda.CUDAGraph()
+with torch.cuda.graph(g):        # the FIRST call of this process that wants the workspace: none yet, none may be allocated here
+    A.append_attention_shared(qkv, cu_q, past, kvp, H, Hkv, spt, int4, groups, max_seqlen_q=3, max_group_tokens=6, out=out,
+                              num_prefix_splits=2, num_suffix_splits=2)
+g.replay()
+torch.cuda.synchronize()
+hp = host_pool(pools.k.cpu().numpy(), pools.v.cpu().numpy(), Hkv, int4)
+ref = expected(qkv.cpu().numpy(), cu_np, pasts, aliased, hp, H, Hkv)
+err = float(np.abs(out.cpu().numpy().astype(np.float32) - ref).max())
+same = torch.equal(out, A.append_attention(qkv, cu_q, past, kvp, H, Hkv, spt, int4, max_seqlen_q=3))
+print(f"CHILD err={err:.3e} unsplit={int(same)}")
+"""
+
+
+def test_first_call_inside_a_capture_falls_back_to_the_unsplit_launch(gpu):
+    """tests/test_append_split_gpu.py's rule for this entry's own fall-back, in a fresh process (the workspace is allocated lazily, once
+    per process and device): P = 2, S = 2 asked for, the linear un-split launch runs."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-c", _CHILD, root, os.path.join(root, "tests")], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    line = [l for l in r.stdout.splitlines() if l.startswith("CHILD")][-1]
+    print(line)
+    err, same = float(line.split("err=")[1].split()[0]), line.endswith("unsplit=1")
+    assert err <= TOL, line
+    assert same, "a first call inside a capture must be the un-split launch, bit for bit"
 
 
 # ---- 4. planted keys ----------------------------------------------------------------------------------------------------------------------

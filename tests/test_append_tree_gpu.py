@@ -2,6 +2,9 @@
 DecodeEngine.verify_tree): chains against the linear entries bit for bit, random trees and arbitrary words against the float64 oracle
 of tests/_tree_cases.py, leaks, the path commit byte for byte, and the engine."""
 import copy
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -147,6 +150,62 @@ def test_random_trees_against_the_float64_oracle(gpu, H, Hkv, int4):
         print(f"tree attention H={H} Hkv={Hkv} int4={int4} splits={splits}: max abs err {err:.3e}")
         assert err <= TOL, f"num_splits={splits}: max abs err {err:.2e}"
     _spare_blocks_untouched(c.pools, c.tables, c.nblocks)
+
+
+# ---- 2b. no workspace yet: the un-split tree launch ------------------------------------------------------------------------------
+_CHILD = r"""
+import sys
+sys.path[:0] = [sys.argv[1], sys.argv[2]]
+import numpy as np, torch
+from _append_cases import host_pool, scattered_tables
+from _helpers import DevPools, dev
+from _tree_cases import expected_tree, words_from_parents
+from qserve_amd import append as A
+from qserve_backend import fused_attention as fa
+gpu = torch.device("cuda:0")
+H, Hkv, int4, B, past_len, n, BASE = 8, 2, True, 2, 200, 3, 1e4
+spt = Hkv * 64
+r = np.random.default_rng(6)
+W = (H + 2 * Hkv) * 128
+tables, nblocks = scattered_tables(r, B, 5)
+pools = DevPools(nblocks, Hkv, int4, gpu)
+kvp = pools.pointers(tables)
+ctx = dev(r.standard_normal((B * past_len, W)).astype(np.float16))
+cu = dev(np.array([0, past_len, 2 * past_len], np.int32))
+fa.apply_bias_rope_update_kv_cache(ctx, dev(np.array([past_len] * B, np.int32)), fa.compute_padding_offsets(cu, past_len, B * past_len), kvp,
+                                   H, Hkv, past_len, 64, spt, 128, BASE, 8192, True, int4, True)
+parents = [-1, 0, 0] * B                                  # a fork: node 2 must not see node 1
+cu_np, past_np = np.array([0, n, 2 * n], np.int32), np.array([past_len] * B, np.int32)
+masks = A.tree_masks_from_parents(parents, cu_np).to(gpu)
+qkv = dev(r.standard_normal((B * n, W)).astype(np.float16))
+cu_q, past = dev(cu_np), dev(past_np)
+A.append_tree_rope_update_kv_cache(qkv, cu_q, past, kvp, masks, H, Hkv, spt, BASE, int4)
+out = torch.zeros((B * n, H, 128), dtype=torch.float16, device=gpu)
+torch.cuda.synchronize()
+g = torch.cuda.CUDAGraph()
+with torch.cuda.graph(g):        # the FIRST split call of this process: no workspace yet, none may be allocated here
+    A.append_tree_attention(qkv, cu_q, past, kvp, masks, H, Hkv, spt, int4, max_seqlen_q=n, out=out, max_past=past_len, num_splits=3)
+g.replay()
+torch.cuda.synchronize()
+hp = host_pool(pools.k.cpu().numpy(), pools.v.cpu().numpy(), Hkv, int4)
+ref = expected_tree(qkv.cpu().numpy(), cu_np, past_np, tables, hp, H, Hkv, words_from_parents(parents[:n]) * B)
+err = float(np.abs(out.cpu().numpy().astype(np.float64) - ref).max())
+same = torch.equal(out, A.append_tree_attention(qkv, cu_q, past, kvp, masks, H, Hkv, spt, int4, max_seqlen_q=n))
+print(f"CHILD err={err:.3e} unsplit={int(same)}")
+"""
+
+
+def test_first_split_call_inside_a_capture_is_the_unsplit_tree_launch(gpu):
+    """tests/test_append_split_gpu.py's rule for this entry's own fall-back, in a fresh process (the workspace is allocated lazily, once
+    per process and device): B = 2, past 200 (4 pages), n = 3, a forking tree, 3 splits asked for."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-c", _CHILD, root, os.path.join(root, "tests")], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    line = [l for l in r.stdout.splitlines() if l.startswith("CHILD")][-1]
+    print(line)
+    err, same = float(line.split("err=")[1].split()[0]), line.endswith("unsplit=1")
+    assert err <= TOL, line
+    assert same, "a first split call inside a capture must be the un-split tree launch, bit for bit"
 
 
 # ---- 3. every mask bit ----------------------------------------------------------------------------------------------------------
