@@ -739,6 +739,52 @@ int qs_stop_update(const int32_t* history, int64_t hist_stride, int cap, const i
                    const int32_t* limit_lens, int32_t* finished, int batch, int n, int max_accept, int num_stops, int stop_width,
                    int check_root, qs_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Log-probabilities (no reference counterpart: its sampler layer computes them with torch ops on the host's schedule).  For every token
+ * one round - a decode step or a tree verification - emits: its log-probability, its rank and a short top list, from the round's fp16
+ * logit rows, on the device: capturable, nothing allocated, no workspace, nothing read back.  One entry covers a plain batch of rows
+ * (n = max_accept = 1, node_tokens = accept_idx = accept_lens = null: row b is scored for next_token[b]) and an accepted path.
+ *
+ * logits fp16 [batch * n, n_vocab] with row stride row_stride (elements).  node_tokens int64 [batch, n] or null; accept_idx int32
+ * [batch, max_accept] or null; accept_lens int32 [batch] or null; next_token int64 [batch]; lengths int32 [batch] or null.
+ *
+ * Slot (b, j), 1 <= j <= max_accept - the e_j of qs_stop_update, the row convention of qs_history_append, so after a clipping
+ * qs_stop_update the same arrays describe the clipped path:
+ *     m      = accept_lens[b] cut to 0 .. max_accept; accept_lens null: m = 1; node_tokens or accept_idx null: m is cut to 0 .. 1;
+ *     live   iff j <= m; a dead slot writes nothing;
+ *     row    = b * n + clamp(accept_idx[b, j-1], 0, n-1)        (accept_idx null: node 0) - the row whose head emitted the token;
+ *     id t   = node_tokens[b, clamp(accept_idx[b, j], 0, n-1)]  for j < m,      next_token[b]  for j == m;
+ *     column = L - 1 + j with L = max(lengths[b], 0) from BEFORE the round advances it - the token's text position -, or j - 1 where
+ *              lengths is null.  A column >= out_cols is skipped.
+ * Element (b, column) of out_lp (float) and out_rank (int32, may be null) lives at b * out_stride + column; the top lists out_top_ids
+ * (int32) / out_top_lp (float) at (b * out_stride + column) * top, `top` entries each, 0 <= top <= 32.
+ *
+ * Per live slot, with the row x[0 .. n_vocab), T = seq_temperature[b] (float [batch]) where given, else `temperature`; T < 1e-5 (or NaN)
+ * is taken as T = 1, so a greedy row reports the untempered distribution.  Top-k and top-p do not enter: the values describe
+ * softmax(x / T) of the logits as handed in (the penalised logits when the caller penalised first).
+ *     m = max x;  a_i = (x_i - m) * float(log2(e) / T) in fp32;  F_i = floor(exp2(a_i) * 2^40);  W = sum F_i, an exact 64-bit integer sum;
+ *     lp(i) = (a_i - (log2(float(W)) - 40)) * ln 2 in fp32                   (exp2 / log2: the hardware's, ~1 ulp each)
+ *     out_lp   = lp(t); t outside [0, n_vocab): NaN, and no address is formed from t; x_t = -inf: -inf.
+ *     out_rank = 1 + #{i : key(x_i) > key(x_t)} + #{i < t : key(x_i) == key(x_t)}, key = the order-preserving 16-bit key of the fp16 value
+ *                (-0 is +0); 0 when t is out of range.  An exact integer.
+ *     top list = the first `top` ids in the order (key descending, index ascending) with their lp; only ids whose logit is not -inf are
+ *                listed; if fewer than `top` exist, the tail is id -1 with lp -inf.  Ids are exact: no floating-point comparison decides
+ *                them, a tie class of any size is cut by index.
+ * Elements between n_vocab and the row stride are never read into a result.  Rows with NaN, +inf or no finite logit are the caller's
+ * error; the call still ends.  All sums are integer sums: bit-identical run to run and eager against graph replay; against the exact
+ * log-softmax |lp - exact| <= 1e-5 + 2^-21 * |lp|.
+ *
+ * QS_EINVAL before any device call: logits, next_token or out_lp null; n_vocab < 8 or > 2^22, row_stride < n_vocab or not a multiple of
+ * 8; n or max_accept outside 1 .. 64; top outside 0 .. 32; top > 0 without out_top_ids and out_top_lp; node_tokens null with n > 1;
+ * accept_idx null with max_accept > 1; out_cols < 0 or out_stride < out_cols; batch < 0 or > 65 535 (one grid row per sequence); logits
+ * not 16-byte, an int64 array not 8-byte, an int32 / float array not 4-byte aligned.  batch == 0: QS_OK, no launch.  One workgroup of
+ * 1024 threads per slot.
+ * ---------------------------------------------------------------------------------------------------------- */
+int qs_logprob_rows(const void* logits, int64_t row_stride, int n_vocab, const int64_t* node_tokens, const int32_t* accept_idx,
+                    const int32_t* accept_lens, const int64_t* next_token, const int32_t* lengths, int batch, int n, int max_accept,
+                    float temperature, const float* seq_temperature, int top, float* out_lp, int32_t* out_rank, int32_t* out_top_ids,
+                    float* out_top_lp, int64_t out_stride, int out_cols, qs_stream_t stream);
+
 /* Timing tool (scripts/trace_attn.py): device-to-device copy of the first `bytes` of the split-KV workspace, where the
  * trace instantiation of the KV4 decode attention (qs_set_attention_variant(232)) leaves its s_memtime stamps.
  * (A library built with -DQS_RING_TRACE additionally exports qs_debug_ring_trace(void* buf) for scripts/trace_gemm.py;

@@ -29,6 +29,7 @@ import qserve_backend.qgemm_w4a8_per_group as gemm_grp
 
 from . import drafting as draftingmod
 from . import fused as fusedmod
+from . import logprobs as logprobsmod
 from . import penalties as penaltiesmod
 from . import sampling as samplingmod
 from . import stopping as stoppingmod
@@ -302,6 +303,12 @@ class DecodeEngine:
         # the per-step k of step()
         self.stopping = None
         self.finished = self.limit_lens = self._stop_seqs = self._stop_lens = self._stop_k = None
+        # set_logprobs: (top, tempered) while the log-probability launch runs behind the heads; its persistent logs (created by the first
+        # call, re-created for another `top`): float32 [B, max_len], int32 [B, max_len], int32 / float32 [B, max_len, top]; where the
+        # generated text begins (the prompt length of the last prefill entry); what the captured step was captured with
+        self._logprobs = None
+        self.logprob_log = self.rank_log = self.top_ids_log = self.top_lp_log = None
+        self._text_start = self._graph_logprobs = self._graph_keep = None
 
     def _single_gpu(self, what):
         """What every entry behind the un-cut fp16 lm_head asks for (sampling, penalties, shared prefixes, tree verification, drafting):
@@ -506,9 +513,14 @@ class DecodeEngine:
                 self.lengths.fill_(prompt_len)                       # the first new token will hold position prompt_len
                 return self._step_keys()
 
-            self._head(self.final, self.tokens, keys if self.sampling is not None else None)
+            logits = self._head(self.final, self.tokens, keys if self.sampling is not None else None)
+            if self._logprobs is not None:                           # a new text: the first token's entry lands at column prompt_len
+                self._clear_logprob_logs()
+                self.lengths.fill_(prompt_len)
+                self._logprob_update(logits, self.tokens)
         self.lengths.fill_(prompt_len + 1)
         self._len_bound = prompt_len + 1
+        self._text_start = prompt_len
 
     def prefill(self, prompt_len, tokens=None):
         """Run the prompt through the model: per layer  norm+quant -> qkv GEMM -> apply_bias_rope_update_kv_cache
@@ -661,6 +673,7 @@ class DecodeEngine:
             return self._verify_tree_device(draft_tokens, par, sampled=sampled)
         assert self.penalties is None, "verify_tree: penalties (set_penalties) need device_walk=True - the host walk does not penalise"
         assert self.stopping is None, "verify_tree: stopping (set_stopping) needs device_walk=True - the host walk does not clip its path"
+        assert self._logprobs is None, "verify_tree: log-probabilities (set_logprobs) need device_walk=True - the host walk does not record them"
         max_past = int(self.lengths.max()) - 1
         assert max_past + n <= self.mb * 64, "verify_tree: the tree does not fit the sequences' page tables"
         _, toks, past, h, final, logits, am = self._verify_forward(draft_tokens, par, max_past, sampled)
@@ -760,6 +773,8 @@ class DecodeEngine:
         accept_idx, accept_lens, last, nxt = appendmod.accept_greedy(toks.view(-1), am, c["parents"], c["cu"], max_accept=n, out=out)
         if self.stopping is not None:                                       # clip the path at the first stop; a finished row accepts nothing
             self._stop_update(nxt, node_tokens=toks, accept_idx=accept_idx, accept_lens=accept_lens, last_row=last)
+        if self._logprobs is not None:                                      # the (clipped) path's rows, each scored for the token behind it
+            self._logprob_update(logits, nxt, node_tokens=toks, accept_idx=accept_idx, accept_lens=accept_lens)
         appendmod.commit_path_layers(c["layer_tables"], past, accept_idx, accept_lens, self.mb, self.Hkv, self.size_per_token, self.int4)
         self.hidden.copy_(torch.index_select(h, 0, last))
         self.final.copy_(torch.index_select(final, 0, last))
@@ -791,7 +806,7 @@ class DecodeEngine:
         g, res = self._capture(lambda: self._verify_tree_device(self._verify_draft, par, max_past=hint, out=out, sampled=sampled), n)
         # every tensor the graph touches and that was allocated outside the capture stays referenced as long as the graph does: the
         # four outputs of the walk (two of them are not part of the result) and the tree's constants (the cache may evict them)
-        self._verify_keep = (out, self._tree_constants(par), self.penalties, self.prompt_lens, self._stop_tensors())
+        self._verify_keep = (out, self._tree_constants(par), self.penalties, self.prompt_lens, self._stop_tensors(), self._logprob_tensors())
         self.verify_graph, self._verify_n, self._verify_result = g, n, res
         return g
 
@@ -940,25 +955,90 @@ class DecodeEngine:
         return stoppingmod.stop_update(self.history, self.lengths, next_token, self.finished, self._stop_seqs, self._stop_lens, self.limit_lens,
                                        self.prompt_lens, **path)
 
+    # ---- log-probabilities (qserve_amd.logprobs, csrc/logprob_rows.hip) ---------------------------------------------------------
+    def set_logprobs(self, top=0, tempered=False):
+        """Record, for every token the engine emits from now on, its log-probability, its rank and the `top` (0 .. 32) most likely ids
+        with their log-probabilities, on the device: one `logprobs.logprob_path` launch per round, behind the head - behind the stop
+        launch while set_stopping is on, so a clipped path records exactly what it emits and a frozen row records nothing - and in front
+        of the advance of the lengths: in step() (hence capture() / run()), between the stop launch and the commit of
+        verify_tree(device_walk=True) (hence capture_verify, speculate, capture_speculate) - there the kernel itself gathers the rows
+        on the accepted path and the token each is scored for -, and in the head of a prefill entry, whose token lands at column
+        prompt_len (a prefill entry also clears the logs: a new text begins).  The logs, indexed by text position like `history`:
+        `logprob_log` float32 [B, max_len] (NaN where nothing was recorded), `rank_log` int32 [B, max_len] (0), `top_ids_log` int32
+        [B, max_len, top] (-1) and `top_lp_log` float32 [B, max_len, top] (NaN); logprobs() reads them.  The values describe
+        softmax(logits / T) of the logits the head saw - penalised while set_penalties is on; top-k and top-p do not enter - with T = 1,
+        or with `tempered` the temperature of set_sampling (which must be on; < 1e-5, the greedy setting, counts as 1).
+        include/qserve_amd.h (`qs_logprob_rows`) has the arithmetic.
+
+        The call clears the logs.  They are persistent device tensors (re-created only for another `top`); whether the launch exists,
+        `top` and `tempered` are frozen into a capture - capture after switching; generate() re-captures by itself.
+        set_logprobs(None) switches it off: every path launches exactly what it launches without this call.  The host-walk
+        verify_tree(device_walk=False) refuses to run while it is on.  Single GPU, with the lm_head."""
+        if top is None:
+            self._logprobs = None
+            return
+        self._single_gpu("set_logprobs")
+        top = int(top)
+        assert 0 <= top <= logprobsmod.MAX_TOP, f"set_logprobs: top={top} (0 .. {logprobsmod.MAX_TOP})"
+        assert self.cfg["vocab"] >= 8 and self.cfg["vocab"] % 8 == 0, "set_logprobs: the logit rows need a vocabulary that is a multiple of 8"
+        assert not tempered or self.sampling is not None, "set_logprobs(tempered=True): set_sampling first (its temperature is the one used)"
+        if self.logprob_log is None or self.top_ids_log.size(2) != top:
+            self.logprob_log, self.rank_log, self.top_ids_log, self.top_lp_log = logprobsmod.new_logs(self.B, self.max_len, top, self.dev)
+        self._logprobs = (top, bool(tempered))
+        self._clear_logprob_logs()
+
+    def _clear_logprob_logs(self):
+        self.logprob_log.fill_(float("nan"))
+        self.rank_log.zero_()
+        self.top_ids_log.fill_(-1)
+        self.top_lp_log.fill_(float("nan"))
+
+    def _logprob_tensors(self):
+        """What a captured graph with the log-probability launch writes (None while set_logprobs is off)."""
+        return None if self._logprobs is None else (self.logprob_log, self.rank_log, self.top_ids_log, self.top_lp_log, self._samp_t)
+
+    def _logprob_update(self, logits, next_token, **path):
+        """The launch of set_logprobs on what a round is about to emit, at the lengths as they stand (not yet advanced)."""
+        top, tempered = self._logprobs
+        logprobsmod.logprob_path(logits, path.get("node_tokens"), path.get("accept_idx"), path.get("accept_lens"), next_token, self.lengths,
+                                 temperature=self._samp_t[:self.B] if tempered else 1.0, top=top,
+                                 out=(self.logprob_log, self.rank_log, self.top_ids_log, self.top_lp_log))
+
+    def logprobs(self):
+        """Read the logs of set_logprobs once -> per sequence a dict of lists over its generated text, positions prompt_len ..
+        lengths[b] - 1 - entry i belongs to token i of generate()'s texts, the first token of the prefill included (NaN / 0 where nothing
+        was recorded, e.g. for a prefill that ran before set_logprobs): "logprobs" floats, "ranks" ints, "top_ids" / "top_logprobs"
+        lists of `top` entries each."""
+        assert self.logprob_log is not None, "logprobs: set_logprobs first"
+        assert self._text_start is not None, "logprobs: after a prefill entry (it says where the generated text begins)"
+        lens = self.lengths.cpu().tolist()
+        lp, rank, ids, tlp = (t.cpu() for t in (self.logprob_log, self.rank_log, self.top_ids_log, self.top_lp_log))
+        P, res = self._text_start, []
+        for b in range(self.B):
+            end = min(lens[b], self.max_len)
+            res.append(dict(logprobs=lp[b, P:end].tolist(), ranks=rank[b, P:end].tolist(), top_ids=ids[b, P:end].tolist(),
+                            top_logprobs=tlp[b, P:end].tolist()))
+        return res
+
     def generate(self, max_rounds, parents=None, poll_every=8, sampled=False):
         """Decode until every sequence has finished (after set_stopping), with the host looking at the device once per burst: replay
         the captured step graph - or, with `parents`, the captured speculate graph of that tree - `poll_every` times, then read
         (`finished`, `lengths`) back in one copy; that is the only host <-> device traffic of the loop.  `_len_bound` is set from it.
         Ends when no sequence is live, when `max_rounds` rounds are done, or when another round would not fit the page tables by the
-        bound (a burst is shortened to what fits).  A graph that does not exist yet, or that was captured without the stop launch (for
-        speculation also: of another tree or head), is captured first - the warm-up of capture() / capture_speculate() is a real round
+        bound (a burst is shortened to what fits).  A graph that does not exist yet, or that was captured without the stop launch or with
+        another state of set_logprobs (for speculation also: of another tree or head), is captured first - the warm-up of capture() / capture_speculate() is a real round
         that is not counted.
         -> (texts: per sequence the list of generated tokens history[b, prompt_lens[b] : lengths[b]], the first token of the prefill
         included; reasons: `finished` as a list; rounds; read_backs) - the texts are read once, after the loop."""
         assert self.stopping is not None, "generate: set_stopping first (nothing else ends the loop)"
         assert max_rounds >= 0 and poll_every >= 1
         if parents is None:
-            if self.graph is None or not self._graph_stops:
+            if self.graph is None or not self._graph_stops or self._graph_logprobs != self._logprobs:
                 self.capture(piecewise=False)
             advance, run = 1, self.run
         else:
             par = self._tree_arg(parents, "generate")
-            if self.speculate_graph is None or self._speculate_tree != (tuple(par), bool(sampled), True):
+            if self.speculate_graph is None or self._speculate_tree != (tuple(par), bool(sampled), True, self._logprobs):
                 self.capture_speculate(par, sampled=sampled)
             advance, run = len(par), self.run_speculate
         rounds = reads = 0
@@ -1038,10 +1118,10 @@ class DecodeEngine:
         # every tensor the graph touches and that was allocated outside the capture stays referenced as long as the graph does: the
         # draft buffer, the four outputs of the walk, the tree's constants (the cache may evict them), step()'s record constants
         self._speculate_keep = (draft, out, self._tree_constants(par), self._step_record, self.history, self.penalties, self.prompt_lens,
-                                self._stop_tensors())
+                                self._stop_tensors(), self._logprob_tensors())
         self.speculate_graph, self._speculate_n, self._speculate_result = g, n, res
         # (generate: is the captured round the one it was asked for - this tree, this head, the stop launch in it?)
-        self._speculate_tree = (tuple(par), bool(sampled), self.stopping is not None)
+        self._speculate_tree = (tuple(par), bool(sampled), self.stopping is not None, self._logprobs)
         return g
 
     def run_speculate(self):
@@ -1070,12 +1150,16 @@ class DecodeEngine:
             yield self._head_local()                                 # candidates of the ranks meet in the sum all-reduce
             self._head_finish(self.head_cand_res)
         elif self.with_lm_head:                                      # (penalty context: history[b, :lengths[b]], the text so far)
-            self._head(self.final, self.tokens, self._step_keys if self.sampling is not None else None)
+            logits = self._head(self.final, self.tokens, self._step_keys if self.sampling is not None else None)
         if self.stopping is not None:                                # set_stopping: k = 0 (a stop before the new token, or a frozen row) / 1
             k = self._stop_update(self.tokens, out_lens=self._stop_k)
+            if self._logprobs is not None:                           # set_logprobs: the new token's entry; a row with k = 0 writes none
+                self._logprob_update(logits, self.tokens, accept_lens=k)
             self.lengths.add_(k)
             self._record_step(k)
             return
+        if self._logprobs is not None:
+            self._logprob_update(logits, self.tokens)
         self.lengths.add_(1)
         if self.history is not None:                                 # enable_drafting: the new token joins the text
             self._record_step()
@@ -1163,6 +1247,7 @@ class DecodeEngine:
         if not piecewise:
             self.graph, _ = self._capture(self.step, 1)
             self._graph_stops = self.stopping is not None    # (generate: does the captured step hold the stop launch?)
+            self._graph_logprobs, self._graph_keep = self._logprobs, self._logprob_tensors()   # (... and the log-probability launch?)
             return self.graph
         self._warm_up(self.step)
         pool = torch.cuda.graph_pool_handle()
