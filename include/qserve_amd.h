@@ -785,6 +785,61 @@ int qs_logprob_rows(const void* logits, int64_t row_stride, int n_vocab, const i
                     float temperature, const float* seq_temperature, int top, float* out_lp, int32_t* out_rank, int32_t* out_top_ids,
                     float* out_top_lp, int64_t out_stride, int out_cols, qs_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Constrained decoding (no reference counterpart): a TOKEN AUTOMATON restricts what every sequence may emit - a regular expression, a
+ * choice list, a JSON shape of bounded depth, compiled on the host into two device tables - and the three entries below apply it inside
+ * the decode round, on the device: capturable, nothing allocated, nothing read back, no scratch.  Integer rules only: bit-identical run
+ * to run and eager against graph replay.
+ *
+ * Tables, shared by all sequences of a call (several grammars live in one table as disjoint state ranges):
+ *     token_class int16 [n_vocab]   the class of every token id, in 0 .. C-1; a negative class, or one >= C: never allowed in any state.
+ *     next        int32 [S, C], row stride next_stride >= C (elements).  next[s, c] >= 0: the state after a token of class c in state s;
+ *                 a negative entry: not allowed in s.  A token t is allowed in s iff next[s, token_class[t]] >= 0.
+ * A STATE outside 0 .. S-1, negative or not, is UNCONSTRAINED: -1 by convention, and QS_FSM_DEAD (-2), what a transition over a token
+ * that is not allowed yields.
+ *     T(st, t) = st                                  if st is outside 0 .. S-1   (unconstrained stays unconstrained, dead stays dead)
+ *              = QS_FSM_DEAD                         if t is outside [0, n_vocab), or c = token_class[t] is outside [0, C), or next[st, c] < 0
+ *              = next[st, c]                         otherwise.
+ * No address is ever formed from an out-of-range token, class or state.
+ *
+ * qs_constrain_node_states: the state of every node of a draft tree - the state reached along the path root -> node.  state int32
+ * [batch]; node_tokens int64 [batch, n] (column 0, the root's, is not read); parents int32 [n] (ONE tree shape, as for the drafter;
+ * both may be null when n == 1); node_state int32 [batch, n], written:
+ *     node_state[b, 0] = state[b];      node_state[b, i] = T(node_state[b, a], node_tokens[b, i])  for i >= 1, a = parents[i].
+ * A parent entry not in 0 .. i-1 hangs the node off the root (a = 0), the convention of qs_ngram_draft_tree / qs_penalize_rows; its
+ * children follow the rule through it.  A dead node only says "this node cannot be accepted": its parent's row, masked, never yields
+ * its token.  One wave64 per sequence.
+ *
+ * qs_constrain_rows: the mask.  logits fp16 [rows, n_vocab] with row stride row_stride (elements), edited IN PLACE; row_state int32
+ * [rows] - node_state flattened for a verification, state itself for a plain step.  For every row r with s = row_state[r] in 0 .. S-1:
+ *     logits[r, t] = -inf (bits 0xFC00) for every t in [0, n_vocab) whose class is outside [0, C) or has next[s, class] < 0;
+ * every other element keeps its bits, and so does the padding between n_vocab and the row stride.  A row whose state is outside
+ * 0 .. S-1 is NOT WRITTEN at all (nor read).  One workgroup of 512 threads per (row, slice of the vocabulary); the allowed set of the
+ * row's state is staged in LDS as one bit per class.
+ *
+ * qs_constrain_advance: the state after the round, behind the walk (and behind qs_stop_update where present), on the arrays of
+ * qs_history_append.  node_state int32 [batch, n] or null; accept_idx int32 [batch, max_accept] or null; accept_lens int32 [batch] or
+ * null; next_token int64 [batch]; state int32 [batch], in and out:
+ *     k  = accept_lens[b] cut to 0 .. max_accept; accept_lens null: k = 1.    k == 0 (a frozen row, a path clipped to nothing): not written.
+ *     st = node_state[b, clamp(accept_idx[b, k-1], 0, n-1)];  node_state or accept_idx null: st = state[b].
+ *     st outside 0 .. S-1: state[b] is not written;  else state[b] = T(st, next_token[b]).
+ * st is the state of the row that emitted e_k, and after a clipping qs_stop_update next_token[b] IS e_k.  One thread per sequence.
+ *
+ * QS_EINVAL before any device call: a null required pointer (state, token_class, next; node_state / logits, row_state / next_token);
+ * n_vocab < 8 or > 2^22; row_stride < n_vocab or not a multiple of 8; C outside 1 .. 32 768; S < 1; next_stride < C; n or max_accept
+ * outside 1 .. 64; node_tokens or parents null with n > 1; accept_idx null with max_accept > 1; batch / rows < 0 or > 2^24; logits or
+ * token_class not 16-byte, an int64 array not 8-byte, an int32 array not 4-byte aligned.  batch == 0 / rows == 0: QS_OK, no launch.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define QS_FSM_DEAD (-2)
+int qs_constrain_node_states(const int32_t* state, const int64_t* node_tokens, const int32_t* parents, const int16_t* token_class,
+                             int n_vocab, const int32_t* next, int64_t next_stride, int S, int C, int batch, int n,
+                             int32_t* node_state, qs_stream_t stream);
+int qs_constrain_rows(void* logits, int64_t row_stride, int n_vocab, const int32_t* row_state, const int16_t* token_class,
+                      const int32_t* next, int64_t next_stride, int S, int C, int rows, qs_stream_t stream);
+int qs_constrain_advance(int32_t* state, const int32_t* node_state, const int32_t* accept_idx, const int32_t* accept_lens,
+                         const int64_t* next_token, const int16_t* token_class, int n_vocab, const int32_t* next, int64_t next_stride,
+                         int S, int C, int batch, int n, int max_accept, qs_stream_t stream);
+
 /* Timing tool (scripts/trace_attn.py): device-to-device copy of the first `bytes` of the split-KV workspace, where the
  * trace instantiation of the KV4 decode attention (qs_set_attention_variant(232)) leaves its s_memtime stamps.
  * (A library built with -DQS_RING_TRACE additionally exports qs_debug_ring_trace(void* buf) for scripts/trace_gemm.py;

@@ -92,6 +92,9 @@ SIGNATURES = {
     "qs_ngram_draft_lds_tokens": (_i, []),
     "qs_stop_update": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "qs_logprob_rows": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _i, _vp, _vp, _vp, _vp, _i64, _i, _vp]),
+    "qs_constrain_node_states": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i64, _i, _i, _i, _i, _vp, _vp]),
+    "qs_constrain_rows": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _i64, _i, _i, _i, _vp]),
+    "qs_constrain_advance": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
 }
 
 

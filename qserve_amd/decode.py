@@ -27,6 +27,7 @@ import qserve_backend.layernorm_ops as layernorm_ops
 import qserve_backend.qgemm_w4a8_per_chn as gemm_chn
 import qserve_backend.qgemm_w4a8_per_group as gemm_grp
 
+from . import constraints as constraintsmod
 from . import drafting as draftingmod
 from . import fused as fusedmod
 from . import logprobs as logprobsmod
@@ -309,6 +310,10 @@ class DecodeEngine:
         self._logprobs = None
         self.logprob_log = self.rank_log = self.top_ids_log = self.top_lp_log = None
         self._text_start = self._graph_logprobs = self._graph_keep = None
+        # set_constraint: the device tables (token_class, next) while the heads mask - the SAME tuple as long as the same automaton is
+        # on, so a capture can tell whether it was made with it -, the TokenDFA they came from, the state of every sequence int32 [B],
+        # the states of a verification's nodes int32 [B * MAX_TREE]; what the captured step / round was captured with
+        self._fsm = self._fsm_src = self._fsm_kept = self.fsm_state = self._fsm_node_state = self._graph_fsm = self._speculate_fsm = None
 
     def _single_gpu(self, what):
         """What every entry behind the un-cut fp16 lm_head asks for (sampling, penalties, shared prefixes, tree verification, drafting):
@@ -356,10 +361,14 @@ class DecodeEngine:
         (llama_w4a8_unpad.py:392,476), the penalty launch while set_penalties is on (`draft`: the drafted tokens and the tree of a
         verification; a step's context is the text alone; the prefill entries and the host-walk verify_tree refuse to run while penalties
         are on, so their heads never penalise), then out[r] = the arg-max of row r or, with `keys`, the token drawn under the
-        Philox keys keys() - computed behind the logits, from the lengths as they stand then.  -> the logits (penalised, while on)."""
+        Philox keys keys() - computed behind the logits, from the lengths as they stand then.  While set_constraint is on the mask
+        launch runs behind the penalties: every row under the automaton state of its own node - `fsm_state` for a step and for the
+        prompt head, the states along the draft's paths for a verification.  -> the logits (penalised and masked, while on)."""
         logits = torch.matmul(final, self.lm_head.t())
         if self.penalties is not None:
             self._penalize(logits, *draft)
+        if self._fsm is not None:
+            self._constrain(logits, *draft)
         if keys is not None:
             self._sample(logits, out, keys())
         else:
@@ -518,6 +527,8 @@ class DecodeEngine:
                 self._clear_logprob_logs()
                 self.lengths.fill_(prompt_len)
                 self._logprob_update(logits, self.tokens)
+            if self._fsm is not None:                                # the first token was drawn under the start states: move over it
+                self._fsm_advance(self.tokens)
         self.lengths.fill_(prompt_len + 1)
         self._len_bound = prompt_len + 1
         self._text_start = prompt_len
@@ -674,6 +685,7 @@ class DecodeEngine:
         assert self.penalties is None, "verify_tree: penalties (set_penalties) need device_walk=True - the host walk does not penalise"
         assert self.stopping is None, "verify_tree: stopping (set_stopping) needs device_walk=True - the host walk does not clip its path"
         assert self._logprobs is None, "verify_tree: log-probabilities (set_logprobs) need device_walk=True - the host walk does not record them"
+        assert self._fsm is None, "verify_tree: a constraint (set_constraint) needs device_walk=True - the host walk does not advance its states"
         max_past = int(self.lengths.max()) - 1
         assert max_past + n <= self.mb * 64, "verify_tree: the tree does not fit the sequences' page tables"
         _, toks, past, h, final, logits, am = self._verify_forward(draft_tokens, par, max_past, sampled)
@@ -775,13 +787,15 @@ class DecodeEngine:
             self._stop_update(nxt, node_tokens=toks, accept_idx=accept_idx, accept_lens=accept_lens, last_row=last)
         if self._logprobs is not None:                                      # the (clipped) path's rows, each scored for the token behind it
             self._logprob_update(logits, nxt, node_tokens=toks, accept_idx=accept_idx, accept_lens=accept_lens)
+        if self._fsm is not None:                                           # the state of the (clipped) path's last row, over the token it emitted
+            self._fsm_advance(nxt, node_state=self._fsm_node_state[:B * n].view(B, n), accept_idx=accept_idx, accept_lens=accept_lens)
         appendmod.commit_path_layers(c["layer_tables"], past, accept_idx, accept_lens, self.mb, self.Hkv, self.size_per_token, self.int4)
         self.hidden.copy_(torch.index_select(h, 0, last))
         self.final.copy_(torch.index_select(final, 0, last))
         self.tokens.copy_(nxt)                                              # in place: captured graphs read these tensors
         self.lengths.add_(accept_lens)
         self._len_bound += n
-        self.last_verify_logits = logits.view(B, n, -1)                     # (penalised, while set_penalties is on)
+        self.last_verify_logits = logits.view(B, n, -1)                     # (penalised / masked, while set_penalties / set_constraint is on)
         return accept_idx, accept_lens, am.view(B, n)
 
     def _walk_outputs(self, n):
@@ -806,7 +820,8 @@ class DecodeEngine:
         g, res = self._capture(lambda: self._verify_tree_device(self._verify_draft, par, max_past=hint, out=out, sampled=sampled), n)
         # every tensor the graph touches and that was allocated outside the capture stays referenced as long as the graph does: the
         # four outputs of the walk (two of them are not part of the result) and the tree's constants (the cache may evict them)
-        self._verify_keep = (out, self._tree_constants(par), self.penalties, self.prompt_lens, self._stop_tensors(), self._logprob_tensors())
+        self._verify_keep = (out, self._tree_constants(par), self.penalties, self.prompt_lens, self._stop_tensors(), self._logprob_tensors(),
+                             self._fsm_tensors())
         self.verify_graph, self._verify_n, self._verify_result = g, n, res
         return g
 
@@ -1020,25 +1035,93 @@ class DecodeEngine:
                             top_logprobs=tlp[b, P:end].tolist()))
         return res
 
+    # ---- constrained decoding (qserve_amd.constraints, csrc/constrain_rows.hip) ---------------------------------------------------
+    def set_constraint(self, dfa, start_states=0):
+        """Restrict what every sequence may emit to the language of a token automaton (`constraints.TokenDFA`, on the host or on the
+        device), on the device: `fsm_state` int32 [B] holds the automaton state of every sequence - `start_states` now: an int, or one per
+        sequence, -1 for a sequence that stays unconstrained (several grammars in one batch: `TokenDFA.union` and its offsets).  From
+        then on every head masks its rows in place, behind the penalty launch and in front of the arg-max / the sampler
+        (`constraints.constrain_rows`: -inf wherever the row's state does not allow the token): step() (hence capture() / run()) and the
+        head of a prefill entry under `fsm_state`, verify_tree(device_walk=True) (hence capture_verify, speculate, capture_speculate)
+        every row under the state of its own node, the state reached along the path root -> node (`constraints.node_states`, launched
+        just before).  A child is accepted only if it holds the token its parent's masked row produced, so greedy and sampled
+        speculation stay lossless: the generated tokens are those of constrained step()s, whatever was drafted.  `constraints.advance`
+        then moves `fsm_state` over what the round emitted: behind the head in step() and in a prefill entry, behind the walk and the
+        stop launch (with its clipped k) and in front of the commit in a verification; a frozen row keeps its state.  The logits a head
+        returns, `last_verify_logits` and what set_logprobs scores are the MASKED ones.
+
+        A state the automaton has no way out of for the token emitted becomes constraints.DEAD (-2) - it cannot happen through the
+        engine's own heads unless a state allows no token at all - and a dead or negative state is unconstrained.  Unlike penalties and
+        stopping the constraint needs no `history`: the prefill entries run while it is on, mask the first token with the start states
+        and advance once - so call set_constraint (again) BEFORE every prefill: `fsm_state` is where the last text left it.
+
+        `fsm_state` and the node states live in persistent device tensors; `fsm_state` is filled in place, so a captured graph sees new
+        start states.  The tables, and whether the launches exist at all, are frozen into a capture - capture after switching;
+        generate() re-captures by itself.  Calling it again with the SAME TokenDFA object keeps the tables (and every capture made with
+        them) and only refills the states - also across a set_constraint(None) in between: the uploaded tables of the last automaton are
+        kept, and a capture made with them is used again unless the graph was captured anew while the constraint was off.
+        set_constraint(None) switches it off: every path launches exactly what it launches without this call.  The host-walk verify_tree(device_walk=False) refuses to run while it is on.  Single GPU, with the lm_head; the
+        vocabulary must be a multiple of 8 and equal dfa.token_class.numel()."""
+        if dfa is None:
+            self._fsm = None                                 # (the uploaded tables stay in _fsm_kept, for the same object's return)
+            return
+        self._single_gpu("set_constraint")
+        from .append import MAX_TREE
+        B, V = self.B, self.cfg["vocab"]
+        assert isinstance(dfa, constraintsmod.TokenDFA), "set_constraint: a constraints.TokenDFA (or None)"
+        assert V >= 8 and V % 8 == 0, "set_constraint: the logit rows need a vocabulary that is a multiple of 8"
+        assert dfa.V == V, f"set_constraint: the automaton names {dfa.V} tokens, the vocabulary has {V}"
+        start_states = torch.as_tensor(start_states, device="cpu")          # (a Python or numpy integer, a sequence, an array, a tensor)
+        assert start_states.dim() <= 1 and not start_states.is_floating_point() and start_states.dtype != torch.bool, \
+            f"set_constraint: start_states is one int, or one int per sequence ({B}), got {start_states.dtype} {tuple(start_states.shape)}"
+        starts = [int(start_states)] * B if start_states.dim() == 0 else [int(v) for v in start_states]
+        assert len(starts) == B, f"set_constraint: start_states is one int, or one per sequence ({B})"
+        if self.fsm_state is None:
+            self.fsm_state = torch.full((B,), -1, dtype=torch.int32, device=self.dev)
+            self._fsm_node_state = torch.full((B * MAX_TREE,), -1, dtype=torch.int32, device=self.dev)
+        self.fsm_state.copy_(torch.tensor(starts, dtype=torch.int32))
+        if self._fsm_src is not dfa:
+            d = dfa.to(self.dev)
+            self._fsm_kept, self._fsm_src = (d.token_class, d.next), dfa
+        self._fsm = self._fsm_kept
+
+    def _fsm_tensors(self):
+        """What a captured graph with the constraint launches reads and writes (None while set_constraint is off)."""
+        return None if self._fsm is None else (self._fsm, self.fsm_state, self._fsm_node_state)
+
+    def _constrain(self, logits, node_tokens=None, tree=None):
+        """The mask launch in front of a head: `logits` [B * n, V] in place, the rows of a draft under their nodes' states."""
+        token_class, nxt = self._fsm
+        states = self.fsm_state
+        if node_tokens is not None:
+            states = self._fsm_node_state[:node_tokens.numel()]
+            constraintsmod.node_states(self.fsm_state, node_tokens, tree, token_class, nxt, out=states)
+        constraintsmod.constrain_rows(logits, states, token_class, nxt)
+
+    def _fsm_advance(self, next_token, **path):
+        """The launch that moves `fsm_state` over what a round emitted."""
+        constraintsmod.advance(self.fsm_state, next_token, *self._fsm, **path)
+
     def generate(self, max_rounds, parents=None, poll_every=8, sampled=False):
         """Decode until every sequence has finished (after set_stopping), with the host looking at the device once per burst: replay
         the captured step graph - or, with `parents`, the captured speculate graph of that tree - `poll_every` times, then read
         (`finished`, `lengths`) back in one copy; that is the only host <-> device traffic of the loop.  `_len_bound` is set from it.
         Ends when no sequence is live, when `max_rounds` rounds are done, or when another round would not fit the page tables by the
         bound (a burst is shortened to what fits).  A graph that does not exist yet, or that was captured without the stop launch or with
-        another state of set_logprobs (for speculation also: of another tree or head), is captured first - the warm-up of capture() / capture_speculate() is a real round
+        another state of set_logprobs or set_constraint (for speculation also: of another tree or head), is captured first - the warm-up of capture() / capture_speculate() is a real round
         that is not counted.
         -> (texts: per sequence the list of generated tokens history[b, prompt_lens[b] : lengths[b]], the first token of the prefill
         included; reasons: `finished` as a list; rounds; read_backs) - the texts are read once, after the loop."""
         assert self.stopping is not None, "generate: set_stopping first (nothing else ends the loop)"
         assert max_rounds >= 0 and poll_every >= 1
         if parents is None:
-            if self.graph is None or not self._graph_stops or self._graph_logprobs != self._logprobs:
+            if self.graph is None or not self._graph_stops or self._graph_logprobs != self._logprobs or self._graph_fsm is not self._fsm:
                 self.capture(piecewise=False)
             advance, run = 1, self.run
         else:
             par = self._tree_arg(parents, "generate")
-            if self.speculate_graph is None or self._speculate_tree != (tuple(par), bool(sampled), True, self._logprobs):
+            if self.speculate_graph is None or self._speculate_tree != (tuple(par), bool(sampled), True, self._logprobs) or \
+                    self._speculate_fsm is not self._fsm:
                 self.capture_speculate(par, sampled=sampled)
             advance, run = len(par), self.run_speculate
         rounds = reads = 0
@@ -1118,8 +1201,9 @@ class DecodeEngine:
         # every tensor the graph touches and that was allocated outside the capture stays referenced as long as the graph does: the
         # draft buffer, the four outputs of the walk, the tree's constants (the cache may evict them), step()'s record constants
         self._speculate_keep = (draft, out, self._tree_constants(par), self._step_record, self.history, self.penalties, self.prompt_lens,
-                                self._stop_tensors(), self._logprob_tensors())
+                                self._stop_tensors(), self._logprob_tensors(), self._fsm_tensors())
         self.speculate_graph, self._speculate_n, self._speculate_result = g, n, res
+        self._speculate_fsm = self._fsm                                     # (... and the automaton it masks with?)
         # (generate: is the captured round the one it was asked for - this tree, this head, the stop launch in it?)
         self._speculate_tree = (tuple(par), bool(sampled), self.stopping is not None, self._logprobs)
         return g
@@ -1155,11 +1239,15 @@ class DecodeEngine:
             k = self._stop_update(self.tokens, out_lens=self._stop_k)
             if self._logprobs is not None:                           # set_logprobs: the new token's entry; a row with k = 0 writes none
                 self._logprob_update(logits, self.tokens, accept_lens=k)
+            if self._fsm is not None:                                # set_constraint: a row with k = 0 keeps its state
+                self._fsm_advance(self.tokens, accept_lens=k)
             self.lengths.add_(k)
             self._record_step(k)
             return
         if self._logprobs is not None:
             self._logprob_update(logits, self.tokens)
+        if self._fsm is not None:
+            self._fsm_advance(self.tokens)
         self.lengths.add_(1)
         if self.history is not None:                                 # enable_drafting: the new token joins the text
             self._record_step()
@@ -1247,7 +1335,8 @@ class DecodeEngine:
         if not piecewise:
             self.graph, _ = self._capture(self.step, 1)
             self._graph_stops = self.stopping is not None    # (generate: does the captured step hold the stop launch?)
-            self._graph_logprobs, self._graph_keep = self._logprobs, self._logprob_tensors()   # (... and the log-probability launch?)
+            self._graph_logprobs, self._graph_keep = self._logprobs, (self._logprob_tensors(), self._fsm_tensors())   # (... and the log-probability launch?)
+            self._graph_fsm = self._fsm                      # (... and the automaton it masks with?)
             return self.graph
         self._warm_up(self.step)
         pool = torch.cuda.graph_pool_handle()
