@@ -840,6 +840,36 @@ int qs_constrain_advance(int32_t* state, const int32_t* node_state, const int32_
                          const int64_t* next_token, const int16_t* token_class, int n_vocab, const int32_t* next, int64_t next_stride,
                          int S, int C, int batch, int n, int max_accept, qs_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * LoRA adapters next to the W4A8 linears (no reference counterpart): every SEQUENCE of a batch runs under its own low-rank adapter, or
+ * under none.  A delta cannot be merged into 4-bit packed weights, so it is applied behind the base GEMM, per row, on the quantised
+ * activations that GEMM read.  Rows are sequence-major with rows_per_seq rows per sequence (1 for a decode step, the chunk, the prompt
+ * length, a tree's node count).  qs_lora_rows updates the fp16 output of the base linear IN PLACE: for row t of T, s = t / rows_per_seq,
+ * a = seq_adapter[s] (int32, on the device).  a outside 0 .. slots-1 (-1 by convention: the base model): nothing of the row is read
+ * or written, and no address is formed from a.  Otherwise, for every column n, g the segment n lies in:
+ *     t_j       = float(x_scale[t]) * sum_k float(A[a, g r + j, k]) * x[t, k]            j = 0 .. r-1, float32, kept in float32
+ *     out[t, n] = fp16(float(out[t, n]) + scaling[a] * sum_j float(B[a, n, j]) * t_j)
+ * x int8 [T, K], row stride x_stride; x_scale fp16 [T]; A fp16 [slots, nseg r, K]; B fp16 [slots, N, r]; scaling float32 [slots];
+ * out fp16 [T, N], row stride out_stride (elements).  The N columns are cut into nseg (1 .. 3) SEGMENTS by their ascending ends
+ * seg_end0 .. seg_end{nseg-1} (the last one is N; the others are ignored) - q / k / v of a fused qkv, gate / up - and every segment has
+ * its own r rows of A: a fused projection reads r columns of B per output, not nseg r columns of a block-diagonal matrix.
+ * The float32 sums are taken in a fixed order (products of fp16 and int8 values are exact in float32): results are bit-identical run
+ * to run and eager against graph replay; against another order of the sums, |got - y| <= 2^-11 |y| + 2^-24 + 2 (K + r + 4) 2^-24 M with
+ * M = scaling sum_j |B| x_scale sum_k |A x|.  Two launches on `stream` (capturable): the float32 partial sums of the K slices travel
+ * through `workspace` (workspace_size bytes, at least qs_lora_rows_workspace(T, K, r, nseg); not shared with a launch that may overlap).
+ * No atomics, no in-launch waits.
+ *
+ * QS_EINVAL before any device call: a null pointer; r not 8, 16, 32 or 64; K not a multiple of 128 in 128 .. 2^20; N not a multiple of
+ * 64 in 64 .. 2^22; nseg outside 1 .. 3; segment ends not ascending multiples of 64 or the last one not N; slots < 1; T < 0 or > 2^24;
+ * rows_per_seq < 1 or not a divisor of T; x_stride < K or not a multiple of 16; out_stride < N or not a multiple of 8; out, x, A, B or
+ * the workspace not 16-byte, scaling or seq_adapter not 4-byte, x_scale not 2-byte aligned; a workspace that is too small.  T == 0:
+ * QS_OK, no launch.  qs_lora_rows_workspace: the bytes, or QS_EINVAL for a T, K, r or nseg outside those ranges.
+ * ---------------------------------------------------------------------------------------------------------- */
+int64_t qs_lora_rows_workspace(int T, int K, int r, int nseg);
+int qs_lora_rows(void* out, int64_t out_stride, const int8_t* x, int64_t x_stride, const void* x_scale, const void* A, const void* B,
+                 const float* scaling, const int32_t* seq_adapter, int slots, int T, int K, int N, int r, int rows_per_seq, int nseg,
+                 int seg_end0, int seg_end1, int seg_end2, void* workspace, int64_t workspace_size, qs_stream_t stream);
+
 /* Timing tool (scripts/trace_attn.py): device-to-device copy of the first `bytes` of the split-KV workspace, where the
  * trace instantiation of the KV4 decode attention (qs_set_attention_variant(232)) leaves its s_memtime stamps.
  * (A library built with -DQS_RING_TRACE additionally exports qs_debug_ring_trace(void* buf) for scripts/trace_gemm.py;

@@ -95,6 +95,8 @@ SIGNATURES = {
     "qs_constrain_node_states": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i64, _i, _i, _i, _i, _vp, _vp]),
     "qs_constrain_rows": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _i64, _i, _i, _i, _vp]),
     "qs_constrain_advance": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
+    "qs_lora_rows_workspace": (_i64, [_i, _i, _i, _i]),
+    "qs_lora_rows": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp]),
 }
 
 

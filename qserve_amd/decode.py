@@ -31,6 +31,7 @@ from . import constraints as constraintsmod
 from . import drafting as draftingmod
 from . import fused as fusedmod
 from . import logprobs as logprobsmod
+from . import lora as loramod
 from . import penalties as penaltiesmod
 from . import sampling as samplingmod
 from . import stopping as stoppingmod
@@ -314,6 +315,11 @@ class DecodeEngine:
         # on, so a capture can tell whether it was made with it -, the TokenDFA they came from, the state of every sequence int32 [B],
         # the states of a verification's nodes int32 [B * MAX_TREE]; what the captured step / round was captured with
         self._fsm = self._fsm_src = self._fsm_kept = self.fsm_state = self._fsm_node_state = self._graph_fsm = self._speculate_fsm = None
+        # enable_lora: the adapter table (lora.LoraTable) and the adapter of every sequence int32 [B] (-1: the base model), filled in
+        # place; set_lora: True while lora_rows runs behind the four linears of every layer; the step's workspace; what the captured
+        # step / verification / round was captured with
+        self.lora_table = self.lora_ids = self._lora_step_ws = None
+        self._lora = self._graph_lora = self._verify_lora = self._speculate_lora = False
 
     def _single_gpu(self, what):
         """What every entry behind the un-cut fp16 lm_head asks for (sampling, penalties, shared prefixes, tree verification, drafting):
@@ -424,6 +430,15 @@ class DecodeEngine:
         qa, qo, q_mlp, q_scale, q_sum, qkv, proj, proj_res, gate_up, mlp_act = (
             bufs[k] for k in ("qa", "qo", "q_mlp", "q_scale", "q_sum", "qkv", "proj", "proj_res", "gate_up", "mlp_act"))
         sums = q_sum if fuse_sum else None
+        # set_lora: lora_rows behind every base GEMM (and its bias), on that GEMM's quantised input.  A linear with an adapter takes the
+        # path a linear with a bias takes: no planes form, no silu * mul epilogue - the delta has to be added in between
+        lora = self._lora_plan(h.size(0)) if self._lora else None
+
+        def lora_add(li, name, out, xq):
+            if lora is not None:
+                A, B = self.lora_table.layers[li][name]
+                loramod.lora_rows(out, xq, q_scale, A, B, self.lora_table.scaling, self.lora_ids, lora[0], self.lora_table.shapes[name][2],
+                                  workspace=lora[1])
 
         def norm_quant(x, w):
             if fuse_sum:
@@ -442,17 +457,18 @@ class DecodeEngine:
         # kernel that follows sums them and applies the GEMM's epilogue (bit-identical pair fusion; single GPU only - under
         # tensor parallelism the all-reduce sits between the two)
         def proj_add_norm_quant(lin, name, xq, x, w):
-            pl = planes.get(name) if fuse and self.tp_world == 1 else None
+            pl = planes.get(name) if fuse and self.tp_world == 1 and lora is None else None
             if pl is not None:
                 lin.planes(xq, pl)
                 lin.add_norm_quant_planes(qa, x, pl, q_scale, q_sum, w, q_scale, eps, sums)
                 return True
             return False
 
-        def row_parallel(lin, xq):
+        def row_parallel(li, name, lin, xq):
             """lin(xq) -> the rows to add to h: the projection's output or, under tensor parallelism, its sum over the ranks."""
             lin(xq, q_scale, q_sum, proj)
             if self.tp_world == 1:
+                lora_add(li, name, proj, xq)                         # (set_lora is single GPU)
                 return proj
             yield proj
             if lin.defer_bias and lin.bias is not None:
@@ -464,15 +480,18 @@ class DecodeEngine:
             if li == 0:
                 norm_quant(h, L["ln1"])
             L["qkv"](qa, q_scale, q_sum, qkv)
+            lora_add(li, "qkv", qkv, qa)
             attention(li, qkv)
             if not proj_add_norm_quant(L["o"], "o", qo, h, L["ln2"]):
-                res = yield from row_parallel(L["o"], qo)
+                res = yield from row_parallel(li, "o", L["o"], qo)
                 add_norm_quant(h, res, L["ln2"])
-            if fuse and L["gate_up"].bias is None:     # gate_up GEMM with the silu * mul epilogue, then the quantiser
+            plain = L["gate_up"].bias is not None or lora is not None   # something is added between the GEMM and silu * mul
+            if fuse and not plain:                     # gate_up GEMM with the silu * mul epilogue, then the quantiser
                 L["gate_up"].silu_mul(qa, q_scale, q_sum, mlp_act, gate_up)
             else:
                 L["gate_up"](qa, q_scale, q_sum, gate_up)
-            if fuse and L["gate_up"].bias is not None:
+                lora_add(li, "gate_up", gate_up, qa)
+            if fuse and plain:
                 fusedmod.silu_and_mul_quant(q_mlp, gate_up, q_scale, sums)
             else:
                 if not fuse:
@@ -480,7 +499,7 @@ class DecodeEngine:
                 self._quant(q_mlp, mlp_act, q_sum, q_scale)
             if li + 1 < nl and proj_add_norm_quant(L["down"], "down", q_mlp, h, self.layers[li + 1]["ln1"]):
                 continue                                             # (next layer's input norm done from the planes)
-            res = yield from row_parallel(L["down"], q_mlp)
+            res = yield from row_parallel(li, "down", L["down"], q_mlp)
             if li + 1 < nl:
                 add_norm_quant(h, res, self.layers[li + 1]["ln1"])   # next layer's input norm
             else:
@@ -615,6 +634,9 @@ class DecodeEngine:
         self._prefill_entry("prefill_shared")
         cfg, B, dev = self.cfg, self.B, self.dev
         self._single_gpu("prefill_shared")
+        assert not self._lora, \
+            "prefill_shared: LoRA is on (set_lora) - a shared prefix under different adapters has different K / V, so its pages cannot " \
+            "be computed once for the batch; set_lora(None), or prefill_chunked"
         prefix_tokens, suffix_tokens = prefix_tokens.to(dev), suffix_tokens.to(dev)
         assert prefix_tokens.dim() == 1 and suffix_tokens.dim() == 2 and suffix_tokens.size(0) == B and suffix_tokens.size(1) >= 1, \
             "prefill_shared: prefix_tokens [P], suffix_tokens [B, S] with S >= 1"
@@ -821,8 +843,9 @@ class DecodeEngine:
         # every tensor the graph touches and that was allocated outside the capture stays referenced as long as the graph does: the
         # four outputs of the walk (two of them are not part of the result) and the tree's constants (the cache may evict them)
         self._verify_keep = (out, self._tree_constants(par), self.penalties, self.prompt_lens, self._stop_tensors(), self._logprob_tensors(),
-                             self._fsm_tensors())
+                             self._fsm_tensors(), self._lora_tensors())
         self.verify_graph, self._verify_n, self._verify_result = g, n, res
+        self._verify_lora = self._lora                                      # (was it captured with the LoRA launches?)
         return g
 
     def run_verify(self, draft_tokens):
@@ -1102,26 +1125,86 @@ class DecodeEngine:
         """The launch that moves `fsm_state` over what a round emitted."""
         constraintsmod.advance(self.fsm_state, next_token, *self._fsm, **path)
 
+    # ---- LoRA adapters (qserve_amd.lora, csrc/lora_rows.hip) -----------------------------------------------------------------------
+    def enable_lora(self, slots, rank):
+        """Create the adapter table: `slots` adapters of rank <= `rank` (8, 16, 32 or 64) for the four linears of every layer
+        (`lora.LoraTable`, zeroed), and `lora_ids` int32 [B], every sequence at -1.  Nothing runs differently until set_lora.  A second
+        call makes a new table and switches LoRA off; a graph captured with the old one keeps reading the old one.  Single GPU, with
+        the lm_head."""
+        self._single_gpu("enable_lora")
+        self.lora_table = loramod.LoraTable(self.cfg, slots, rank, self.dev)
+        self.lora_ids = torch.full((self.B,), -1, dtype=torch.int32, device=self.dev)
+        ws = max(loramod.workspace_bytes(self.B, K, self.lora_table.rank, len(ends)) for K, _, ends in self.lora_table.shapes.values())
+        self._lora_step_ws = torch.empty((max(ws, 16),), dtype=torch.uint8, device=self.dev)
+        self._lora = False
+
+    def load_lora(self, slot, tensors, alpha):
+        """`lora.LoraTable.load`: fill `slot` from a dict of PEFT-named lora_A / lora_B tensors, scaling = alpha / r'.  In place: a captured
+        graph sees the new adapter."""
+        assert self.lora_table is not None, "load_lora: enable_lora first"
+        self.lora_table.load(slot, tensors, alpha)
+
+    def unload_lora(self, slot):
+        """`lora.LoraTable.unload`: zero `slot` (sequences still pointing at it add exact zeros)."""
+        assert self.lora_table is not None, "unload_lora: enable_lora first"
+        self.lora_table.unload(slot)
+
+    def set_lora(self, adapter_ids):
+        """Run sequence b under adapter adapter_ids[b] (one int per sequence; -1, or any id outside 0 .. slots-1: the base model) from
+        now on: one `lora.lora_rows` call behind each of the four base GEMMs of every layer (and behind its bias), on the quantised
+        activations that GEMM read, on every path - step() (hence capture() / run()), prefill, prefill_chunked, verify_tree, speculate and
+        their captures; rows_per_seq is the path's rows / B.  While on, the four linears take the path a linear with a bias takes: `o`
+        and `down` run without the planes form, gate_up as the plain GEMM followed by silu_and_mul + quant - the same values, bit for bit,
+        for a sequence at -1.  The ids live in `lora_ids`, filled in place: a captured graph sees later changes of them (and of the
+        table's slots); whether the launches exist at all is frozen into a capture - capture after switching; generate() re-captures by
+        itself.  set_lora(None) switches it off: every path launches exactly what it launches without this call.  prefill_shared refuses
+        to run while it is on.  Single GPU, with the lm_head."""
+        if adapter_ids is None:
+            self._lora = False
+            return
+        self._single_gpu("set_lora")
+        assert self.lora_table is not None, "set_lora: enable_lora first"
+        ids = torch.as_tensor(adapter_ids, device="cpu")
+        assert ids.dim() == 1 and ids.numel() == self.B and not ids.is_floating_point() and ids.dtype != torch.bool, \
+            f"set_lora: one int per sequence ({self.B}), got {ids.dtype} {tuple(ids.shape)}"
+        self.lora_ids.copy_(ids.to(torch.int32))
+        self._lora = True
+
+    def _lora_plan(self, rows):
+        """(rows_per_seq, workspace) of the lora_rows calls of a layer stack over `rows` rows: the step's persistent workspace, or a
+        fresh one sized for the largest of the four linears (inside a capture it lives in the graph's pool)."""
+        assert rows % self.B == 0
+        if rows == self.B:
+            return 1, self._lora_step_ws
+        t = self.lora_table
+        ws = max(loramod.workspace_bytes(rows, K, t.rank, len(ends)) for K, _, ends in t.shapes.values())
+        return rows // self.B, torch.empty((max(ws, 16),), dtype=torch.uint8, device=self.dev)
+
+    def _lora_tensors(self):
+        """What a captured graph with the LoRA launches reads (None while set_lora is off)."""
+        return (self.lora_table, self.lora_ids, self._lora_step_ws) if self._lora else None
+
     def generate(self, max_rounds, parents=None, poll_every=8, sampled=False):
         """Decode until every sequence has finished (after set_stopping), with the host looking at the device once per burst: replay
         the captured step graph - or, with `parents`, the captured speculate graph of that tree - `poll_every` times, then read
         (`finished`, `lengths`) back in one copy; that is the only host <-> device traffic of the loop.  `_len_bound` is set from it.
         Ends when no sequence is live, when `max_rounds` rounds are done, or when another round would not fit the page tables by the
         bound (a burst is shortened to what fits).  A graph that does not exist yet, or that was captured without the stop launch or with
-        another state of set_logprobs or set_constraint (for speculation also: of another tree or head), is captured first - the warm-up of capture() / capture_speculate() is a real round
+        another state of set_logprobs, set_constraint or set_lora (for speculation also: of another tree or head), is captured first - the warm-up of capture() / capture_speculate() is a real round
         that is not counted.
         -> (texts: per sequence the list of generated tokens history[b, prompt_lens[b] : lengths[b]], the first token of the prefill
         included; reasons: `finished` as a list; rounds; read_backs) - the texts are read once, after the loop."""
         assert self.stopping is not None, "generate: set_stopping first (nothing else ends the loop)"
         assert max_rounds >= 0 and poll_every >= 1
         if parents is None:
-            if self.graph is None or not self._graph_stops or self._graph_logprobs != self._logprobs or self._graph_fsm is not self._fsm:
+            if self.graph is None or not self._graph_stops or self._graph_logprobs != self._logprobs or self._graph_fsm is not self._fsm or \
+                    self._graph_lora != self._lora:
                 self.capture(piecewise=False)
             advance, run = 1, self.run
         else:
             par = self._tree_arg(parents, "generate")
             if self.speculate_graph is None or self._speculate_tree != (tuple(par), bool(sampled), True, self._logprobs) or \
-                    self._speculate_fsm is not self._fsm:
+                    self._speculate_fsm is not self._fsm or self._speculate_lora != self._lora:
                 self.capture_speculate(par, sampled=sampled)
             advance, run = len(par), self.run_speculate
         rounds = reads = 0
@@ -1201,9 +1284,10 @@ class DecodeEngine:
         # every tensor the graph touches and that was allocated outside the capture stays referenced as long as the graph does: the
         # draft buffer, the four outputs of the walk, the tree's constants (the cache may evict them), step()'s record constants
         self._speculate_keep = (draft, out, self._tree_constants(par), self._step_record, self.history, self.penalties, self.prompt_lens,
-                                self._stop_tensors(), self._logprob_tensors(), self._fsm_tensors())
+                                self._stop_tensors(), self._logprob_tensors(), self._fsm_tensors(), self._lora_tensors())
         self.speculate_graph, self._speculate_n, self._speculate_result = g, n, res
         self._speculate_fsm = self._fsm                                     # (... and the automaton it masks with?)
+        self._speculate_lora = self._lora                                   # (... and the LoRA launches?)
         # (generate: is the captured round the one it was asked for - this tree, this head, the stop launch in it?)
         self._speculate_tree = (tuple(par), bool(sampled), self.stopping is not None, self._logprobs)
         return g
@@ -1335,8 +1419,9 @@ class DecodeEngine:
         if not piecewise:
             self.graph, _ = self._capture(self.step, 1)
             self._graph_stops = self.stopping is not None    # (generate: does the captured step hold the stop launch?)
-            self._graph_logprobs, self._graph_keep = self._logprobs, (self._logprob_tensors(), self._fsm_tensors())   # (... and the log-probability launch?)
+            self._graph_logprobs, self._graph_keep = self._logprobs, (self._logprob_tensors(), self._fsm_tensors(), self._lora_tensors())   # (... and the log-probability launch?)
             self._graph_fsm = self._fsm                      # (... and the automaton it masks with?)
+            self._graph_lora = self._lora                    # (... and the LoRA launches?)
             return self.graph
         self._warm_up(self.step)
         pool = torch.cuda.graph_pool_handle()
