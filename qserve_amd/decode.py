@@ -17,6 +17,7 @@ H/tp query heads, Hkv/tp KV heads and the matching column / row shards; the part
 down_proj are summed with one RCCL all-reduce each.
 """
 import os
+from types import SimpleNamespace
 
 import torch
 
@@ -279,9 +280,9 @@ class DecodeEngine:
             n = tp_world * B * 8
             self.head_cand = self.proj_out.view(-1)[:n].view(tp_world, B, 8)      # what this rank contributes
             self.head_cand_res = self.proj_res.view(-1)[:n].view(tp_world, B, 8)  # the sum over the ranks
-        self.graph = None
-        self.pieces = None
-        self._graph_stops = False
+        # capture / capture_verify / capture_speculate: the graphs, and for each the record of what it was captured with (`_captured`)
+        self.graph = self.pieces = self.verify_graph = self.speculate_graph = None
+        self._step_capture = self._verify_capture = self._speculate_capture = None
         # an integer upper bound of `lengths`, kept on the host: set by the prefill entries, + 1 per step() / run(), + n per device-walk
         # verify_tree (which cannot know how many nodes were accepted without reading the device).  A planner hint and the "does it fit
         # the page tables" bound only - no result depends on it.  sync_length_bound() makes it exact again, at the price of one read-back.
@@ -289,10 +290,6 @@ class DecodeEngine:
         self._tree_cache = {}            # parent tuple -> the per-tree device constants of the device-walk verify_tree
         self._layer_tables = None        # append.layer_table_pointers(self.tables), built on first use
         self.last_verify_logits = None   # verify_tree: the logits [B, n, V] of its last call
-        # capture_verify / capture_speculate: the graph, the tree's n, the persistent result triple, and every tensor the graph touches
-        # that was allocated outside the capture (it stays referenced as long as the graph does); _verify_draft: run_verify's input
-        self.verify_graph = self._verify_n = self._verify_result = self._verify_keep = self._verify_draft = None
-        self.speculate_graph = self._speculate_n = self._speculate_result = self._speculate_keep = self._speculate_tree = None
         self.sampling = None             # set_sampling: {"seed"} while the head samples; the parameters live in device tensors:
         self._samp_t = self._samp_k = self._samp_p = self._samp_ids = None      # temperature, top-k, top-p per row; arange(B)
         self.penalties = None            # set_penalties: the (repetition, frequency, presence) device tensors while the heads penalise
@@ -307,19 +304,17 @@ class DecodeEngine:
         self.finished = self.limit_lens = self._stop_seqs = self._stop_lens = self._stop_k = None
         # set_logprobs: (top, tempered) while the log-probability launch runs behind the heads; its persistent logs (created by the first
         # call, re-created for another `top`): float32 [B, max_len], int32 [B, max_len], int32 / float32 [B, max_len, top]; where the
-        # generated text begins (the prompt length of the last prefill entry); what the captured step was captured with
+        # generated text begins (the prompt length of the last prefill entry)
         self._logprobs = None
-        self.logprob_log = self.rank_log = self.top_ids_log = self.top_lp_log = None
-        self._text_start = self._graph_logprobs = self._graph_keep = None
+        self.logprob_log = self.rank_log = self.top_ids_log = self.top_lp_log = self._text_start = None
         # set_constraint: the device tables (token_class, next) while the heads mask - the SAME tuple as long as the same automaton is
         # on, so a capture can tell whether it was made with it -, the TokenDFA they came from, the state of every sequence int32 [B],
-        # the states of a verification's nodes int32 [B * MAX_TREE]; what the captured step / round was captured with
-        self._fsm = self._fsm_src = self._fsm_kept = self.fsm_state = self._fsm_node_state = self._graph_fsm = self._speculate_fsm = None
+        # the states of a verification's nodes int32 [B * MAX_TREE]
+        self._fsm = self._fsm_src = self._fsm_kept = self.fsm_state = self._fsm_node_state = None
         # enable_lora: the adapter table (lora.LoraTable) and the adapter of every sequence int32 [B] (-1: the base model), filled in
-        # place; set_lora: True while lora_rows runs behind the four linears of every layer; the step's workspace; what the captured
-        # step / verification / round was captured with
+        # place; set_lora: True while lora_rows runs behind the four linears of every layer; the step's workspace
         self.lora_table = self.lora_ids = self._lora_step_ws = None
-        self._lora = self._graph_lora = self._verify_lora = self._speculate_lora = False
+        self._lora = False
 
     def _single_gpu(self, what):
         """What every entry behind the un-cut fp16 lm_head asks for (sampling, penalties, shared prefixes, tree verification, drafting):
@@ -545,9 +540,7 @@ class DecodeEngine:
             if self._logprobs is not None:                           # a new text: the first token's entry lands at column prompt_len
                 self._clear_logprob_logs()
                 self.lengths.fill_(prompt_len)
-                self._logprob_update(logits, self.tokens)
-            if self._fsm is not None:                                # the first token was drawn under the start states: move over it
-                self._fsm_advance(self.tokens)
+            self._emit(logits, self.tokens)                          # (stopping is off here, by _prefill_entry)
         self.lengths.fill_(prompt_len + 1)
         self._len_bound = prompt_len + 1
         self._text_start = prompt_len
@@ -701,15 +694,12 @@ class DecodeEngine:
         par = self._tree_arg(parents, "verify_tree", drafting=False)
         n = len(par)
         assert tuple(draft_tokens.shape) == (B, n) and draft_tokens.dtype == torch.int64
-        assert not sampled or self.sampling is not None, "verify_tree(sampled=True): set_sampling first"
+        self._sampled_entry("verify_tree", sampled)
         if device_walk:
             return self._verify_tree_device(draft_tokens, par, sampled=sampled)
-        assert self.penalties is None, "verify_tree: penalties (set_penalties) need device_walk=True - the host walk does not penalise"
-        assert self.stopping is None, "verify_tree: stopping (set_stopping) needs device_walk=True - the host walk does not clip its path"
-        assert self._logprobs is None, "verify_tree: log-probabilities (set_logprobs) need device_walk=True - the host walk does not record them"
-        assert self._fsm is None, "verify_tree: a constraint (set_constraint) needs device_walk=True - the host walk does not advance its states"
+        self._host_walk_entry()
         max_past = int(self.lengths.max()) - 1
-        assert max_past + n <= self.mb * 64, "verify_tree: the tree does not fit the sequences' page tables"
+        self._fits("verify_tree", n, max_past)
         _, toks, past, h, final, logits, am = self._verify_forward(draft_tokens, par, max_past, sampled)
         am = am.view(B, n)
         # the greedy walk, on the host (n <= 64 nodes per sequence)
@@ -744,6 +734,25 @@ class DecodeEngine:
         tree's n nodes each, whatever was accepted."""
         self._len_bound = int(self.lengths.max())
         return self._len_bound
+
+    def _sampled_entry(self, what, sampled):
+        """What every entry with a `sampled` argument asks for before it samples."""
+        assert not sampled or self.sampling is not None, f"{what}(sampled=True): set_sampling first"
+
+    def _host_walk_entry(self):
+        """What verify_tree(device_walk=False) refuses: the features whose launches only the device walk issues."""
+        for on, why in ((self.penalties, "penalties (set_penalties) need device_walk=True - the host walk does not penalise"),
+                        (self.stopping, "stopping (set_stopping) needs device_walk=True - the host walk does not clip its path"),
+                        (self._logprobs, "log-probabilities (set_logprobs) need device_walk=True - the host walk does not record them"),
+                        (self._fsm, "a constraint (set_constraint) needs device_walk=True - the host walk does not advance its states")):
+            assert on is None, f"verify_tree: {why}"
+
+    def _fits(self, what, n, max_past=None):
+        """Do n more slots behind `max_past` fit the page tables?  None: behind the host-side bound of the lengths."""
+        by_bound = max_past is None
+        assert (self._len_bound - 1 if by_bound else max_past) + n <= self.mb * 64, \
+            f"{what}: the tree does not fit the sequences' page tables" + \
+            (" (by the host-side bound of the lengths: sync_length_bound())" if by_bound else "")
 
     def _tree_constants(self, par):
         """The device tensors a verification or a drafter needs for the tree `par` (built on the host once, then served from the cache)."""
@@ -800,17 +809,11 @@ class DecodeEngine:
         `out`: accept_greedy's four output tensors (None: fresh ones)."""
         from . import append as appendmod
         B, n = self.B, len(par)
-        assert self._len_bound - 1 + n <= self.mb * 64, \
-            "verify_tree: the tree does not fit the sequences' page tables (by the host-side bound of the lengths: sync_length_bound())"
+        self._fits("verify_tree", n)
         hint = self._len_bound - 1 if max_past is None else int(max_past)
         c, toks, past, h, final, logits, am = self._verify_forward(draft_tokens, par, hint, sampled)
         accept_idx, accept_lens, last, nxt = appendmod.accept_greedy(toks.view(-1), am, c["parents"], c["cu"], max_accept=n, out=out)
-        if self.stopping is not None:                                       # clip the path at the first stop; a finished row accepts nothing
-            self._stop_update(nxt, node_tokens=toks, accept_idx=accept_idx, accept_lens=accept_lens, last_row=last)
-        if self._logprobs is not None:                                      # the (clipped) path's rows, each scored for the token behind it
-            self._logprob_update(logits, nxt, node_tokens=toks, accept_idx=accept_idx, accept_lens=accept_lens)
-        if self._fsm is not None:                                           # the state of the (clipped) path's last row, over the token it emitted
-            self._fsm_advance(nxt, node_state=self._fsm_node_state[:B * n].view(B, n), accept_idx=accept_idx, accept_lens=accept_lens)
+        self._emit(logits, nxt, node_tokens=toks, accept_idx=accept_idx, accept_lens=accept_lens, last_row=last)
         appendmod.commit_path_layers(c["layer_tables"], past, accept_idx, accept_lens, self.mb, self.Hkv, self.size_per_token, self.int4)
         self.hidden.copy_(torch.index_select(h, 0, last))
         self.final.copy_(torch.index_select(final, 0, last))
@@ -820,11 +823,18 @@ class DecodeEngine:
         self.last_verify_logits = logits.view(B, n, -1)                     # (penalised / masked, while set_penalties / set_constraint is on)
         return accept_idx, accept_lens, am.view(B, n)
 
-    def _walk_outputs(self, n):
-        """Persistent (accept_idx, accept_lens, last_row, next_token) tensors for the device walk of a captured n-node verification."""
-        B, dev = self.B, self.dev
-        return (torch.zeros((B, n), dtype=torch.int32, device=dev), torch.zeros((B,), dtype=torch.int32, device=dev),
-                torch.zeros((B,), dtype=torch.int64, device=dev), torch.zeros((B,), dtype=torch.int64, device=dev))
+    def _capture_round(self, what, par, fn, max_past, sampled):
+        """capture_verify / capture_speculate behind `_tree_arg`: capture fn - _verify_tree_device or _speculate - over a persistent
+        [B, n] draft buffer and persistent (accept_idx, accept_lens, last_row, next_token) outputs of the walk -> the record.  Kept: those
+        buffers (two of the outputs are not part of the result) and the tree's constants, which the cache may evict."""
+        self._sampled_entry(what, sampled)
+        n, B, dev = len(par), self.B, self.dev
+        hint = self.max_len if max_past is None else int(max_past)
+        draft = torch.zeros((B, n), dtype=torch.int64, device=dev)
+        out = (torch.zeros((B, n), dtype=torch.int32, device=dev), torch.zeros((B,), dtype=torch.int32, device=dev),
+               torch.zeros((B,), dtype=torch.int64, device=dev), torch.zeros((B,), dtype=torch.int64, device=dev))
+        captured = self._capture(lambda: fn(draft, par, max_past=hint, out=out, sampled=sampled), n)
+        return self._captured(captured, n, draft, out, self._tree_constants(par), tree=tuple(par), sampled=bool(sampled))
 
     def capture_verify(self, parents, max_past=None, sampled=False):
         """Capture one device-walk verify_tree of the tree `parents` in a hipGraph, the way capture() captures step() (`_capture`: a
@@ -834,32 +844,21 @@ class DecodeEngine:
         restore or do not care about - what capture() implies for step().  `sampled=True` captures verify_tree(sampled=True) (after
         set_sampling).  Single GPU, with the lm_head."""
         par = self._tree_arg(parents, "capture_verify", drafting=False)
-        n, B, dev = len(par), self.B, self.dev
-        assert not sampled or self.sampling is not None, "capture_verify(sampled=True): set_sampling first"
-        hint = self.max_len if max_past is None else int(max_past)
-        self._verify_draft = torch.zeros((B, n), dtype=torch.int64, device=dev)
-        out = self._walk_outputs(n)
-        g, res = self._capture(lambda: self._verify_tree_device(self._verify_draft, par, max_past=hint, out=out, sampled=sampled), n)
-        # every tensor the graph touches and that was allocated outside the capture stays referenced as long as the graph does: the
-        # four outputs of the walk (two of them are not part of the result) and the tree's constants (the cache may evict them)
-        self._verify_keep = (out, self._tree_constants(par), self.penalties, self.prompt_lens, self._stop_tensors(), self._logprob_tensors(),
-                             self._fsm_tensors(), self._lora_tensors())
-        self.verify_graph, self._verify_n, self._verify_result = g, n, res
-        self._verify_lora = self._lora                                      # (was it captured with the LoRA launches?)
-        return g
+        self._verify_capture = self._capture_round("capture_verify", par, self._verify_tree_device, max_past, sampled)
+        self.verify_graph = self._verify_capture.graph
+        return self.verify_graph
 
     def run_verify(self, draft_tokens):
         """Replay the verification capture_verify captured on `draft_tokens` int64 [B, n] -> the persistent (accept_idx, accept_lens,
         argmax) tensors of the capture (overwritten by the next replay)."""
         assert self.verify_graph is not None, "run_verify: capture_verify first"
-        n = self._verify_n
-        assert tuple(draft_tokens.shape) == (self.B, n) and draft_tokens.dtype == torch.int64
-        assert self._len_bound - 1 + n <= self.mb * 64, \
-            "run_verify: the tree does not fit the sequences' page tables (by the host-side bound of the lengths: sync_length_bound())"
-        self._verify_draft.copy_(draft_tokens)
+        cap = self._verify_capture
+        assert tuple(draft_tokens.shape) == (self.B, cap.n) and draft_tokens.dtype == torch.int64
+        self._fits("run_verify", cap.n)
+        cap.keep[0][0].copy_(draft_tokens)                                  # (the capture's draft buffer)
         self.verify_graph.replay()
-        self._len_bound += n
-        return self._verify_result
+        self._len_bound += cap.n
+        return cap.result
 
     # ---- n-gram drafting and the closed speculative loop (qserve_amd.drafting, csrc/ngram_draft.hip) -----------------------------
     def enable_drafting(self, prompt_tokens, max_ngram=4, min_match=1, pad_token=0):
@@ -936,8 +935,7 @@ class DecodeEngine:
     # ---- stop conditions (qserve_amd.stopping, csrc/stop_update.hip) -----------------------------------------------------------
     def set_stopping(self, stop=(), max_new_tokens=None):
         """End sequences on the device (after enable_drafting: the rule reads `history` and `prompt_lens`): one `stopping.stop_update`
-        launch behind the head of step() (hence capture() / run()) and between the walk and the commit of verify_tree(device_walk=True)
-        (hence capture_verify, speculate, capture_speculate).  `stop`: token ids and / or sequences of ids (at most 32 of at most 8 tokens);
+        launch in the tail of every round (`_emit` has where, and the order).  `stop`: token ids and / or sequences of ids (at most 32 of at most 8 tokens);
         a sequence ends with the token that completes one of them INSIDE its generated text (a match may not begin in the prompt).
         `max_new_tokens`: an int, or one per sequence - a sequence ends when its text holds prompt + max_new_tokens tokens; None: the
         history's capacity (prompt_len + max_new of the engine), which an explicit value must not exceed.  A round's path is clipped at
@@ -983,10 +981,6 @@ class DecodeEngine:
         self._stop_k.zero_()                                                # m = 0: nothing is emitted, the current token is looked at
         self._stop_update(self.tokens, accept_lens=self._stop_k, check_root=True)
 
-    def _stop_tensors(self):
-        """What a captured graph with the stop launch reads (None while stopping is off)."""
-        return None if self.stopping is None else (self.finished, self.limit_lens, self._stop_seqs, self._stop_lens, self._stop_k)
-
     def _stop_update(self, next_token, **path):
         """The launch of set_stopping's rule on what a round is about to emit, from `history` and the lengths as they stand (not yet
         advanced) -> k int32 [B]."""
@@ -996,12 +990,10 @@ class DecodeEngine:
     # ---- log-probabilities (qserve_amd.logprobs, csrc/logprob_rows.hip) ---------------------------------------------------------
     def set_logprobs(self, top=0, tempered=False):
         """Record, for every token the engine emits from now on, its log-probability, its rank and the `top` (0 .. 32) most likely ids
-        with their log-probabilities, on the device: one `logprobs.logprob_path` launch per round, behind the head - behind the stop
-        launch while set_stopping is on, so a clipped path records exactly what it emits and a frozen row records nothing - and in front
-        of the advance of the lengths: in step() (hence capture() / run()), between the stop launch and the commit of
-        verify_tree(device_walk=True) (hence capture_verify, speculate, capture_speculate) - there the kernel itself gathers the rows
-        on the accepted path and the token each is scored for -, and in the head of a prefill entry, whose token lands at column
-        prompt_len (a prefill entry also clears the logs: a new text begins).  The logs, indexed by text position like `history`:
+        with their log-probabilities, on the device: one `logprobs.logprob_path` launch in the tail of every round (`_emit` has where,
+        and the order: a clipped path records exactly what it emits and a frozen row records nothing) - in a verification the kernel
+        itself gathers the rows on the accepted path and the token each is scored for -, and in the head of a prefill entry, whose token
+        lands at column prompt_len (a prefill entry also clears the logs: a new text begins).  The logs, indexed by text position like `history`:
         `logprob_log` float32 [B, max_len] (NaN where nothing was recorded), `rank_log` int32 [B, max_len] (0), `top_ids_log` int32
         [B, max_len, top] (-1) and `top_lp_log` float32 [B, max_len, top] (NaN); logprobs() reads them.  The values describe
         softmax(logits / T) of the logits the head saw - penalised while set_penalties is on; top-k and top-p do not enter - with T = 1,
@@ -1031,17 +1023,6 @@ class DecodeEngine:
         self.top_ids_log.fill_(-1)
         self.top_lp_log.fill_(float("nan"))
 
-    def _logprob_tensors(self):
-        """What a captured graph with the log-probability launch writes (None while set_logprobs is off)."""
-        return None if self._logprobs is None else (self.logprob_log, self.rank_log, self.top_ids_log, self.top_lp_log, self._samp_t)
-
-    def _logprob_update(self, logits, next_token, **path):
-        """The launch of set_logprobs on what a round is about to emit, at the lengths as they stand (not yet advanced)."""
-        top, tempered = self._logprobs
-        logprobsmod.logprob_path(logits, path.get("node_tokens"), path.get("accept_idx"), path.get("accept_lens"), next_token, self.lengths,
-                                 temperature=self._samp_t[:self.B] if tempered else 1.0, top=top,
-                                 out=(self.logprob_log, self.rank_log, self.top_ids_log, self.top_lp_log))
-
     def logprobs(self):
         """Read the logs of set_logprobs once -> per sequence a dict of lists over its generated text, positions prompt_len ..
         lengths[b] - 1 - entry i belongs to token i of generate()'s texts, the first token of the prefill included (NaN / 0 where nothing
@@ -1069,9 +1050,8 @@ class DecodeEngine:
         every row under the state of its own node, the state reached along the path root -> node (`constraints.node_states`, launched
         just before).  A child is accepted only if it holds the token its parent's masked row produced, so greedy and sampled
         speculation stay lossless: the generated tokens are those of constrained step()s, whatever was drafted.  `constraints.advance`
-        then moves `fsm_state` over what the round emitted: behind the head in step() and in a prefill entry, behind the walk and the
-        stop launch (with its clipped k) and in front of the commit in a verification; a frozen row keeps its state.  The logits a head
-        returns, `last_verify_logits` and what set_logprobs scores are the MASKED ones.
+        then moves `fsm_state` over what the round emitted, in its tail (`_emit` has where, and the order); a frozen row keeps its state.
+        The logits a head returns, `last_verify_logits` and what set_logprobs scores are the MASKED ones.
 
         A state the automaton has no way out of for the token emitted becomes constraints.DEAD (-2) - it cannot happen through the
         engine's own heads unless a state allows no token at all - and a dead or negative state is unconstrained.  Unlike penalties and
@@ -1108,10 +1088,6 @@ class DecodeEngine:
             self._fsm_kept, self._fsm_src = (d.token_class, d.next), dfa
         self._fsm = self._fsm_kept
 
-    def _fsm_tensors(self):
-        """What a captured graph with the constraint launches reads and writes (None while set_constraint is off)."""
-        return None if self._fsm is None else (self._fsm, self.fsm_state, self._fsm_node_state)
-
     def _constrain(self, logits, node_tokens=None, tree=None):
         """The mask launch in front of a head: `logits` [B * n, V] in place, the rows of a draft under their nodes' states."""
         token_class, nxt = self._fsm
@@ -1120,10 +1096,6 @@ class DecodeEngine:
             states = self._fsm_node_state[:node_tokens.numel()]
             constraintsmod.node_states(self.fsm_state, node_tokens, tree, token_class, nxt, out=states)
         constraintsmod.constrain_rows(logits, states, token_class, nxt)
-
-    def _fsm_advance(self, next_token, **path):
-        """The launch that moves `fsm_state` over what a round emitted."""
-        constraintsmod.advance(self.fsm_state, next_token, *self._fsm, **path)
 
     # ---- LoRA adapters (qserve_amd.lora, csrc/lora_rows.hip) -----------------------------------------------------------------------
     def enable_lora(self, slots, rank):
@@ -1180,31 +1152,82 @@ class DecodeEngine:
         ws = max(loramod.workspace_bytes(rows, K, t.rank, len(ends)) for K, _, ends in t.shapes.values())
         return rows // self.B, torch.empty((max(ws, 16),), dtype=torch.uint8, device=self.dev)
 
-    def _lora_tensors(self):
-        """What a captured graph with the LoRA launches reads (None while set_lora is off)."""
-        return (self.lora_table, self.lora_ids, self._lora_step_ws) if self._lora else None
+    # ---- what the features share: the tail of a round, and what a capture freezes and keeps --------------------------------------
+    def _emit(self, logits, next_token, node_tokens=None, accept_idx=None, accept_lens=None, last_row=None):
+        """THE tail of a round, on what it is about to emit, at the lengths as they stand (not yet advanced): behind the head of step()
+        (hence capture() / run()) and of a prefill entry (where stopping is off), between the walk and the commit of
+        verify_tree(device_walk=True) (hence capture_verify, speculate, capture_speculate).  `logits`: the rows the head saw;
+        `next_token`: the token behind the path; a verification adds its draft and the walk's outputs (`node_tokens` [B, n], `accept_idx`,
+        `accept_lens`, `last_row`), the others give none: one token per sequence.  In this order, whatever is switched on:
+          1. set_stopping: `stopping.stop_update` clips the path at the first stop, in place, -> k int32 [B] - `accept_lens` itself, or
+             `_stop_k` (0 / 1) for a step; a finished row emits nothing;
+          2. set_logprobs: `logprobs.logprob_path` scores the (clipped) path's rows, each for the token behind it - k = 0 writes nothing;
+          3. set_constraint: `constraints.advance` moves `fsm_state` from the state of the (clipped) path's last row - under a draft its
+             node's, of `_fsm_node_state` - over the token it emitted; k = 0 keeps the state.
+        -> k while stopping is on (what the lengths advance by), else None."""
+        k = accept_lens
+        if self.stopping is not None:
+            k = self._stop_update(next_token, node_tokens=node_tokens, accept_idx=accept_idx, accept_lens=accept_lens, last_row=last_row,
+                                  out_lens=self._stop_k if accept_lens is None else None)
+        if self._logprobs is not None:
+            top, tempered = self._logprobs
+            logprobsmod.logprob_path(logits, node_tokens, accept_idx, k, next_token, self.lengths,
+                                     temperature=self._samp_t[:self.B] if tempered else 1.0, top=top,
+                                     out=(self.logprob_log, self.rank_log, self.top_ids_log, self.top_lp_log))
+        if self._fsm is not None:
+            node_state = None if node_tokens is None else self._fsm_node_state[:node_tokens.numel()].view_as(node_tokens)
+            constraintsmod.advance(self.fsm_state, next_token, *self._fsm, node_state=node_state, accept_idx=accept_idx, accept_lens=k)
+        return k if self.stopping is not None else None
+
+    def _capture_state(self):
+        """What a capture freezes besides its own arguments, and generate() compares: whether the stop launch exists, the state of
+        set_logprobs, the automaton whose tables are on - set_constraint uploads them once per TokenDFA object, so the object stands for
+        the tables and compares by identity -, whether the LoRA launches exist.  (Frozen too, and not in it: whether the head samples or
+        penalises.)"""
+        return dict(stops=self.stopping is not None, logprobs=self._logprobs, automaton=None if self._fsm is None else self._fsm_src,
+                    lora=self._lora)
+
+    def _kept_tensors(self):
+        """Every persistent tensor a captured graph may touch and a later call may replace, by feature (None while the feature is off)."""
+        return dict(drafting=(self._step_record, self.history, self.prompt_lens), penalties=self.penalties,
+                    stopping=None if self.stopping is None else (self.finished, self.limit_lens, self._stop_seqs, self._stop_lens, self._stop_k),
+                    logprobs=None if self._logprobs is None else (self.logprob_log, self.rank_log, self.top_ids_log, self.top_lp_log,
+                                                                  self._samp_t),
+                    constraint=None if self._fsm is None else (self._fsm, self.fsm_state, self._fsm_node_state),
+                    lora=(self.lora_table, self.lora_ids, self._lora_step_ws) if self._lora else None)
+
+    def _captured(self, captured, n, *buffers, **own):
+        """The record of the graph `_capture` just returned as `captured`: `graph`; `result`: what the captured call returned, tensors
+        the replays overwrite; `n`: what a replay adds to the bound of the lengths; `state`: _capture_state() now, with what else decides
+        whether this is the graph generate() was asked for (`own`; a round: the tree and the head); `keep`: every tensor the graph touches
+        that was allocated outside the capture - it stays referenced as long as the graph does -: the capture's own `buffers` (a round:
+        the draft buffer first) and _kept_tensors()."""
+        return SimpleNamespace(graph=captured[0], result=captured[1], n=n, state=dict(self._capture_state(), **own),
+                               keep=(buffers, self._kept_tensors()))
+
+    def _stale(self, cap, **own):
+        """generate(): was the graph of the record `cap` made in another state than the engine is in now, or not for `own`?"""
+        return cap.state != dict(self._capture_state(), **own)
 
     def generate(self, max_rounds, parents=None, poll_every=8, sampled=False):
         """Decode until every sequence has finished (after set_stopping), with the host looking at the device once per burst: replay
         the captured step graph - or, with `parents`, the captured speculate graph of that tree - `poll_every` times, then read
         (`finished`, `lengths`) back in one copy; that is the only host <-> device traffic of the loop.  `_len_bound` is set from it.
         Ends when no sequence is live, when `max_rounds` rounds are done, or when another round would not fit the page tables by the
-        bound (a burst is shortened to what fits).  A graph that does not exist yet, or that was captured without the stop launch or with
-        another state of set_logprobs, set_constraint or set_lora (for speculation also: of another tree or head), is captured first - the warm-up of capture() / capture_speculate() is a real round
-        that is not counted.
+        bound (a burst is shortened to what fits).  A graph that does not exist yet, or that was captured in another `_capture_state()`
+        (for speculation also: of another tree or head), is captured first - the warm-up of capture() / capture_speculate() is a real
+        round that is not counted.
         -> (texts: per sequence the list of generated tokens history[b, prompt_lens[b] : lengths[b]], the first token of the prefill
         included; reasons: `finished` as a list; rounds; read_backs) - the texts are read once, after the loop."""
         assert self.stopping is not None, "generate: set_stopping first (nothing else ends the loop)"
         assert max_rounds >= 0 and poll_every >= 1
         if parents is None:
-            if self.graph is None or not self._graph_stops or self._graph_logprobs != self._logprobs or self._graph_fsm is not self._fsm or \
-                    self._graph_lora != self._lora:
+            if self.graph is None or self._stale(self._step_capture):
                 self.capture(piecewise=False)
             advance, run = 1, self.run
         else:
             par = self._tree_arg(parents, "generate")
-            if self.speculate_graph is None or self._speculate_tree != (tuple(par), bool(sampled), True, self._logprobs) or \
-                    self._speculate_fsm is not self._fsm or self._speculate_lora != self._lora:
+            if self.speculate_graph is None or self._stale(self._speculate_capture, tree=tuple(par), sampled=bool(sampled)):
                 self.capture_speculate(par, sampled=sampled)
             advance, run = len(par), self.run_speculate
         rounds = reads = 0
@@ -1256,12 +1279,12 @@ class DecodeEngine:
         drafting.history_append.  `tokens`, `lengths`, the cache and `history` end where accept_lens[b] decode steps would have left
         them.  -> the triple of verify_tree.  `sampled=True`: verify_tree(sampled=True), after set_sampling."""
         par = self._tree_arg(parents, "speculate")
-        assert not sampled or self.sampling is not None, "speculate(sampled=True): set_sampling first"
-        return self._speculate(par, sampled=sampled)
+        self._sampled_entry("speculate", sampled)
+        return self._speculate(None, par, sampled=sampled)
 
-    def _speculate(self, par, max_past=None, out=None, draft=None, sampled=False):
-        """speculate() behind its argument checks.  `max_past`, `out`: as for _verify_tree_device; `draft`: the [B, n] buffer the
-        drafter fills (None: a fresh one)."""
+    def _speculate(self, draft, par, max_past=None, out=None, sampled=False):
+        """speculate() behind its argument checks.  `draft`: the [B, n] buffer the drafter fills (None: a fresh one); `max_past`, `out`:
+        as for _verify_tree_device."""
         draft = self.draft_tree(par, out=draft)
         past = self.lengths - 1                                             # before the verification advances the lengths
         res = self._verify_tree_device(draft, par, max_past=max_past, out=out, sampled=sampled)
@@ -1275,33 +1298,19 @@ class DecodeEngine:
         on it.  The warm-up is a real round: it advances `tokens`, `lengths`, the cache and `history` like any other.  `sampled=True`
         captures speculate(sampled=True) (after set_sampling).  Single GPU, with the lm_head, after enable_drafting."""
         par = self._tree_arg(parents, "capture_speculate")
-        n, B, dev = len(par), self.B, self.dev
-        assert not sampled or self.sampling is not None, "capture_speculate(sampled=True): set_sampling first"
-        hint = self.max_len if max_past is None else int(max_past)
-        draft = torch.zeros((B, n), dtype=torch.int64, device=dev)
-        out = self._walk_outputs(n)
-        g, res = self._capture(lambda: self._speculate(par, max_past=hint, out=out, draft=draft, sampled=sampled), n)
-        # every tensor the graph touches and that was allocated outside the capture stays referenced as long as the graph does: the
-        # draft buffer, the four outputs of the walk, the tree's constants (the cache may evict them), step()'s record constants
-        self._speculate_keep = (draft, out, self._tree_constants(par), self._step_record, self.history, self.penalties, self.prompt_lens,
-                                self._stop_tensors(), self._logprob_tensors(), self._fsm_tensors(), self._lora_tensors())
-        self.speculate_graph, self._speculate_n, self._speculate_result = g, n, res
-        self._speculate_fsm = self._fsm                                     # (... and the automaton it masks with?)
-        self._speculate_lora = self._lora                                   # (... and the LoRA launches?)
-        # (generate: is the captured round the one it was asked for - this tree, this head, the stop launch in it?)
-        self._speculate_tree = (tuple(par), bool(sampled), self.stopping is not None, self._logprobs)
-        return g
+        self._speculate_capture = self._capture_round("capture_speculate", par, self._speculate, max_past, sampled)
+        self.speculate_graph = self._speculate_capture.graph
+        return self.speculate_graph
 
     def run_speculate(self):
         """Replay the round capture_speculate captured: no argument, nothing copied from the host -> the persistent (accept_idx,
         accept_lens, argmax) tensors of the capture (overwritten by the next replay)."""
         assert self.speculate_graph is not None, "run_speculate: capture_speculate first"
-        n = self._speculate_n
-        assert self._len_bound - 1 + n <= self.mb * 64, \
-            "run_speculate: the tree does not fit the sequences' page tables (by the host-side bound of the lengths: sync_length_bound())"
+        cap = self._speculate_capture
+        self._fits("run_speculate", cap.n)
         self.speculate_graph.replay()
-        self._len_bound += n
-        return self._speculate_result
+        self._len_bound += cap.n
+        return cap.result
 
     # ---- one decode step (llama_w4a8_unpad.py:330-361 per layer) --------------------------------------------
     def _segments(self):
@@ -1314,27 +1323,16 @@ class DecodeEngine:
                     proj=self.proj_out, proj_res=self.proj_res, gate_up=self.gate_up_buf, mlp_act=self.mlp_act)
         yield from self._layer_stack(self.hidden, bufs, self._step_attention, self.planes)
         layernorm_ops.rms_norm(self.final, self.hidden, self.norm_w, self.cfg["eps"])
+        logits = None                                                # (the features of the tail need the un-cut head: _single_gpu)
         if self.with_lm_head and self.vocab_parallel:
             yield self._head_local()                                 # candidates of the ranks meet in the sum all-reduce
             self._head_finish(self.head_cand_res)
         elif self.with_lm_head:                                      # (penalty context: history[b, :lengths[b]], the text so far)
             logits = self._head(self.final, self.tokens, self._step_keys if self.sampling is not None else None)
-        if self.stopping is not None:                                # set_stopping: k = 0 (a stop before the new token, or a frozen row) / 1
-            k = self._stop_update(self.tokens, out_lens=self._stop_k)
-            if self._logprobs is not None:                           # set_logprobs: the new token's entry; a row with k = 0 writes none
-                self._logprob_update(logits, self.tokens, accept_lens=k)
-            if self._fsm is not None:                                # set_constraint: a row with k = 0 keeps its state
-                self._fsm_advance(self.tokens, accept_lens=k)
-            self.lengths.add_(k)
+        k = self._emit(logits, self.tokens)                          # set_stopping: k = 0 (a stop before the new token, or a frozen row) / 1
+        self.lengths.add_(1 if k is None else k)
+        if self.history is not None:                                 # enable_drafting: the new token joins the text (k = 0: it does not)
             self._record_step(k)
-            return
-        if self._logprobs is not None:
-            self._logprob_update(logits, self.tokens)
-        if self._fsm is not None:
-            self._fsm_advance(self.tokens)
-        self.lengths.add_(1)
-        if self.history is not None:                                 # enable_drafting: the new token joins the text
-            self._record_step()
 
     def _step_attention(self, li, qkv):
         """single_query_attention of layer li on the step's qkv rows -> q_attn / q_scale / q_sum, quantised."""
@@ -1417,11 +1415,8 @@ class DecodeEngine:
             piecewise = self.tp_world > 1 and self.ar is None   # the direct all-reduce is an ordinary kernel: one graph
         self.pieces = None
         if not piecewise:
-            self.graph, _ = self._capture(self.step, 1)
-            self._graph_stops = self.stopping is not None    # (generate: does the captured step hold the stop launch?)
-            self._graph_logprobs, self._graph_keep = self._logprobs, (self._logprob_tensors(), self._fsm_tensors(), self._lora_tensors())   # (... and the log-probability launch?)
-            self._graph_fsm = self._fsm                      # (... and the automaton it masks with?)
-            self._graph_lora = self._lora                    # (... and the LoRA launches?)
+            self._step_capture = self._captured(self._capture(self.step, 1), 1)
+            self.graph = self._step_capture.graph
             return self.graph
         self._warm_up(self.step)
         pool = torch.cuda.graph_pool_handle()
@@ -1440,7 +1435,7 @@ class DecodeEngine:
                 break
             self._reduce(partial)             # keeps the data flow of the capture pass identical to a real step
         self.pieces = pieces
-        self.graph = None
+        self.graph = self._step_capture = None
         return pieces
 
     def check(self):

@@ -72,7 +72,8 @@ def capture_main():
         if i == 3:                                           # the same automaton, new states: no re-capture, the graph reads them
             for e in (cap, twin):
                 e.set_constraint(dfa, [3, 1, -1])
-            assert cap.speculate_graph is graph and cap._speculate_fsm is cap._fsm
+            made = cap._speculate_capture
+            assert cap.speculate_graph is graph and made.state["automaton"] is dfa and made.keep[1]["constraint"][0] is cap._fsm
         got = cap.run_speculate()
         want = twin.speculate(E.PAR)
         torch.cuda.synchronize()
@@ -111,7 +112,7 @@ def generate_main():
         assert len(t) == 5 and all(x % C == 3 and x != eos for x in t[:4]) and t[4] == eos, t
     assert reasons == [1, 1, 1] and e.fsm_state.tolist() == [sink] * 3 and rounds <= 6
     with_mask = e.graph
-    assert e._graph_fsm is e._fsm
+    assert e._step_capture.state["automaton"] is dfa and e._step_capture.keep[1]["constraint"][0] is e._fsm
     e.set_constraint(None)
     e.set_stopping([], [8, 8, 8])
     e.generate(2, poll_every=2)

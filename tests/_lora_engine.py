@@ -51,7 +51,7 @@ def capture_main():
     cap, twin = lora_engine(toks, MIXED), lora_engine(toks, MIXED)
     cap.capture()                                            # (its warm-up is a real step)
     twin.step()
-    assert cap._graph_lora is True and cap._graph_keep[2] is not None
+    assert cap._step_capture.state["lora"] is True and cap._step_capture.keep[1]["lora"] is not None
     E.assert_same_state(cap, twin, "after capture")
     graph = cap.graph
     for i in range(4):
@@ -73,7 +73,7 @@ def capture_main():
     cap.capture_speculate(E.PAR)
     twin.speculate(E.PAR)
     ref.speculate(E.PAR)
-    assert cap._speculate_lora is True
+    assert cap._speculate_capture.state["lora"] is True
     E.assert_same_state(cap, twin, "after capture_speculate")
     S.plant(ref, (cap, twin))                                # (ref runs under the same adapters: what it says next is what the twins will say)
     graph, longest = cap.speculate_graph, 0

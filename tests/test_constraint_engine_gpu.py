@@ -138,7 +138,7 @@ def test_start_states_of_every_integer_kind_and_the_tables_across_off(gpu):
     with pytest.raises(AssertionError, match="one per sequence"):
         e.set_constraint(dfa, [0, 1])
     e.set_constraint(None)
-    assert e._fsm is None and e._fsm_tensors() is None
+    assert e._fsm is None and e._kept_tensors()["constraint"] is None
     e.set_constraint(dfa, [2, -1, 0])
     assert e._fsm is tables and e.fsm_state is state and e.fsm_state.tolist() == [2, -1, 0]
     e.set_constraint(CE.automaton(), 1)

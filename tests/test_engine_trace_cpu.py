@@ -7,7 +7,9 @@ the sampler: token 0).  A trace line is the entry's name (without `qs_`), every 
 engine tensor whose storage holds the address, as `name+byte offset` - `layers[1].ln1`, `q_act`, `bufs.qa` (the `_prompt_buffers` of
 the running call), `tables[0]`, `history` ... -, `tmp` for anything else and `0` for null.  No address and no tensor value reaches the
 file.  The tree constants of `_tree_cache` are left unnamed on purpose: whether a verification builds or caches them is not part of the
-call sequence.
+call sequence.  Two seams above the C ABI add lines of their own: the `generate` scenario replaces the engine's `_capture(fn, advance)`
+with a stand-in that writes `capture`, calls fn once and replays by calling it again, so that generate / run / run_speculate run on the
+host; the LoRA scenario records the `lora_rows` calls where the engine makes them (the wrapper insists on a device workspace).
 
 The golden is a table of the distinct lines plus, per scenario, the indices into it.  `python tests/test_engine_trace_cpu.py --record
 [--decode FILE]` rewrites it; FILE is another revision of qserve_amd/decode.py to record from (it is loaded as a module of the
@@ -27,6 +29,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "engine_traces.json")
 PAR = [-1, 0, 0, 1, 1, 2]                      # six nodes, two branchings
 MAX_GOLDEN_BYTES = 72737                       # the largest golden the repository held before this one
+# what a capture notes about its graph (result, kept tensors, private buffers) - tuples under these names in the revisions that kept
+# it in engine attributes - is left unnamed like `_tree_cache`: where the engine keeps it is not part of the call sequence
+CAPTURE_BOOKKEEPING = ("_graph_", "_verify_", "_speculate_")
 
 
 # ---- the three stubs the engine goes on from ---------------------------------------------------------------------------------------
@@ -88,7 +93,7 @@ class Recorder:
     def _ranges(self):
         found = []
         for attr, v in vars(self.eng).items():
-            if attr != "_tree_cache":
+            if attr != "_tree_cache" and not attr.startswith(CAPTURE_BOOKKEEPING):
                 _tensors(v, attr, found)
         _tensors(self.bufs, "bufs", found)
         best = {}
@@ -131,7 +136,8 @@ def install(monkeypatch, decode_file=None):
     import qserve_amd.backend._util as U
     from qserve_amd._lib import SIGNATURES, lib
     F.install(monkeypatch)
-    mods = [importlib.import_module("qserve_amd." + m) for m in ("append", "sampling", "penalties", "drafting")]
+    mods = [importlib.import_module("qserve_amd." + m)
+            for m in ("append", "sampling", "penalties", "drafting", "stopping", "logprobs", "constraints", "lora")]
     if decode_file is None:
         D = importlib.import_module("qserve_amd.decode")
     else:
@@ -144,6 +150,7 @@ def install(monkeypatch, decode_file=None):
             if hasattr(m, attr):
                 monkeypatch.setattr(m, attr, getattr(U, attr))
     rec = Recorder()
+    rec.monkeypatch = monkeypatch
     for symbol, (_, argtypes) in SIGNATURES.items():
         fn = F.SYMBOLS.get(symbol) or STEERING.get(symbol) or (lambda *a: 0)
         monkeypatch.setattr(lib, symbol, rec.wrap(symbol, fn, argtypes), raising=True)
@@ -216,6 +223,101 @@ def _sampled_prefill(D, rec):
     eng.verify_tree(torch.zeros((2, len(PAR)), dtype=torch.int64), PAR, sampled=True)
 
 
+def _dfa():
+    """Four token classes (token % 4), three states; every state allows two of the classes."""
+    from qserve_amd.constraints import TokenDFA
+    nxt = [[(s + c) % 3 if (s + c) % 2 else -1 for c in range(4)] for s in range(3)]
+    return TokenDFA((torch.arange(512) % 4).to(torch.int16), torch.tensor(nxt, dtype=torch.int32))
+
+
+def _featured_engine(D, rec, stopping=False, logprobs=False, constraint=None, sampled=False):
+    """A drafting engine behind its prefill with the features switched on where each may be: the constraint (start states [0, -1]),
+    log-probabilities and sampling in front of the prefill - the prompt head masks, records and advances -, penalties and stopping
+    behind enable_drafting (set_stopping looks at the current token: the `check_root` call)."""
+    eng = _engine(D, rec, max_new=40)
+    toks = torch.randint(0, 512, (2 * 5,), generator=torch.Generator().manual_seed(1))
+    if sampled:
+        eng.set_sampling(0.8, top_k=5, top_p=0.9, seed=11)
+    if logprobs:
+        eng.set_logprobs(top=3)
+    if constraint is not None:
+        eng.set_constraint(constraint, [0, -1])
+    eng.prefill(5, toks)
+    eng.enable_drafting(toks, max_ngram=3, min_match=1, pad_token=7)
+    if sampled:
+        eng.set_penalties(1.2, 0.1, 0.1)
+    if stopping:
+        eng.set_stopping(stop=[3, [4, 5]], max_new_tokens=[6, 30])
+    return eng
+
+
+def _featured(D, rec, stopping=False, logprobs=False, constraint=False, sampled=False):
+    eng = _featured_engine(D, rec, stopping, logprobs, _dfa() if constraint else None, sampled)
+    eng.step()
+    eng.verify_tree(torch.zeros((2, len(PAR)), dtype=torch.int64), PAR, device_walk=True, sampled=sampled)
+    eng.speculate(PAR, sampled=sampled)
+
+
+class _Replay:
+    def __init__(self, fn):
+        self.replay = fn
+
+
+def _generate(D, rec):
+    """generate() over the stand-in for `_capture`: a `capture` line wherever the engine finds its graph missing or stale - and none
+    where it must not."""
+    dfa, other = _dfa(), _dfa()
+    eng = _featured_engine(D, rec, stopping=True, logprobs=True, constraint=dfa)
+
+    def capture(fn, advance):
+        rec.lines.append("capture")
+        res = fn()
+        eng._len_bound -= advance
+        return _Replay(fn), res
+
+    def captures(n, *args, **kw):
+        before = rec.lines.count("capture")
+        rec.lines.append("generate " + " ".join([*map(str, args), *(f"{k}={v}" for k, v in kw.items())]))
+        eng.generate(*args, **kw)
+        assert rec.lines.count("capture") - before == n, f"generate{args, kw}: {rec.lines.count('capture') - before} captures, not {n}"
+
+    eng._capture = capture
+    captures(1, 3, poll_every=2)                                         # no step graph yet
+    eng.set_logprobs(None)
+    captures(1, 1)                                                       # another state of set_logprobs
+    captures(1, 2, parents=PAR)                                          # no speculate graph yet
+    captures(0, 1, parents=PAR)
+    eng.set_constraint(dfa, [0, -1])                                     # the same automaton, new states: the tables stay
+    captures(0, 1)
+    captures(0, 1, parents=PAR)
+    eng.set_constraint(other, [0, -1])                                   # another automaton: other tables
+    captures(1, 1)
+    captures(1, 1, parents=PAR)
+    eng.set_constraint(None)                                             # off and back with no capture in between: the tables stay
+    eng.set_constraint(other, [0, -1])
+    captures(0, 1)
+    captures(0, 1, parents=PAR)
+    captures(1, 1, parents=[-1, 0, 1])                                   # another tree
+    eng.set_sampling(0.8, top_k=5, top_p=0.9, seed=11)
+    captures(1, 1, parents=[-1, 0, 1], sampled=True)                     # another head
+    captures(0, 1, parents=[-1, 0, 1], sampled=True)
+
+
+def _lora(D, rec):
+    """The `lora_rows` calls of a prefill, a step and a device-walk verification, at the Python seam."""
+    def lora_rows(out, x, x_scale, A, B, scaling, seq_adapter, rows_per_seq, seg_ends, workspace=None):
+        ranges = rec._ranges()
+        rec.lines.append("lora_rows " + " ".join(rec.pointer(t.data_ptr(), ranges) for t in (out, x, workspace)) + f" {rows_per_seq}")
+
+    rec.monkeypatch.setattr(D.loramod, "lora_rows", lora_rows)
+    eng = _engine(D, rec)
+    eng.enable_lora(2, 8)
+    eng.set_lora([0, -1])
+    eng.prefill(5)
+    eng.step()
+    eng.verify_tree(torch.zeros((2, len(PAR)), dtype=torch.int64), PAR, device_walk=True)
+
+
 SCENARIOS = {
     "per_channel_fused": lambda D, rec: _prefill_two_steps(D, rec, group_size=-1, fuse_pairs=True),
     "per_channel_op_by_op": lambda D, rec: _prefill_two_steps(D, rec, group_size=-1, fuse_pairs=False),
@@ -230,6 +332,13 @@ SCENARIOS = {
     "verify_tree_device_walk": lambda D, rec: _verify(D, rec, True),
     "sampled_penalised_step_verify_speculate": _sampled_penalised,
     "sampled_prefill_step_host_verify": _sampled_prefill,
+    "stopping_step_verify_speculate": lambda D, rec: _featured(D, rec, stopping=True),
+    "logprobs_step_verify_speculate": lambda D, rec: _featured(D, rec, logprobs=True),
+    "constraint_step_verify_speculate": lambda D, rec: _featured(D, rec, constraint=True),
+    "stopping_logprobs_constraint": lambda D, rec: _featured(D, rec, stopping=True, logprobs=True, constraint=True),
+    "stopping_logprobs_constraint_sampled_penalised": lambda D, rec: _featured(D, rec, True, True, True, sampled=True),
+    "generate_recaptures": _generate,
+    "lora_prefill_step_verify": _lora,
 }
 
 

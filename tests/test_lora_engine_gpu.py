@@ -51,7 +51,7 @@ def test_every_sequence_at_minus_one_is_the_engine_without_lora(gpu):
     E.assert_same_state(c, L.lora_engine(toks, [-1, -1, -1], chunk=16), "prefill_chunked")
     # ... and off again launches what an engine without it launches
     b.set_lora(None)
-    assert not b._lora and b._lora_tensors() is None
+    assert not b._lora and b._kept_tensors()["lora"] is None
     a.step()
     b.step()
     E.assert_same_state(a, b, "step after set_lora(None)")
