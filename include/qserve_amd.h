@@ -883,6 +883,36 @@ int qs_debug_copy_split_workspace(void* dst, size_t bytes);
  * no allocation, nothing but hipGetDevice; safe inside a stream capture.  QS_EINVAL: null output, no current device. */
 int qs_debug_rope_table_state(float base, int* slots_used, int* longest_len_for_base);
 
+/* ----------------------------------------------------------------------------------------------------------
+ * RoPE frequency profiles (no reference counterpart: the reference reads `rope_scaling` and never forwards it to its kernels).
+ * A profile stands in for a rotary base wherever one is passed: 64 float32 denominators denom[pair] and one float32 mscale, with
+ *     ang = (float)pos / denom[pair];   c = (float)cos((double)ang) * mscale;   s = (float)sin((double)ang) * mscale
+ * (float32 division as for a base, ONE float32 multiply; mscale == 1.0f is exact) - the single definition behind the profile's tables
+ * and every in-kernel evaluation; the rotation itself is the one of a base.  llama3, linear and YaRN scaling are such profiles
+ * (Python: qserve_amd.rope computes them from a config's rope_scaling).
+ *
+ * qs_rope_profile_register: *key_out = -(id + 1), a NEGATIVE float, to be passed as `rotary_base` / `rotary_embedding_base` of
+ * qs_apply_bias_rope_update_kv_cache, qs_append_rope_update_kv_cache, qs_append_tree_rope_update_kv_cache, qs_single_query_attention
+ * and qs_single_query_attention_quant - eagerly or inside a stream capture.  Ids are process-wide and content-addressed: the same 64
+ * denominators and mscale, bitwise, give the same key on every device; at most 8 profiles per process.  Registration is eager: it
+ * builds the profile's cos / sin table of `table_positions` rows (1 .. 32768) on the current device, on the NULL stream, and waits for
+ * it before publishing it; register once per device that uses the key.  Profile tables live beside the 8 slots of plain bases, not in
+ * them (qs_debug_rope_table_state does not see them), and are never freed or moved: captured graphs hold their addresses.  An eager
+ * call that needs more rows builds a longer table for the key (the old one stays alive); rows that no table covers - inside a capture,
+ * beyond the 32 768 rows of the writers' tables - are evaluated in the kernel from the profile's 64 denominators in device memory,
+ * with the same values.  Plain (positive) bases keep their code path and their bytes.
+ *
+ * QS_EINVAL with a message, nothing launched: null pointer; pairs != 64; table_positions outside 1 .. 32768; a denominator or mscale
+ * that is not positive and finite; a ninth distinct profile; a call inside a stream capture (or a table that cannot be allocated).
+ * Every entry that rotates returns QS_EINVAL for a negative base that is no registered key, and for a key on a device where it was
+ * not registered.
+ *
+ * qs_debug_rope_profile_state (tests): *profiles_used = profiles of the process, *longest_table_len = rows of the longest table of
+ * `key` on the current device (0: not a key, or not registered there).  Host only, read only; safe inside a stream capture.
+ * ---------------------------------------------------------------------------------------------------------- */
+int qs_rope_profile_register(const float* denom, int pairs /* must be 64 */, float mscale, int table_positions, float* key_out);
+int qs_debug_rope_profile_state(float key, int* profiles_used, int* longest_table_len);
+
 #ifdef __cplusplus
 }
 #endif

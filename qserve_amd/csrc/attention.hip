@@ -95,7 +95,7 @@ __global__ __launch_bounds__(TPB) void decode_attention_kernel(
     const _Float16* __restrict__ q, const _Float16* __restrict__ k, const _Float16* __restrict__ v,
     const int64_t* __restrict__ kv_pointers, const int* __restrict__ lengths, _Float16* __restrict__ out,
     int num_heads, int num_kv_heads, int64_t q_stride0, int64_t kv_stride0, int max_blocks, int timestep,
-    float rope_base) {
+    float rope_base, const float2* __restrict__ rope_tab) {   // rope_tab: a profile key's table (its head holds the profile), else unused
     constexpr int DHB = INT4 ? DH / 2 : DH;            // bytes per token per head
     constexpr int PAGE_BYTES = PAGE_TOK * DHB;         // 4 KiB / 8 KiB per head per page
     constexpr int NLD = PAGE_BYTES / (TPB * 16);       // 16-byte loads per thread per page (1 or 2)
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(TPB) void decode_attention_kernel(
     const _Float16* kb = k + (size_t)b * kv_stride0 + (size_t)hkv * DH;
     const _Float16* vb = v + (size_t)b * kv_stride0 + (size_t)hkv * DH;
     if (tid < 64) {
-        const RopeCS cs = rope_coef(tid, tl, rope_base, DH);
+        const RopeCS cs = rope_coef_any(tid, tl, rope_base, DH, rope_tab);
 #pragma unroll
         for (int h = 0; h < G; ++h) {
             _Float16 a, bb;
@@ -386,7 +386,7 @@ __global__ __launch_bounds__(TPB) void prefill_kv_kernel(_Float16* __restrict__ 
                                                          const int* __restrict__ padding_offset,
                                                          const int64_t* __restrict__ kv_pointers, int num_tokens,
                                                          int max_blocks, int head_num, int kv_head_num, int seq_len,
-                                                         float rope_base) {
+                                                         float rope_base, const float2* __restrict__ rope_tab) {
     constexpr int DHB = INT4 ? DH / 2 : DH;
     // grid.x = token, block = 4 waves; wave w loops over heads w, w+4, ... of the H q heads followed by Hkv "kv jobs"
     const int t = blockIdx.x;
@@ -396,7 +396,7 @@ __global__ __launch_bounds__(TPB) void prefill_kv_kernel(_Float16* __restrict__ 
     if (pos >= seq_lens[b]) return;
     const int n = (head_num + 2 * kv_head_num) * DH;
     _Float16* row = qkv + (size_t)t * n;
-    const RopeCS cs = rope_coef(lane, pos, rope_base, DH);
+    const RopeCS cs = rope_coef_any(lane, pos, rope_base, DH, rope_tab);
     for (int job = wave; job < head_num + kv_head_num; job += 4) {
         if (job < head_num) {
             _Float16* qh = row + job * DH;
@@ -558,7 +558,7 @@ __device__ __forceinline__ void rope_cs_at(const float2* __restrict__ rope_tab, 
         rope_cs_from_table(rope_tab, pos, dg, cs);
     } else {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) cs[j] = rope_coef(8 * dg + j, pos, rope_base, DH);
+        for (int j = 0; j < 8; ++j) cs[j] = rope_coef_any(8 * dg + j, pos, rope_base, DH, rope_tab);
     }
 }
 // the sequence of row t of a packed buffer: the largest b with cu_q[b] <= t (empty sequences are stepped over); -1 for a row of nobody
@@ -631,13 +631,16 @@ __global__ void padding_offsets_kernel(int* __restrict__ out, const int* __restr
     for (int i = threadIdx.x; i < end - beg; i += blockDim.x) out[beg + i] = off;
 }
 
-// family 3: the VALU kernel (no splits, no table: the plan has nothing to add)
+// family 3: the VALU kernel (no splits, no table: the plan has nothing to add; a profile key's table is asked for its head alone)
 template <bool INT4>
 int launch_decode(const DecodeArgs& a, const AttnPlan&) {
     QS_DECODE_LOCALS(a);
+    int tab_len = 0;
+    const float2* tab = base < 0.f ? qs_rope_table(base, max_pos, st, &tab_len) : nullptr;
+    if (base < 0.f && !tab) return QS_EINVAL;
 #define QS_LAUNCH_G(GG)                                                                                            \
     hipLaunchKernelGGL((decode_attention_kernel<GG, INT4>), grid, dim3(TPB), 0, st, q, k, v, kvp, len, out, H, Hkv, \
-                       qs, kvs, mb, timestep, base)
+                       qs, kvs, mb, timestep, base, tab)
     switch (G) {
         case 1: QS_LAUNCH_G(1); break;
         case 2: QS_LAUNCH_G(2); break;
@@ -795,8 +798,10 @@ extern "C" int qs_apply_bias_rope_update_kv_cache(void* qkv, const int32_t* seq_
     // the vectorised writer reads cos / sin from the library's table (positions < seq_len); without one (first call inside
     // a stream capture, all table slots taken) the per-lane form computes them in the kernel
     int tab_len = 0;
-    const float2* tab = g_attn_variant == 2 ? nullptr : qs_rope_table(rotary_embedding_base, seq_len, st, &tab_len);
-    if (tab && tab_len >= seq_len) {
+    const bool key = rotary_embedding_base < 0.f;      // a profile's key: its table always exists (its head holds the profile)
+    const float2* tab = g_attn_variant == 2 && !key ? nullptr : qs_rope_table(rotary_embedding_base, seq_len, st, &tab_len);
+    if (key && !tab) return QS_EINVAL;
+    if (tab && tab_len >= seq_len && g_attn_variant != 2) {
         if (int4_kv_cache)
             hipLaunchKernelGGL(prefill_kv_vec_kernel<true>, dim3(num_tokens), dim3(TPB), 0, st, (_Float16*)qkv, seq_lens,
                                padding_offset, kv_pointers, num_tokens, max_blocks, head_num, kv_head_num, seq_len, tab);
@@ -808,11 +813,11 @@ extern "C" int qs_apply_bias_rope_update_kv_cache(void* qkv, const int32_t* seq_
     if (int4_kv_cache)
         hipLaunchKernelGGL(prefill_kv_kernel<true>, dim3(num_tokens), dim3(TPB), 0, st, (_Float16*)qkv, seq_lens,
                            padding_offset, kv_pointers, num_tokens, max_blocks, head_num, kv_head_num, seq_len,
-                           rotary_embedding_base);
+                           rotary_embedding_base, tab);
     else
         hipLaunchKernelGGL(prefill_kv_kernel<false>, dim3(num_tokens), dim3(TPB), 0, st, (_Float16*)qkv, seq_lens,
                            padding_offset, kv_pointers, num_tokens, max_blocks, head_num, kv_head_num, seq_len,
-                           rotary_embedding_base);
+                           rotary_embedding_base, tab);
     return qs_launch_status("apply_bias_rope_update_kv_cache");
 }
 
@@ -837,8 +842,10 @@ static int append_writer(const char* what, void* qkv, const int32_t* cu_seqlens_
     //  of the library's few table slots; positions a table does not cover are evaluated in the kernel)
     int want = 2048, tab_len = 0;
     while (want < max_blocks * PAGE_TOK && want < 32768) want *= 2;
-    const float2* tab = g_attn_variant == 2 ? nullptr : qs_rope_table(rotary_base, want, st, &tab_len);
-    if (!tab) tab_len = 0;
+    const bool key = rotary_base < 0.f;                // a profile's key: its table always exists (its head holds the profile)
+    const float2* tab = g_attn_variant == 2 && !key ? nullptr : qs_rope_table(rotary_base, want, st, &tab_len);
+    if (key && !tab) return QS_EINVAL;
+    if (!tab || g_attn_variant == 2) tab_len = 0;
     if (tree_mask) {
         if (int4_kv_cache)
             hipLaunchKernelGGL(append_tree_kv_vec_kernel<true>, dim3(num_tokens), dim3(TPB), 0, st, (_Float16*)qkv, cu_seqlens_q, past_lens,

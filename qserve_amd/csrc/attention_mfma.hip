@@ -36,6 +36,7 @@
 #include "attn_host.h"
 #include "kv_quant.h"
 #include <mutex>
+#include <string.h>
 
 namespace {
 
@@ -87,6 +88,8 @@ typedef __attribute__((address_space(3))) const uint8_t* lds_u8;   // 32-bit LDS
 //       L = 1033 ... -12 % at L = 4096), 2 = no compute (DMA + waits only: results are wrong by design),
 //   4 = skip phase A (RoPE / new token: wrong by design), 32 = timeline trace (s_memtime stamps into the split workspace,
 //       scripts/trace_attn.py)
+//   64 = PROFILE, a product form: rope_base is a frequency profile's key (kv_quant.h rope_coef).  A compile-time flag, so that the
+//       plain-base instantiations (EXP = 0) are instruction for instruction the code they were before profiles existed.
 template <int G, int EXP = 0>
 __global__ __launch_bounds__(NWT * 64, 4) void decode_attention_mfma_kernel(
     const _Float16* __restrict__ q, const _Float16* __restrict__ k, const _Float16* __restrict__ v,
@@ -95,6 +98,7 @@ __global__ __launch_bounds__(NWT * 64, 4) void decode_attention_mfma_kernel(
     float rope_base, const float2* __restrict__ rope_tab, int rope_tab_len, int nsplit, float* __restrict__ ws,
     int8_t* __restrict__ qout, __half* __restrict__ qscale, __half* __restrict__ qrowsum, unsigned* __restrict__ qcounters,
     int kflags) {
+    constexpr bool PROFILE = (EXP & 64) != 0;
     __shared__ __attribute__((aligned(16))) uint8_t s_kv[2 * NW * 2 * USB];     // [K | V][wave][slot 0 / 1][2 KiB]
     __shared__ __attribute__((aligned(16))) _Float16 s_meta[NW][2][4][UT];      // [wave][slot]: k scale, k zero, v scale, v zero
     __shared__ __attribute__((aligned(16))) _Float16 s_q[G][DH];                // rotated q of the G heads
@@ -382,7 +386,7 @@ __global__ __launch_bounds__(NWT * 64, 4) void decode_attention_mfma_kernel(
                 cs.c = t.x;
                 cs.s = t.y;
             } else {
-                cs = rope_coef(lane, tl, rope_base, DH);
+                cs = rope_coef<PROFILE>(lane, tl, rope_base, DH, rope_tab);
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the raw q / k / v rows have landed (this wave's queue holds nothing else)
             stamp(7);  // (trace: service wave - q / k / v and the RoPE coefficients are here)
@@ -1011,10 +1015,11 @@ __global__ __launch_bounds__(DH) void decode_attention_merge_kernel(const float*
 
 // cos/sin table [max_pos][64] (float2), every entry double-evaluated and rounded once to float32: bit-identical to the
 // in-kernel path and to the oracle (oracle/kvattn.py rope_coef)
-__global__ void rope_table_kernel(float2* __restrict__ tab, int max_pos, float base) {
+// (a profile key as `base`: the profile already stands in the 64 entries in front of tab - rope_coef reads it there)
+__global__ void rope_table_kernel(float2* tab, int max_pos, float base) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= max_pos * 64) return;
-    const RopeCS cs = rope_coef(i & 63, i >> 6, base, DH);
+    const RopeCS cs = rope_coef_any(i & 63, i >> 6, base, DH, tab);
     tab[i] = make_float2(cs.c, cs.s);
 }
 
@@ -1029,7 +1034,149 @@ constexpr int ROPE_SLOTS = 8;
 RopeTable g_rope[16][ROPE_SLOTS];
 std::mutex g_rope_mutex;   // host state of the slots (several host threads may drive their own bound streams)
 
+// Frequency profiles (qs_rope_profile_register): 64 denominators and an mscale in place of a base, named by the key -(id + 1).  Ids are
+// process-wide and content-addressed; a profile's tables live HERE, beside the base slots above and under the same rule - never freed,
+// never moved, a longer one is a new entry.  Every table carries the profile in the ROPE_PROFILE_HEAD entries in front of row 0.
+constexpr int ROPE_PROFILES = 8, ROPE_PROFILE_TABLES = 12;
+struct RopeProfile {
+    float denom[64];
+    float mscale;
+    RopeTable tabs[16][ROPE_PROFILE_TABLES];      // [device][entry]: base = the key
+};
+RopeProfile g_profile[ROPE_PROFILES];
+int g_profiles = 0;
+
+int profile_of_key(float key) {                   // -(id + 1) -> id, -1 for anything else
+    const float idf = -key - 1.0f;
+    const int id = idf >= 0.f && idf < (float)ROPE_PROFILES ? (int)idf : -1;
+    return id >= 0 && id < g_profiles && (float)id == idf ? id : -1;
+}
+const RopeTable* longest_profile_table(const RopeProfile& p, int dev) {
+    const RopeTable* best = nullptr;
+    for (const RopeTable& r : p.tabs[dev])
+        if (r.tab && (!best || r.len > best->len)) best = &r;
+    return best;
+}
+// a table of `rows` positions for profile `id` on the current device, built on `st` and waited for (g_rope_mutex held, no capture)
+const RopeTable* build_profile_table(int id, int dev, int rows, hipStream_t st) {
+    RopeProfile& p = g_profile[id];
+    RopeTable* slot = nullptr;
+    for (RopeTable& r : p.tabs[dev])
+        if (!r.tab && !slot) slot = &r;
+    if (!slot) return nullptr;
+    float2 head[ROPE_PROFILE_HEAD];
+    for (int i = 0; i < ROPE_PROFILE_HEAD; ++i) head[i] = make_float2(p.denom[i], p.mscale);
+    void* mem = nullptr;
+    if (hipMalloc(&mem, ((size_t)rows * 64 + ROPE_PROFILE_HEAD) * sizeof(float2)) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    float2* tab = reinterpret_cast<float2*>(mem) + ROPE_PROFILE_HEAD;
+    bool ok = hipMemcpyAsync(mem, head, sizeof(head), hipMemcpyHostToDevice, st) == hipSuccess;
+    if (ok) hipLaunchKernelGGL(rope_table_kernel, dim3((rows * 64 + 255) / 256), dim3(256), 0, st, tab, rows, -(float)(id + 1));
+    if (!ok || hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {   // (also: `head` is read before we return)
+        (void)hipGetLastError();
+        (void)hipFree(mem);
+        return nullptr;
+    }
+    slot->len = rows, slot->base = -(float)(id + 1), slot->tab = tab;
+    return slot;
+}
+bool capturing(hipStream_t st) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess) {
+        (void)hipGetLastError();
+        return true;
+    }
+    return cs != hipStreamCaptureStatusNone;
+}
+// qs_rope_table for a key: the longest table of the profile on this device, a longer one first where the call is eager and asks for
+// more rows (the old one stays alive); rows a table does not cover are evaluated in the kernels from the table's head.  nullptr with
+// qs_last_error: no such profile, or not registered on this device.
+const float2* profile_table(float key, int max_pos, int dev, hipStream_t st, int* len_out) {
+    const int id = profile_of_key(key);
+    if (id < 0) {
+        qs_set_error("rotary base %g: a negative base is the key of a RoPE profile, and no profile with this key is registered", (double)key);
+        return nullptr;
+    }
+    const RopeTable* t = longest_profile_table(g_profile[id], dev);
+    if (!t) {
+        qs_set_error("rotary base %g: RoPE profile %d is not registered on device %d (qs_rope_profile_register on that device)", (double)key,
+                     id, dev);
+        return nullptr;
+    }
+    if (t->len < max_pos && !capturing(st)) {
+        const RopeTable* longer = build_profile_table(id, dev, max_pos, st);
+        if (longer) t = longer;
+    }
+    *len_out = t->len;
+    return t->tab;
+}
+
 }  // namespace
+
+extern "C" int qs_rope_profile_register(const float* denom, int pairs, float mscale, int table_positions, float* key_out) {
+    QS_REQUIRE(denom && key_out, "rope_profile_register: null pointer");
+    QS_REQUIRE(pairs == 64, "rope_profile_register: pairs=%d, only 64 (head_dim 128) is supported", pairs);
+    QS_REQUIRE(table_positions > 0 && table_positions <= 32768, "rope_profile_register: table_positions=%d not in 1 .. 32768", table_positions);
+    QS_REQUIRE(mscale > 0.f && mscale < INFINITY, "rope_profile_register: mscale must be positive and finite");
+    for (int i = 0; i < 64; ++i) QS_REQUIRE(denom[i] > 0.f && denom[i] < INFINITY, "rope_profile_register: denom[%d] must be positive and finite", i);
+    std::lock_guard<std::mutex> lock(g_rope_mutex);
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) {
+        (void)hipGetLastError();
+        qs_set_error("rope_profile_register: no current device");
+        return QS_EINVAL;
+    }
+    // The entry has no stream: the table is built on the NULL stream and waited for.  A capture of the NULL stream is seen here; under
+    // a capture of another stream the allocation below is what the runtime refuses (the error then names the capture as well).
+    hipStream_t st = nullptr;
+    if (capturing(st)) {
+        qs_set_error("rope_profile_register: called inside a stream capture - register before capturing (the table is built eagerly)");
+        return QS_EINVAL;
+    }
+    int id = -1;
+    for (int i = 0; i < g_profiles && id < 0; ++i)
+        if (!memcmp(g_profile[i].denom, denom, sizeof(float) * 64) && !memcmp(&g_profile[i].mscale, &mscale, sizeof(float))) id = i;
+    const bool fresh = id < 0;
+    if (fresh) {
+        if (g_profiles == ROPE_PROFILES) {
+            qs_set_error("rope_profile_register: all %d RoPE profiles of this process are taken", ROPE_PROFILES);
+            return QS_EINVAL;
+        }
+        id = g_profiles;
+        memcpy(g_profile[id].denom, denom, sizeof(float) * 64);
+        g_profile[id].mscale = mscale;
+        ++g_profiles;      // (taken back below if the first table cannot be built: nobody has seen the key)
+    }
+    const RopeTable* t = longest_profile_table(g_profile[id], dev);
+    if ((!t || t->len < table_positions) && !build_profile_table(id, dev, table_positions, st) && !t) {
+        if (fresh) --g_profiles;
+        qs_set_error("rope_profile_register: the table of %d positions could not be built on device %d (out of memory, or a stream "
+                     "capture in progress: register before capturing)", table_positions, dev);
+        return QS_EINVAL;
+    }
+    *key_out = -(float)(id + 1);
+    return QS_OK;
+}
+
+// tests: the profiles of the process and the longest table of `key` on the current device - read only, no device work
+extern "C" int qs_debug_rope_profile_state(float key, int* profiles_used, int* longest_table_len) {
+    QS_REQUIRE(profiles_used && longest_table_len, "debug_rope_profile_state: null output");
+    std::lock_guard<std::mutex> lock(g_rope_mutex);
+    int dev = 0;
+    *profiles_used = *longest_table_len = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) {
+        (void)hipGetLastError();
+        qs_set_error("debug_rope_profile_state: no current device");
+        return QS_EINVAL;
+    }
+    *profiles_used = g_profiles;
+    const int id = profile_of_key(key);
+    const RopeTable* t = id >= 0 ? longest_profile_table(g_profile[id], dev) : nullptr;
+    if (t) *longest_table_len = t->len;
+    return QS_OK;
+}
 
 // tests (include/qserve_amd.h): the table slots of the current device as qs_rope_table would find them - read only, no device work
 extern "C" int qs_debug_rope_table_state(float base, int* slots_used, int* longest_len_for_base) {
@@ -1053,12 +1200,18 @@ extern "C" int qs_debug_rope_table_state(float base, int* slots_used, int* longe
 
 // Library-managed RoPE table (per device, per base).  Returns nullptr when it cannot be (re)built right now, e.g.
 // while the stream is being captured into a graph before the first eager call; callers then compute in-kernel.
+// base < 0, the key of a frequency profile: nullptr is an ERROR (qs_last_error is set, the caller returns QS_EINVAL without a launch) -
+// a registered profile always has a table on its device, and the kernels find the profile in front of its row 0.
 const float2* qs_rope_table(float base, int max_pos, hipStream_t st, int* len_out) {
     std::lock_guard<std::mutex> lock(g_rope_mutex);
     int dev = 0;
     *len_out = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) {
+        if (base < 0.f) qs_set_error("rotary base %g: no current device", (double)base);
+        return nullptr;
+    }
     if (max_pos > 32768) max_pos = 32768;
+    if (base < 0.f) return profile_table(base, max_pos < 1 ? 1 : max_pos, dev, st, len_out);   // a profile's key: its own tables
     if (max_pos <= 0) return nullptr;
     RopeTable* slot = nullptr;
     for (int i = 0; i < ROPE_SLOTS; ++i) {
@@ -1202,6 +1355,7 @@ int qs_launch_decode_mfma(const DecodeArgs& a, const attn_plan::AttnPlan& plan) 
     int kflags = plan.kflags, exp_flags = plan.exp_flags;
     int tab_len = 0;
     const float2* tab = qs_rope_table(base, max_pos, st, &tab_len);
+    if (base < 0.f && !tab) return QS_EINVAL;      // a profile key that is not registered on this device (qs_last_error says which)
     const int blocks = (int)(grid.x * grid.y);
     const size_t per_split = attn_plan::decode_split_bytes(blocks, G);
     int nsplit = plan.nsplit > 1 ? attn_plan::fit_splits(plan.nsplit, per_split, qs_split_workspace_capacity(), attn_plan::NO_SPLIT_CAP) : 1;
@@ -1223,9 +1377,12 @@ int qs_launch_decode_mfma(const DecodeArgs& a, const attn_plan::AttnPlan& plan) 
         *fused = true;
         if (g_inject_fault & 2) kflags |= 64, g_inject_fault &= ~2;   // one-shot (qs_debug_inject_fault)
     }
-#define QS_LAUNCH_G(GG)                                                                                             \
-    hipLaunchKernelGGL((decode_attention_mfma_kernel<GG>), grid, dim3(NWT * 64), 0, st, q, k, v, kvp, len, out, H, Hkv, \
-                       qs, kvs, mb, timestep, base, tab, tab_len, nsplit, ws, qout, qscale, qsum, qcnt, kflags)
+#define QS_LAUNCH_GP(KERNEL)                                                                                                      \
+    hipLaunchKernelGGL((KERNEL), grid, dim3(NWT * 64), 0, st, q, k, v, kvp, len, out, H, Hkv, qs, kvs, mb, timestep, base, tab, tab_len, \
+                       nsplit, ws, qout, qscale, qsum, qcnt, kflags)
+#define QS_LAUNCH_G(GG)                                                \
+    if (base < 0.f) QS_LAUNCH_GP((decode_attention_mfma_kernel<GG, 64>));  \
+    else QS_LAUNCH_GP(decode_attention_mfma_kernel<GG>)
 #define QS_LAUNCH_EXP(E)                                                                                              \
     case E:                                                                                                            \
         hipLaunchKernelGGL((decode_attention_mfma_kernel<4, E>), grid, dim3(NWT * 64), 0, st, q, k, v, kvp, len, out, H,  \
@@ -1262,6 +1419,7 @@ int qs_launch_decode_mfma(const DecodeArgs& a, const attn_plan::AttnPlan& plan) 
             return QS_ENOSUP;
     }
 #undef QS_LAUNCH_G
+#undef QS_LAUNCH_GP
     if (nsplit > 1)
         hipLaunchKernelGGL(decode_attention_merge_kernel, dim3(H, grid.y), dim3(DH), 0, st, ws, out, H, Hkv, G, nsplit);
     return qs_launch_status("single_query_attention");

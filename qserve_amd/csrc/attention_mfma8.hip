@@ -47,8 +47,10 @@ constexpr int NT_AUX = QS_KV8_NT ? 2 : 0;
 typedef __attribute__((address_space(3))) const uint8_t* lds_u8;   // 32-bit LDS address (keeps ds_read, not flat_load)
 #define LDS_AT(T, p) (*(const __attribute__((address_space(3))) T*)(p))
 
-template <int G>
-__global__ __launch_bounds__(NW * 64, 2) void decode_attention_mfma8_kernel(
+// The body of the two kernels below.  PROFILE: rope_base is a frequency profile's key (kv_quant.h rope_coef) - the plain-base kernel keeps
+// its name and the code it always had, the profile form is a kernel of its own (decode_profile_mfma8).
+template <int G, bool PROFILE>
+__device__ __forceinline__ void decode_attention_mfma8_body(
     const _Float16* __restrict__ q, const _Float16* __restrict__ k, const _Float16* __restrict__ v,
     const int64_t* __restrict__ kv_pointers, const int* __restrict__ lengths, _Float16* __restrict__ out,
     int num_heads, int num_kv_heads, int64_t q_stride0, int64_t kv_stride0, int max_blocks, int timestep,
@@ -131,7 +133,7 @@ __global__ __launch_bounds__(NW * 64, 2) void decode_attention_mfma8_kernel(
             cs.c = t.x;
             cs.s = t.y;
         } else {
-            cs = rope_coef(tid, tl, rope_base, DH);
+            cs = rope_coef<PROFILE>(tid, tl, rope_base, DH, rope_tab);
         }
 #pragma unroll
         for (int h = 0; h < G; ++h) {
@@ -475,6 +477,25 @@ __global__ __launch_bounds__(NW * 64, 2) void decode_attention_mfma8_kernel(
     }
 }
 
+template <int G>
+__global__ __launch_bounds__(NW * 64, 2) void decode_attention_mfma8_kernel(
+    const _Float16* __restrict__ q, const _Float16* __restrict__ k, const _Float16* __restrict__ v,
+    const int64_t* __restrict__ kv_pointers, const int* __restrict__ lengths, _Float16* __restrict__ out,
+    int num_heads, int num_kv_heads, int64_t q_stride0, int64_t kv_stride0, int max_blocks, int timestep,
+    float rope_base, const float2* __restrict__ rope_tab, int rope_tab_len, int nsplit, float* __restrict__ ws) {
+    decode_attention_mfma8_body<G, false>(q, k, v, kv_pointers, lengths, out, num_heads, num_kv_heads, q_stride0, kv_stride0, max_blocks, timestep,
+                                            rope_base, rope_tab, rope_tab_len, nsplit, ws);
+}
+template <int G>
+__global__ __launch_bounds__(NW * 64, 2) void decode_profile_mfma8(
+    const _Float16* __restrict__ q, const _Float16* __restrict__ k, const _Float16* __restrict__ v,
+    const int64_t* __restrict__ kv_pointers, const int* __restrict__ lengths, _Float16* __restrict__ out,
+    int num_heads, int num_kv_heads, int64_t q_stride0, int64_t kv_stride0, int max_blocks, int timestep,
+    float rope_base, const float2* __restrict__ rope_tab, int rope_tab_len, int nsplit, float* __restrict__ ws) {
+    decode_attention_mfma8_body<G, true>(q, k, v, kv_pointers, lengths, out, num_heads, num_kv_heads, q_stride0, kv_stride0, max_blocks, timestep,
+                                            rope_base, rope_tab, rope_tab_len, nsplit, ws);
+}
+
 }  // namespace
 
 // called from attention.hip's dispatcher for KV8 with its plan (nsplit: fewer where the split workspace cannot hold them)
@@ -482,15 +503,19 @@ int qs_launch_decode_mfma8(const DecodeArgs& a, const attn_plan::AttnPlan& plan)
     QS_DECODE_LOCALS(a);
     int tab_len = 0;
     const float2* tab = qs_rope_table(base, max_pos, st, &tab_len);
+    if (base < 0.f && !tab) return QS_EINVAL;      // a profile key that is not registered on this device (qs_last_error says which)
     const int blocks = (int)(grid.x * grid.y);
     const size_t per_split = attn_plan::decode_split_bytes(blocks, G);
     int nsplit = plan.nsplit > 1 ? attn_plan::fit_splits(plan.nsplit, per_split, qs_split_workspace_capacity(), attn_plan::NO_SPLIT_CAP) : 1;
     float* ws = nsplit > 1 ? qs_split_workspace(per_split * nsplit, st) : nullptr;
     if (!ws) nsplit = 1;
     grid.z = nsplit;
-#define QS_LAUNCH_G(GG)                                                                                              \
-    hipLaunchKernelGGL((decode_attention_mfma8_kernel<GG>), grid, dim3(NW * 64), 0, st, q, k, v, kvp, len, out, H, Hkv, \
-                       qs, kvs, mb, timestep, base, tab, tab_len, nsplit, ws)
+#define QS_LAUNCH_GP(KERNEL)                                                                                                       \
+    hipLaunchKernelGGL((KERNEL), grid, dim3(NW * 64), 0, st, q, k, v, kvp, len, out, H, Hkv, qs, kvs, mb, timestep, base, tab, tab_len, \
+                       nsplit, ws)
+#define QS_LAUNCH_G(GG)                                      \
+    if (base < 0.f) QS_LAUNCH_GP(decode_profile_mfma8<GG>);  \
+    else QS_LAUNCH_GP(decode_attention_mfma8_kernel<GG>)
     switch (G) {
         case 1: QS_LAUNCH_G(1); break;
         case 2: QS_LAUNCH_G(2); break;
@@ -505,6 +530,7 @@ int qs_launch_decode_mfma8(const DecodeArgs& a, const attn_plan::AttnPlan& plan)
             return QS_ENOSUP;
     }
 #undef QS_LAUNCH_G
+#undef QS_LAUNCH_GP
     if (nsplit > 1) qs_launch_attention_merge(ws, out, H, Hkv, G, nsplit, (int)grid.y, st);
     return qs_launch_status("single_query_attention");
 }

@@ -21,14 +21,30 @@ struct RopeCS {
 };
 // cos/sin of pos / base^(2i/dim): every step rounded to float32 from a double evaluation, so that host oracle and
 // device agree bit for bit (the reference's fast-math __powf/__cosf are not reproducible anyway).
-__device__ __forceinline__ RopeCS rope_coef(int pair, int pos, float base, int dim) {
-    const float expo = (float)(2 * pair) / (float)dim;
-    const float denom = (float)pow((double)base, (double)expo);
+// PROFILE: `base` is the key of a registered frequency profile (a negative float; qs_rope_profile_register, include/qserve_amd.h),
+// `tab` is row 0 of one of the profile's tables, and the 64 float2 in FRONT of row 0 are the profile itself - .x = denom[pair],
+// .y = mscale -, which stand in for pow(): ang = pos / denom[pair], cos and sin as for a base, then ONE float32 multiply by mscale.
+// A compile-time switch, so that the code of a plain base is the code it always was; rope_coef_any chooses by the sign of the base.
+constexpr int ROPE_PROFILE_HEAD = 64;   // float2 entries in front of row 0 of a profile's table
+template <bool PROFILE = false>
+__device__ __forceinline__ RopeCS rope_coef(int pair, int pos, float base, int dim, const float2* __restrict__ tab = nullptr) {
+    float denom, mscale = 1.0f;
+    if constexpr (PROFILE) {
+        const float2 prof = tab[pair - ROPE_PROFILE_HEAD];
+        denom = prof.x, mscale = prof.y;
+    } else {
+        const float expo = (float)(2 * pair) / (float)dim;
+        denom = (float)pow((double)base, (double)expo);
+    }
     const float ang = (float)pos / denom;
     RopeCS r;
     r.c = (float)cos((double)ang);
     r.s = (float)sin((double)ang);
+    if constexpr (PROFILE) r.c *= mscale, r.s *= mscale;
     return r;
+}
+__device__ __forceinline__ RopeCS rope_coef_any(int pair, int pos, float base, int dim, const float2* __restrict__ tab) {
+    return base < 0.f ? rope_coef<true>(pair, pos, base, dim, tab) : rope_coef<false>(pair, pos, base, dim);
 }
 __device__ __forceinline__ void rope_pair(float a, float b, RopeCS cs, _Float16& oa, _Float16& ob) {
 #pragma clang fp contract(off)

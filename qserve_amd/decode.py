@@ -34,6 +34,7 @@ from . import fused as fusedmod
 from . import logprobs as logprobsmod
 from . import lora as loramod
 from . import penalties as penaltiesmod
+from . import rope as ropemod
 from . import sampling as samplingmod
 from . import stopping as stoppingmod
 from . import tp as tpmod
@@ -65,6 +66,9 @@ def _tree_depths(par):
 
 LLAMA3_8B = dict(name="Llama-3-8B", hidden=4096, heads=32, kv_heads=8, inter=14336, layers=32, vocab=128256,
                  rope_theta=5e5, eps=1e-5)
+LLAMA31_8B = dict(LLAMA3_8B, name="Llama-3.1-8B",
+                  rope_scaling=dict(rope_type="llama3", factor=8.0, low_freq_factor=1.0, high_freq_factor=4.0,
+                                    original_max_position_embeddings=8192))
 QWEN15_72B = dict(name="Qwen1.5-72B", hidden=8192, heads=64, kv_heads=64, inter=24576, layers=80, vocab=152064,
                   rope_theta=1e6, eps=1e-6, qkv_bias=True)     # attention_bias: q/k/v projections carry a bias
 LLAMA2_7B = dict(name="Llama-2-7B", hidden=4096, heads=32, kv_heads=32, inter=11008, layers=32, vocab=32000,
@@ -211,6 +215,14 @@ class DecodeEngine:
         # ---- paged KV pools (cache_engine.py:59-115) and pointer tables (model_runner.py:396-414)
         self.max_len = prompt_len + max_new
         self.mb = (self.max_len + 63) // 64 + 1            # README.md:369 page budget rule (+1 page)
+        # ---- what every rotating call takes as its rotary base: cfg["rope_theta"], or - with a `rope_scaling` (llama3, linear, yarn) - the
+        # key of its frequency profile (qserve_amd/rope.py), registered on this engine's device with a table over max_len rounded up to 64
+        # (content-addressed: every tensor-parallel rank gets the same key on its own device)
+        self.rope_base = cfg["rope_theta"]
+        prof = ropemod.profile(cfg["rope_theta"], cfg.get("rope_scaling"), cfg.get("max_pos"))
+        if prof is not None:
+            with torch.cuda.device(self.dev):
+                self.rope_base = ropemod.register(prof[0], prof[1], (self.max_len + 63) // 64 * 64)
         dhb = 64 if int4_kv else 128
         self.size_per_token = self.Hkv * dhb
         self.page_bytes = self.Hkv * 64 * dhb + 64 * self.Hkv * 4
@@ -388,7 +400,7 @@ class DecodeEngine:
             work = qkv if li == 0 else (qkv * (1.0 + 0.01 * li)).half()
             fused_attention.apply_bias_rope_update_kv_cache(
                 work, seq, pad, self.tables[li], self.H, self.Hkv, prompt_len, 64, self.size_per_token, 128,
-                self.cfg["rope_theta"], 8192, True, self.int4, True)
+                self.rope_base, 8192, True, self.int4, True)
         self.lengths.fill_(prompt_len + 1)
         self._len_bound = prompt_len + 1
         torch.cuda.synchronize()
@@ -567,7 +579,7 @@ class DecodeEngine:
         def attend(li, qkv):
             fused_attention.apply_bias_rope_update_kv_cache(
                 qkv, seq, pad, self.tables[li], self.H, self.Hkv, prompt_len, 64, self.size_per_token, 128,
-                cfg["rope_theta"], 8192, True, self.int4, True)
+                self.rope_base, 8192, True, self.int4, True)
             q, k, v = qkv.split([self.H * 128, self.Hkv * 128, self.Hkv * 128], dim=-1)
             return flash_attn_varlen_func(q.reshape(T, self.H, 128), k.reshape(T, self.Hkv, 128),
                                           v.reshape(T, self.Hkv, 128), cu, cu, prompt_len, prompt_len, dropout_p=0.0,
@@ -594,7 +606,7 @@ class DecodeEngine:
         chunk = min(chunk, prompt_len)
 
         def attend(li, qkv, cu, past, n, c0):
-            return appendmod.append(qkv, cu, past, self.tables[li], self.H, self.Hkv, self.size_per_token, cfg["rope_theta"], self.int4,
+            return appendmod.append(qkv, cu, past, self.tables[li], self.H, self.Hkv, self.size_per_token, self.rope_base, self.int4,
                                     max_seqlen_q=n, max_past=c0)
 
         h = self._prompt_chunks(tokens.view(B, prompt_len), chunk, self._prompt_buffers(B * chunk), 0, attend)
@@ -642,7 +654,7 @@ class DecodeEngine:
         bufs = self._prompt_buffers(max(B * min(chunk, R), min(chunk, P64)))
         # 1. the whole pages of the prefix, once, through row 0 of the tables
         def attend_prefix(li, qkv, cu, past, n, c0):
-            return appendmod.append(qkv, cu, past, self.tables[li][0:1], self.H, self.Hkv, self.size_per_token, cfg["rope_theta"],
+            return appendmod.append(qkv, cu, past, self.tables[li][0:1], self.H, self.Hkv, self.size_per_token, self.rope_base,
                                     self.int4, max_seqlen_q=n, max_past=c0)
 
         self._prompt_chunks(prefix_tokens[:P64].unsqueeze(0), chunk, bufs, 0, attend_prefix)
@@ -653,7 +665,7 @@ class DecodeEngine:
         groups = appendmod.shared_prefix_groups([B], [P64], dev, batch=B)
 
         def attend_own(li, qkv, cu, past, n, c0):
-            return appendmod.append_shared(qkv, cu, past, self.tables[li], self.H, self.Hkv, self.size_per_token, cfg["rope_theta"],
+            return appendmod.append_shared(qkv, cu, past, self.tables[li], self.H, self.Hkv, self.size_per_token, self.rope_base,
                                            self.int4, groups, max_seqlen_q=n, max_group_tokens=B * n, max_prefix=P64, max_suffix_past=c0)
 
         h = self._prompt_chunks(own, chunk, bufs, P64, attend_own)
@@ -795,7 +807,7 @@ class DecodeEngine:
 
         def attend(li, qkv):
             return appendmod.append_tree(qkv, cu, past, self.tables[li], masks, self.H, self.Hkv, self.size_per_token,
-                                         cfg["rope_theta"], self.int4, max_seqlen_q=n, max_past=max_past).reshape(B * n, -1)
+                                         self.rope_base, self.int4, max_seqlen_q=n, max_past=max_past).reshape(B * n, -1)
 
         self._prompt_layers(h, self._prompt_buffers(B * n), attend)
         final = torch.empty_like(h)
@@ -1342,10 +1354,10 @@ class DecodeEngine:
         if self.fuse_pairs:  # attention + invoke_quant(_fuse_sum) of its output in one call (bit-identical pair fusion)
             fusedmod.single_query_attention_quant(
                 q, k, v, self.tables[li], self.lengths, self.q_attn, self.q_scale, 8192, 64, self.size_per_token, self.max_len, 128,
-                cfg["rope_theta"], True, self.int4, True, quant_sum=self.q_sum if self.group_size == -1 else None)
+                self.rope_base, True, self.int4, True, quant_sum=self.q_sum if self.group_size == -1 else None)
         else:
             attn = fused_attention.single_query_attention(
-                q, k, v, self.tables[li], self.lengths, None, 8192, 64, self.size_per_token, self.max_len, 128, cfg["rope_theta"], True,
+                q, k, v, self.tables[li], self.lengths, None, 8192, 64, self.size_per_token, self.max_len, 128, self.rope_base, True,
                 self.int4, True)
             self._quant(self.q_attn, attn.reshape(B, -1), self.q_sum, self.q_scale)
 
