@@ -870,6 +870,65 @@ int qs_lora_rows(void* out, int64_t out_stride, const int8_t* x, int64_t x_strid
                  const float* scaling, const int32_t* seq_adapter, int slots, int T, int K, int N, int r, int rows_per_seq, int nseg,
                  int seg_end0, int seg_end1, int seg_end2, void* workspace, int64_t workspace_size, qs_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------------------------
+ * Mixture-of-experts layers over the W4A8 linears (no reference counterpart: the reference's Mixtral block raises before routing -
+ * its MoE kernels and `moe_helpers` were never released).  Pipeline of one sparse MLP on T token rows, E experts, k experts per token,
+ * P = T k (token, expert) pairs:  qs_moe_route -> grouped gate_up GEMM (row_src = pair_token) -> qs_silu_and_mul_quant over the P
+ * sorted rows -> grouped down GEMM -> qs_moe_combine.  Nothing is read back: every routing value stays on the device, every grid is
+ * sized from (T, E, k, N, K), so the pipeline can be captured in a hipGraph.  Python: qserve_amd.moe; numpy restatement:
+ * tests/_moe_cases.py.
+ *
+ * qs_moe_route (csrc/moe_route.hip): logits fp16 [T, E], row stride `logits_stride` elements, finite.  Per token the k largest
+ * logits ordered by (value descending, expert index ascending), compared as the fp16 values they are: ties of any size go to the
+ * lower index.  weights: softmax over all experts renormalised over the chosen k (the Mixtral rule) = softmax over the k chosen
+ * logits l_0 >= l_1 >= ..., float32 op by op:  e_j = expf(float(l_j) - float(l_0));  s = ((e_0 + e_1) + ...) + e_{k-1};
+ * w_j = e_j / s (IEEE division).  Outputs: expert_ids int32 [T, k]; weights float32 [T, k]; expert_offsets int32 [E + 1], the
+ * exclusive prefix of the experts' pair counts (expert_offsets[E] = P); pair_token int32 [P], the source token of every position of
+ * the expert-sorted order; pair_pos int32 [T, k], the sorted position of pair (t, j).  The sort is stable: inside an expert the pairs
+ * are ordered by (t, j).  No atomic decides an output: results are bit-identical from run to run and under graph replay.  One launch
+ * for T <= 256 and P <= 2048, four otherwise (select, per-chunk counts, scan, scatter) with the counts in `workspace`;
+ * qs_moe_route_workspace gives the bytes a call needs (>= 16).  T == 0 writes the (all zero) offsets.
+ * QS_EINVAL before any device call: null pointer; T outside 0 .. 2^24; E outside 1 .. 64; k outside 1 .. min(E, 8); P > 2^24;
+ * logits_stride < E; logits not 2-byte or another tensor not 4-byte aligned; a workspace that is too small.
+ *
+ * qs_w4a8_per_chn_moe_gemm / qs_w4a8_per_group_moe_gemm (csrc/gemm_w4a8_moe.hip): for every sorted position p < P, with e the expert
+ * whose range expert_offsets[e] <= p < expert_offsets[e + 1] holds p:  out[p, :] = W[e] x[row_src[p], :]  (row_src == NULL: x row p).
+ * Weights: the reference's packed layout stacked over experts - qweight int8 [E, N, K/2], wscales (s1_scales) / w_szs (s1_szeros)
+ * fp16 [E, N], per-group zeros (s2_zeros) / scales_i8 (s2_scales) int8 [E, K/128, N].  x int8 [x_rows, K] with row stride x_stride;
+ * ascales / a_ssums fp16 [x_rows], indexed by the SOURCE row; out fp16 [P, N] with row stride out_stride.  Arithmetic of the dense
+ * entries: exact int32 accumulation, the per-channel epilogue of the convention qs_set_gemm_epilogue selects at launch time, the
+ * per-group epilogue of qs_w4a8_per_group_gemm - out[p] equals, bit for bit, the dense entry on expert e's tensors and that row.
+ * A workgroup owns (expert, 64 channels, 16 mt sorted rows) and finds its expert from expert_offsets itself; the grid is the bound
+ * ceil(P / (16 mt)) + E - 1 of qs_moe_gemm_plan, surplus workgroups leave at once, rows beyond an expert's range are not stored; rows
+ * >= P of out and columns >= N of a padded row are never written.  Device inputs cannot move an access: offsets are clamped into
+ * [0, P] (a range that runs backwards is empty), row_src values into [0, x_rows - 1].
+ * QS_EINVAL before any device call: null pointer (row_src may be null); P outside 0 .. 2^21; E outside 1 .. 64; N not a multiple of
+ * 64 or > 2^22; K not a multiple of 128 or > 2^20; x_stride < K or not a multiple of 16; out_stride < N or not a multiple of 8;
+ * x_rows < 1, > 2^24, or < P without row_src; x, qweight or out not 16-byte, the weight scales not 8-byte, zeros / scales_i8 /
+ * expert_offsets / row_src not 4-byte, the activation scales not 2-byte aligned.  P == 0: QS_OK, no launch.
+ * qs_moe_gemm_plan: plan4 = {mt, waves per workgroup, row blocks launched, 64-channel units} - a pure function of (P, E, N, K)
+ * (csrc/moe_plan.h); every plan computes the same bits.
+ *
+ * qs_moe_combine (csrc/moe_route.hip): out[t, :] = half(sum_j weights[t, j] * float(y[pair_pos[t, j], :])) for t < T: float32, j
+ * ascending, the first product alone and each further one added to it, multiply and add rounded separately (no contraction), one
+ * rounding to fp16.  y fp16 [T k, N] / out fp16 [T, N] with row strides; pair_pos values are clamped into [0, T k - 1].
+ * QS_EINVAL before any device call: null pointer; T outside 0 .. 2^24; k outside 1 .. 8; N not a multiple of 64 in 64 .. 2^22; a
+ * stride < N or not a multiple of 8; out or y not 16-byte, weights or pair_pos not 4-byte aligned.  T == 0: QS_OK, no launch.
+ * ---------------------------------------------------------------------------------------------------------- */
+int64_t qs_moe_route_workspace(int T, int E, int k);
+int qs_moe_route(const void* logits, int64_t logits_stride, int T, int E, int k, int32_t* expert_ids, float* weights,
+                 int32_t* expert_offsets, int32_t* pair_token, int32_t* pair_pos, void* workspace, int64_t workspace_size,
+                 qs_stream_t stream);
+int qs_moe_gemm_plan(int P, int E, int N, int K, int* plan4);
+int qs_w4a8_per_chn_moe_gemm(const int8_t* x, int64_t x_stride, int x_rows, const int32_t* row_src, const int32_t* expert_offsets,
+                             const int8_t* qweight, const void* wscales, const void* ascales, const void* w_szs, const void* a_ssums,
+                             void* out, int64_t out_stride, int P, int E, int N, int K, qs_stream_t stream);
+int qs_w4a8_per_group_moe_gemm(const int8_t* x, int64_t x_stride, int x_rows, const int32_t* row_src, const int32_t* expert_offsets,
+                               const int8_t* qweight, const int8_t* zeros, const int8_t* scales_i8, const void* wscales,
+                               const void* ascales, void* out, int64_t out_stride, int P, int E, int N, int K, qs_stream_t stream);
+int qs_moe_combine(void* out, int64_t out_stride, const void* y, int64_t y_stride, const float* weights, const int32_t* pair_pos, int T,
+                   int k, int N, qs_stream_t stream);
+
 /* Timing tool (scripts/trace_attn.py): device-to-device copy of the first `bytes` of the split-KV workspace, where the
  * trace instantiation of the KV4 decode attention (qs_set_attention_variant(232)) leaves its s_memtime stamps.
  * (A library built with -DQS_RING_TRACE additionally exports qs_debug_ring_trace(void* buf) for scripts/trace_gemm.py;

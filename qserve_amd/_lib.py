@@ -99,6 +99,12 @@ SIGNATURES = {
     "qs_constrain_advance": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
     "qs_lora_rows_workspace": (_i64, [_i, _i, _i, _i]),
     "qs_lora_rows": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp]),
+    "qs_moe_route_workspace": (_i64, [_i, _i, _i]),
+    "qs_moe_route": (_i, [_vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "qs_moe_gemm_plan": (_i, [_i, _i, _i, _i, _vp]),
+    "qs_w4a8_per_chn_moe_gemm": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
+    "qs_w4a8_per_group_moe_gemm": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
+    "qs_moe_combine": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _i, _i, _i, _vp]),
 }
 
 

@@ -33,6 +33,7 @@ from . import drafting as draftingmod
 from . import fused as fusedmod
 from . import logprobs as logprobsmod
 from . import lora as loramod
+from . import moe as moemod
 from . import penalties as penaltiesmod
 from . import rope as ropemod
 from . import sampling as samplingmod
@@ -77,6 +78,10 @@ LLAMA2_70B = dict(name="Llama-2-70B", hidden=8192, heads=64, kv_heads=8, inter=2
                   rope_theta=1e4, eps=1e-5)
 TINY = dict(name="tiny-llama", hidden=256, heads=4, kv_heads=2, inter=512, layers=2, vocab=512, rope_theta=1e4,
             eps=1e-5)
+# sparse MLPs (qserve_amd.moe): `experts` experts per layer, `experts_per_token` of them per token; `inter` is one expert's width
+MIXTRAL_8X7B = dict(name="Mixtral-8x7B", hidden=4096, heads=32, kv_heads=8, inter=14336, layers=32, vocab=32000, rope_theta=1e6,
+                    eps=1e-5, experts=8, experts_per_token=2)
+TINY_MOE = dict(TINY, name="tiny-moe", experts=4, experts_per_token=2)
 
 
 class W4A8Linear:
@@ -164,8 +169,18 @@ class DecodeEngine:
                  tp_rank=0, tp_world=1, with_lm_head=True, fuse_pairs=True, weights=None, vocab_parallel=True, planes=None,
                  direct_allreduce=None):
         """weights: None = synthetic random-quantised tensors of the right shapes; otherwise this rank's tensors as
-        qserve_amd.loader.load_llama_w4a8 returns them (checkpoint path)."""
+        qserve_amd.loader.load_llama_w4a8 returns them (checkpoint path).  A config with `experts` and `experts_per_token`
+        (MIXTRAL_8X7B, TINY_MOE) builds mixture-of-experts layers: a router `gate` fp16 [E, hid] and two `moe.MoELinear`s in place of
+        gate_up / down (weights: qserve_amd.loader.load_mixtral_w4a8); every path then runs `moe.moe_mlp` in the MLP branch of the layer
+        body.  Single GPU."""
         self.cfg, self.B, self.dev = cfg, batch, torch.device(device)
+        # mixture of experts: (experts, experts per token), or None for a dense model - which launches exactly what it always did
+        self.moe = (int(cfg["experts"]), int(cfg["experts_per_token"])) if cfg.get("experts") else None
+        if self.moe is not None:
+            assert tp_world == 1, \
+                "DecodeEngine: a mixture-of-experts config runs on one GPU - neither expert nor tensor parallelism of the experts is built"
+            assert 1 <= self.moe[1] <= min(self.moe[0], moemod.MAX_TOP_K) and self.moe[0] <= moemod.MAX_EXPERTS, \
+                f"DecodeEngine: experts={self.moe[0]} (<= {moemod.MAX_EXPERTS}), experts_per_token={self.moe[1]} (1 .. min(experts, {moemod.MAX_TOP_K}))"
         # fuse_pairs: issue (residual add + layer norm) and (silu_and_mul + quant) as one launch each
         # (qserve_amd/fused.py: bit-identical to the op pairs; False = the reference's exact op-by-op sequence)
         self.fuse_pairs = fuse_pairs
@@ -191,9 +206,14 @@ class DecodeEngine:
                     ln2=(torch.rand((hid,), device=self.dev, generator=gen) + 0.5).half(),
                     qkv=W4A8Linear(self.qkv_n, hid, group_size, self.dev, gen, bias=bool(cfg.get("qkv_bias"))),
                     o=W4A8Linear(hid, self.H * 128, group_size, self.dev, gen),
-                    gate_up=W4A8Linear(2 * inter, hid, group_size, self.dev, gen),
-                    down=W4A8Linear(hid, inter, group_size, self.dev, gen),
                 ))
+                if self.moe is None:
+                    self.layers[-1].update(gate_up=W4A8Linear(2 * inter, hid, group_size, self.dev, gen),
+                                           down=W4A8Linear(hid, inter, group_size, self.dev, gen))
+                else:
+                    self.layers[-1].update(gate=(torch.randn((self.moe[0], hid), device=self.dev, generator=gen) * hid ** -0.5).half(),   # logits of order 1
+                                           gate_up=moemod.MoELinear(self.moe[0], 2 * inter, hid, group_size, self.dev, gen),
+                                           down=moemod.MoELinear(self.moe[0], hid, inter, group_size, self.dev, gen))
             self.norm_w = (torch.rand((hid,), device=self.dev, generator=gen) + 0.5).half()
             if with_lm_head:
                 self.embed = (torch.randn((cfg["vocab"], hid), device=self.dev, generator=gen) * 0.05).half()
@@ -205,9 +225,16 @@ class DecodeEngine:
                     ln1=L["ln1"].to(self.dev), ln2=L["ln2"].to(self.dev),
                     qkv=W4A8Linear.from_tensors(to(L["qkv"]), group_size),
                     o=W4A8Linear.from_tensors(to(L["o"]), group_size, defer_bias=tp_world > 1),
-                    gate_up=W4A8Linear.from_tensors(to(L["gate_up"]), group_size),
-                    down=W4A8Linear.from_tensors(to(L["down"]), group_size, defer_bias=tp_world > 1),
                 ))
+                if self.moe is None:
+                    self.layers[-1].update(gate_up=W4A8Linear.from_tensors(to(L["gate_up"]), group_size),
+                                           down=W4A8Linear.from_tensors(to(L["down"]), group_size, defer_bias=tp_world > 1))
+                else:
+                    self.layers[-1].update(gate=L["gate"].to(self.dev).half().contiguous(),
+                                           gate_up=moemod.MoELinear.from_tensors(to(L["gate_up"]), group_size),
+                                           down=moemod.MoELinear.from_tensors(to(L["down"]), group_size))
+                    assert tuple(self.layers[-1]["gate"].shape) == (self.moe[0], hid) and self.layers[-1]["down"].experts == self.moe[0] \
+                        and self.layers[-1]["gate_up"].experts == self.moe[0] and self.layers[-1]["gate_up"].n == 2 * inter
                 assert self.layers[-1]["qkv"].n == self.qkv_n and self.layers[-1]["down"].k == inter
             self.norm_w = weights["norm"].to(self.dev)
             if with_lm_head:
@@ -258,6 +285,11 @@ class DecodeEngine:
             self.proj_res = self.proj_out
         self.gate_up_buf = torch.empty((B, 2 * inter), dtype=f16, device=self.dev)
         self.mlp_act = torch.empty((B, inter), dtype=f16, device=self.dev)
+        # mixture of experts: the step's normed fp16 rows (what the router reads) and the buffers of the B * k sorted rows, persistent
+        self.moe_normed = self.moe_bufs = None
+        if self.moe is not None:
+            self.moe_normed = torch.empty((B, hid), dtype=f16, device=self.dev)
+            self.moe_bufs = moemod.mlp_buffers(B, self.moe[0], self.moe[1], hid, inter, self.dev)
         self.final = torch.empty((B, hid), dtype=f16, device=self.dev)
         # K-slice planes (qserve_amd.fused.gemm_planes): the row-parallel projections named in `planes` (default: QS_PLANES or
         # "down") leave int32 partial sums per K slice and the add + norm + quant launch behind them finishes the GEMM - where
@@ -268,7 +300,7 @@ class DecodeEngine:
         if bad:
             raise ValueError(f"planes / QS_PLANES: {bad} - only the row-parallel projections 'o' and 'down' have a planes form")
         self.planes = {}
-        if fuse_pairs and tp_world == 1 and hid <= 4096 and hid % 2048 == 0:
+        if fuse_pairs and tp_world == 1 and hid <= 4096 and hid % 2048 == 0 and self.moe is None:   # (no planes form in MoE layers)
             for name in planes:
                 # one buffer serves every layer: the form is taken only if EVERY layer's projection has it with the same number
                 # of slices (a layer with a bias, or of another shape, would otherwise run the planes path and lose its bias)
@@ -409,13 +441,19 @@ class DecodeEngine:
     def _prompt_buffers(self, T):
         """Activation buffers of the is_prompt path for T rows."""
         f16, i8, dev = torch.float16, torch.int8, self.dev
-        return dict(
+        bufs = dict(
             qa=torch.empty((T, self.hid), dtype=i8, device=dev), qo=torch.empty((T, self.H * 128), dtype=i8, device=dev),
-            q_mlp=torch.empty((T, self.inter), dtype=i8, device=dev), q_scale=torch.empty((T,), dtype=f16, device=dev),
+            q_scale=torch.empty((T,), dtype=f16, device=dev),
             q_sum=torch.empty((T,), dtype=f16, device=dev), qkv=torch.empty((T, self.qkv_n), dtype=f16, device=dev),
-            proj=torch.empty((T, self.hid), dtype=f16, device=dev),
-            gate_up=torch.empty((T, 2 * self.inter), dtype=f16, device=dev),
-            mlp_act=torch.empty((T, self.inter), dtype=f16, device=dev))
+            proj=torch.empty((T, self.hid), dtype=f16, device=dev))
+        if self.moe is not None:                                     # the T * k sorted rows live in `moe` (moe.mlp_buffers)
+            bufs.update(normed=torch.empty((T, self.hid), dtype=f16, device=dev),
+                        moe=moemod.mlp_buffers(T, self.moe[0], self.moe[1], self.hid, self.inter, dev))
+        else:
+            bufs.update(q_mlp=torch.empty((T, self.inter), dtype=i8, device=dev),
+                        gate_up=torch.empty((T, 2 * self.inter), dtype=f16, device=dev),
+                        mlp_act=torch.empty((T, self.inter), dtype=f16, device=dev))
+        return bufs
 
     def _quant(self, out, x, q_sum, q_scale):
         """out / q_scale (/ q_sum: per-channel weights only) = the per-token int8 quantisation of the fp16 rows x."""
@@ -435,7 +473,7 @@ class DecodeEngine:
         eps = self.cfg["eps"]
         fuse_sum, fuse = self.group_size == -1, self.fuse_pairs
         qa, qo, q_mlp, q_scale, q_sum, qkv, proj, proj_res, gate_up, mlp_act = (
-            bufs[k] for k in ("qa", "qo", "q_mlp", "q_scale", "q_sum", "qkv", "proj", "proj_res", "gate_up", "mlp_act"))
+            bufs.get(k) for k in ("qa", "qo", "q_mlp", "q_scale", "q_sum", "qkv", "proj", "proj_res", "gate_up", "mlp_act"))
         sums = q_sum if fuse_sum else None
         # set_lora: lora_rows behind every base GEMM (and its bias), on that GEMM's quantised input.  A linear with an adapter takes the
         # path a linear with a bias takes: no planes form, no silu * mul epilogue - the delta has to be added in between
@@ -489,6 +527,20 @@ class DecodeEngine:
             L["qkv"](qa, q_scale, q_sum, qkv)
             lora_add(li, "qkv", qkv, qa)
             attention(li, qkv)
+            if self.moe is not None:
+                # the sparse MLP (mixtral_w4a8_unpad.py:279-374): the router reads the UN-quantised normed rows, the experts the quantised
+                # ones; `moemod.moe_mlp` is looked up per call (the seam tests wrap)
+                res = yield from row_parallel(li, "o", L["o"], qo)
+                residual_add_(h, res)
+                layernorm_ops.rms_norm(bufs["normed"], h, L["ln2"], eps)
+                logits = torch.matmul(bufs["normed"], L["gate"].t())
+                self._quant(qa, bufs["normed"], q_sum, q_scale)
+                moemod.moe_mlp(proj, qa, q_scale, sums, logits, self.moe[1], L["gate_up"], L["down"], bufs["moe"])
+                if li + 1 < nl:
+                    add_norm_quant(h, proj, self.layers[li + 1]["ln1"])   # next layer's input norm
+                else:
+                    residual_add_(h, proj)
+                continue
             if not proj_add_norm_quant(L["o"], "o", qo, h, L["ln2"]):
                 res = yield from row_parallel(li, "o", L["o"], qo)
                 add_norm_quant(h, res, L["ln2"])
@@ -517,8 +569,10 @@ class DecodeEngine:
         attend(li, qkv) -> fp16 [T, H * 128]: cache write + attention of layer li on its packed qkv rows (prefill: writer + flash
         over the call's own k / v; prefill_chunked: append attention over the pages + the chunk).  The row-parallel partials are
         summed through the process group, in place."""
-        b = {k: v[:h.size(0)] for k, v in bufs.items()}
+        b = {k: v[:h.size(0)] for k, v in bufs.items() if k != "moe"}
         b["proj_res"] = b["proj"]
+        if self.moe is not None:
+            b["moe"] = moemod.slice_buffers(bufs["moe"], h.size(0), self.moe[1])
 
         def attention(li, qkv):
             self._quant(b["qo"], attend(li, qkv), b["q_sum"], b["q_scale"])
@@ -1116,6 +1170,7 @@ class DecodeEngine:
         call makes a new table and switches LoRA off; a graph captured with the old one keeps reading the old one.  Single GPU, with
         the lm_head."""
         self._single_gpu("enable_lora")
+        assert self.moe is None, "enable_lora: LoRA over expert weights is not built - a mixture-of-experts engine runs the base model only"
         self.lora_table = loramod.LoraTable(self.cfg, slots, rank, self.dev)
         self.lora_ids = torch.full((self.B,), -1, dtype=torch.int32, device=self.dev)
         ws = max(loramod.workspace_bytes(self.B, K, self.lora_table.rank, len(ends)) for K, _, ends in self.lora_table.shapes.values())
@@ -1147,6 +1202,7 @@ class DecodeEngine:
             self._lora = False
             return
         self._single_gpu("set_lora")
+        assert self.moe is None, "set_lora: LoRA over expert weights is not built - a mixture-of-experts engine runs the base model only"
         assert self.lora_table is not None, "set_lora: enable_lora first"
         ids = torch.as_tensor(adapter_ids, device="cpu")
         assert ids.dim() == 1 and ids.numel() == self.B and not ids.is_floating_point() and ids.dtype != torch.bool, \
@@ -1333,6 +1389,8 @@ class DecodeEngine:
             torch.index_select(self.embed, 0, self.tokens, out=self.hidden)
         bufs = dict(qa=self.q_act, qo=self.q_attn, q_mlp=self.q_mlp, q_scale=self.q_scale, q_sum=self.q_sum, qkv=self.qkv_buf,
                     proj=self.proj_out, proj_res=self.proj_res, gate_up=self.gate_up_buf, mlp_act=self.mlp_act)
+        if self.moe is not None:
+            bufs.update(normed=self.moe_normed, moe=self.moe_bufs)
         yield from self._layer_stack(self.hidden, bufs, self._step_attention, self.planes)
         layernorm_ops.rms_norm(self.final, self.hidden, self.norm_w, self.cfg["eps"])
         logits = None                                                # (the features of the tail need the un-cut head: _single_gpu)

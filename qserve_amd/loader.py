@@ -152,3 +152,65 @@ def load_llama_w4a8(state, cfg, group_size=-1, tp_rank=0, tp_world=1, load_norm_
             t = state[key].half()
         out[name] = t.to(device) if device is not None else t
     return out
+
+
+def _stack(parts):
+    """[expert 0's tensors, expert 1's, ...] (dicts of one projection each) -> the tensors stacked over experts (moe.MoELinear's form)."""
+    return {k: torch.stack([p[k] for p in parts], dim=0).contiguous() for k in parts[0]}
+
+
+def load_mixtral_w4a8(state, cfg, group_size=-1, load_norm_weights=False, device=None):
+    """`load_llama_w4a8` for the reference's Mixtral checkpoints (qserve/modeling/models/mixtral_w4a8_unpad.py: its `load_weights` maps the
+    same names).  Attention, norms, embeddings and lm_head are read as there; the sparse MLP of layer i is
+    `model.layers.{i}.block_sparse_moe.gate.weight` fp16 [E, hidden] - the router, un-quantised - and per expert e
+    `model.layers.{i}.block_sparse_moe.experts.{e}.{w1,w3,w2}.{qweight,s1_scales,s1_szeros | s2_scales,s2_zeros}`: w1 (gate) and w3 (up)
+    [inter, hidden] are stacked as rows 0 .. inter-1 and inter .. 2 inter-1 of the expert's gate_up (dim 1 for the [K/128, N] tensors), w2
+    [hidden, inter] is its down; the experts are then stacked on a new leading axis, the packed bytes untouched.  cfg: dict with hidden,
+    heads, kv_heads, inter, layers, experts.  Single GPU (no sharding of experts).
+    Returns {"layers": [{"qkv", "o": {tensor dicts}, "gate": tensor, "gate_up", "down": {stacked tensor dicts}, "ln1", "ln2"}], "norm",
+    "embed", "lm_head"} - what DecodeEngine(weights=...) takes for a config with `experts`."""
+    if not isinstance(state, dict):
+        state = dict(state)
+    H, Hkv, hid, E = cfg["heads"], cfg["kv_heads"], cfg["hidden"], cfg["experts"]
+    hd = hid // H
+    assert hd == 128, "the W4A8KV4 kernels are built for head_dim 128"
+
+    def dev(d):
+        return {k: (v.to(device) if device is not None else v).contiguous() for k, v in d.items()}
+
+    def put(t):
+        return t.to(device) if device is not None else t
+
+    def ones():
+        return torch.ones((hid,), dtype=torch.float16)
+
+    layers = []
+    for li in range(cfg["layers"]):
+        p = f"model.layers.{li}."
+        q, k, v = (_linear(state, p + f"self_attn.{n}_proj") for n in ("q", "k", "v"))
+        qkv = fuse_column_parallel([q, k, v], [H * hd, Hkv * hd, Hkv * hd])
+        o = shard_row(_linear(state, p + "self_attn.o_proj"), 0, 1, group_size)
+        m = p + "block_sparse_moe."
+        if m + "gate.weight" not in state:
+            raise KeyError(f"checkpoint has no {m}gate.weight")
+        gate = state[m + "gate.weight"].half()
+        assert tuple(gate.shape) == (E, hid), f"{m}gate.weight is {tuple(gate.shape)}, the config says [{E}, {hid}]"
+        gate_up, down = [], []
+        for e in range(E):
+            w1, w3, w2 = (_linear(state, m + f"experts.{e}.{n}") for n in ("w1", "w3", "w2"))
+            gate_up.append(fuse_column_parallel([w1, w3], [cfg["inter"]] * 2))
+            down.append({k: t for k, t in w2.items() if k != "bias"})
+        ln1 = state[p + "input_layernorm.weight"].half() if load_norm_weights and p + "input_layernorm.weight" in state else ones()
+        ln2 = (state[p + "post_attention_layernorm.weight"].half()
+               if load_norm_weights and p + "post_attention_layernorm.weight" in state else ones())
+        layers.append(dict(qkv=dev(qkv), o=dev(o), gate=put(gate).contiguous(), gate_up=dev(_stack(gate_up)), down=dev(_stack(down)),
+                           ln1=put(ln1), ln2=put(ln2)))
+    out = dict(layers=layers)
+    norm = state["model.norm.weight"].half() if load_norm_weights and "model.norm.weight" in state else ones()
+    for name, key, t in (("norm", None, norm), ("embed", "model.embed_tokens.weight", None), ("lm_head", "lm_head.weight", None)):
+        if t is None:
+            if key not in state:
+                continue
+            t = state[key].half()
+        out[name] = put(t)
+    return out
