@@ -972,6 +972,54 @@ int qs_debug_rope_table_state(float base, int* slots_used, int* longest_len_for_
 int qs_rope_profile_register(const float* denom, int pairs /* must be 64 */, float mscale, int table_positions, float* key_out);
 int qs_debug_rope_profile_state(float key, int* profiles_used, int* longest_table_len);
 
+/* ----------------------------------------------------------------------------------------------------------
+ * Page pool (no reference counterpart: its block manager is host Python).  A pool has N pages per layer, one index space for the K and
+ * the V pool of every layer; each pool tensor holds N + 1 pages of page_bytes bytes, and page N is the SINK: never on the free list,
+ * named by every table entry that names no owned page, so that no entry is ever null or stale.  The two entries move pages between the
+ * free stack and the rows of the per-layer pointer tables on the device: capturable, nothing allocated, nothing read back, all integer.
+ *
+ * State, filled in place.  free_list int32 [N]: a stack, free_list[0 .. count) are the free indices, popped from the top; count int32
+ * [1]; page_ids int32 [batch, max_blocks]: the physical page of logical page j of row b, or -1; owned int32 [batch]: pages a row owns
+ * (its logical pages 0 .. owned - 1); starved int32 [batch]: set when a row was refused pages; error int32 [1]: set on a broken
+ * invariant.  layer_tables int64 [num_layers]: the addresses of the layers' pointer tables int64 [batch, 2, max_blocks] (what
+ * qs_kv_cache_commit_path_layers takes); layer_bases int64 [num_layers, 2]: the K / V pool base addresses.  The table entry of page id
+ * in layer l is layer_bases[l, kv] + id * page_bytes; the sink's is layer_bases[l, kv] + N * page_bytes.
+ *
+ * qs_pages_reserve.  lengths int32 [batch]; extra_rows int32 [batch] or null; finished int32 [batch] or null, in and out.  Per row b:
+ *     e_b    = max(extra_rows[b], 0) if extra_rows is given, otherwise extra;
+ *     need_b = min(ceil((max(lengths[b], 1) - 1 + e_b) / 64), max_blocks)    - the slots a round of e_b new tokens writes;
+ *     grow_b = 0 if finished is given and finished[b] != 0, otherwise max(need_b - owned[b], 0);
+ *     S_b    = grow_0 + .. + grow_b, the inclusive prefix in row order;
+ *     row b is SERVED iff S_b <= count.
+ * A served row's j-th new page, 0 <= j < grow_b, is id = free_list[count - 1 - (S_b - grow_b + j)]: page_ids[b, owned[b] + j] = id, and
+ * entry (b, kv, owned[b] + j) of the K and V tables of all layers becomes that page's address; then owned[b] += grow_b.  A row with
+ * grow_b > 0 that is not served gets nothing: starved[b] = 1, and finished[b] = 3 (no pages) where finished is given and finished[b]
+ * == 0.  count drops by the largest served S_b.  Rows are served all or nothing and the rule is deterministic; with grow <= 1 per row -
+ * every plain step - it is exactly first come in row order.  With larger grows a row may be refused although a lone page remains, and
+ * a later row whose smaller demand would still fit is refused with it (the prefix does not skip).
+ *
+ * qs_pages_release.  rows_mask int32 [batch]: rows with a non-zero entry are MASKED.  With E_b the exclusive prefix of owned over the
+ * masked rows, in row order: free_list[count + E_b + j] = page_ids[b, j] for 0 <= j < owned[b] - rows push their pages back in row
+ * order, then in logical page order -, page_ids[b, j] = -1, the table entries (b, kv, j) of all layers become the sink's address,
+ * owned[b] = 0, starved[b] = 0; count rises by the masked rows' total.  Other rows keep everything.
+ *
+ * Broken invariants: count outside 0 .. N, an owned[b] outside 0 .. max_blocks, a page id outside 0 .. N - 1 among those about to be
+ * popped (reserve) or pushed (release), or a release that would raise count above N: error[0] = 1 and the launch changes NOTHING else.
+ * No address is formed from an unchecked or unclamped index.  What a table already holds is not checked.
+ *
+ * QS_EINVAL before any device call: a null pointer (extra_rows and finished may be null); num_pages < 1; max_blocks or num_layers < 1;
+ * page_bytes < 1; num_pages * num_layers >= 2^30; batch outside 0 .. 1024; batch * max_blocks * 2 * num_layers >= 2^31; extra < 0; an
+ * int32 array not 4-byte, layer_tables or layer_bases not 8-byte aligned.  batch == 0: QS_OK, no launch.  One launch of ONE workgroup
+ * each: a wave64 shuffle scan, the waves' totals through LDS, rows beyond the workgroup's 256 threads by a strided loop; no atomics.
+ * ---------------------------------------------------------------------------------------------------------- */
+int qs_pages_reserve(int32_t* free_list, int32_t* count, int32_t* page_ids, int32_t* owned, int32_t* starved, int32_t* error,
+                     const int64_t* layer_tables, const int64_t* layer_bases, const int32_t* lengths, const int32_t* extra_rows,
+                     int32_t* finished, int batch, int max_blocks, int num_layers, int num_pages, int64_t page_bytes, int extra,
+                     qs_stream_t stream);
+int qs_pages_release(int32_t* free_list, int32_t* count, int32_t* page_ids, int32_t* owned, int32_t* starved, int32_t* error,
+                     const int64_t* layer_tables, const int64_t* layer_bases, const int32_t* rows_mask, int batch, int max_blocks,
+                     int num_layers, int num_pages, int64_t page_bytes, qs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,7 @@ from . import fused as fusedmod
 from . import logprobs as logprobsmod
 from . import lora as loramod
 from . import moe as moemod
+from . import paging as pagingmod
 from . import penalties as penaltiesmod
 from . import rope as ropemod
 from . import sampling as samplingmod
@@ -167,12 +168,24 @@ class W4A8Linear:
 class DecodeEngine:
     def __init__(self, cfg, batch, prompt_len, max_new, group_size=-1, int4_kv=True, device="cuda:0", seed=0,
                  tp_rank=0, tp_world=1, with_lm_head=True, fuse_pairs=True, weights=None, vocab_parallel=True, planes=None,
-                 direct_allreduce=None):
+                 direct_allreduce=None, page_pool=None):
         """weights: None = synthetic random-quantised tensors of the right shapes; otherwise this rank's tensors as
         qserve_amd.loader.load_llama_w4a8 returns them (checkpoint path).  A config with `experts` and `experts_per_token`
         (MIXTRAL_8X7B, TINY_MOE) builds mixture-of-experts layers: a router `gate` fp16 [E, hid] and two `moe.MoELinear`s in place of
         gate_up / down (weights: qserve_amd.loader.load_mixtral_w4a8); every path then runs `moe.moe_mlp` in the MLP branch of the layer
-        body.  Single GPU."""
+        body.  Single GPU.
+
+        `page_pool`: None - every sequence owns ceil(max_len / 64) + 1 private pages for its whole life, and nothing below applies -, or
+        N: the K and V pools of every layer hold N pages (and the sink, page N) that the rows share through `pager`, a
+        `paging.PagePool`: every table entry starts at the sink, every entry that writes the cache begins with ONE reserve launch -
+        step() (hence capture() / run()) for 1 token, verify_tree on both walks and speculate() (hence their captures) for the tree's n
+        nodes -, and the prefill entries release every row and reserve the prompt's pages before their first layer.  While set_stopping
+        is on the reserve is given `finished`: a row that is refused pages ends with stopping.NO_PAGES and is frozen from that very
+        round (stop_update gives k = 0 for finished != 0); generate() reports it.  While it is off, check() raises when a row starved.
+        What a frozen row guarantees under a pool is the bytes of its slots < lengths - 1: its rewrite of slot lengths - 1, and a frozen
+        verification's parked nodes, may land in the sink - valid memory that only ever takes validly quantised K / V, so it stays
+        finite.  Single GPU; prefill_shared refuses to run (aliased prefix pages would be released twice - the pool keeps no reference
+        counts)."""
         self.cfg, self.B, self.dev = cfg, batch, torch.device(device)
         # mixture of experts: (experts, experts per token), or None for a dense model - which launches exactly what it always did
         self.moe = (int(cfg["experts"]), int(cfg["experts_per_token"])) if cfg.get("experts") else None
@@ -253,17 +266,27 @@ class DecodeEngine:
         dhb = 64 if int4_kv else 128
         self.size_per_token = self.Hkv * dhb
         self.page_bytes = self.Hkv * 64 * dhb + 64 * self.Hkv * 4
-        nblocks = batch * self.mb
-        perm = torch.randperm(nblocks, generator=torch.Generator().manual_seed(seed)).reshape(batch, self.mb)
+        assert page_pool is None or (tp_world == 1 and int(page_pool) >= 1), \
+            f"DecodeEngine: page_pool={page_pool} - a page pool has at least one page and runs on one GPU (its allocator is one launch " \
+            "on one device; tensor parallelism under a pool is not built)"
+        nblocks = batch * self.mb if page_pool is None else int(page_pool) + 1       # (+ 1: the sink)
+        perm = torch.randperm(batch * self.mb, generator=torch.Generator().manual_seed(seed)).reshape(batch, self.mb)
         self.pools, self.tables = [], []
         for _ in range(cfg["layers"]):
             kp = torch.zeros((nblocks, self.page_bytes), dtype=torch.uint8, device=self.dev)
             vp = torch.zeros((nblocks, self.page_bytes), dtype=torch.uint8, device=self.dev)
-            t = torch.empty((batch, 2, self.mb), dtype=torch.int64)
-            t[:, 0] = kp.data_ptr() + perm * self.page_bytes
-            t[:, 1] = vp.data_ptr() + perm * self.page_bytes
+            t = torch.zeros((batch, 2, self.mb), dtype=torch.int64)
+            if page_pool is None:
+                t[:, 0] = kp.data_ptr() + perm * self.page_bytes
+                t[:, 1] = vp.data_ptr() + perm * self.page_bytes
             self.pools.append((kp, vp))
             self.tables.append(t.to(self.dev))
+        # page_pool: the allocator over these tables and pools (every entry the sink until a reserve), and the all-ones rows that are
+        # the lengths of a prompt's reserve and the mask of a release of every row
+        self.pager = self._all_rows = None
+        if page_pool is not None:
+            self.pager = pagingmod.PagePool(self.tables, self.pools, self.page_bytes)
+            self._all_rows = torch.ones((batch,), dtype=torch.int32, device=self.dev)
         # ---- activation buffers (ActivationBuffer, input_metadata.py:71-109)
         B = batch
         f16, i8 = torch.float16, torch.int8
@@ -332,7 +355,8 @@ class DecodeEngine:
         # the page tables" bound only - no result depends on it.  sync_length_bound() makes it exact again, at the price of one read-back.
         self._len_bound = prompt_len
         self._tree_cache = {}            # parent tuple -> the per-tree device constants of the device-walk verify_tree
-        self._layer_tables = None        # append.layer_table_pointers(self.tables), built on first use
+        # append.layer_table_pointers(self.tables), built on first use (a page pool has built it)
+        self._layer_tables = None if self.pager is None else self.pager.layer_tables
         self.last_verify_logits = None   # verify_tree: the logits [B, n, V] of its last call
         self.sampling = None             # set_sampling: {"seed"} while the head samples; the parameters live in device tensors:
         self._samp_t = self._samp_k = self._samp_p = self._samp_ids = None      # temperature, top-k, top-p per row; arange(B)
@@ -341,6 +365,7 @@ class DecodeEngine:
         # enable_drafting: the text of every sequence int32 [B, max_len], where its generated part begins int32 [B], the constants of
         # step()'s history_append, and (max_ngram, min_match, pad_token)
         self.history = self.prompt_lens = self._step_record = self._draft_params = self._prompt_len = None
+        self._text_starts = None         # admit: `prompt_lens` as a host list, from the first admit on (None: all rows start at _prompt_len)
         # set_stopping: True while the stop rule runs behind the heads; its persistent device tensors (created by the first call):
         # why each sequence ended int32 [B] (stopping.LIVE / STOPPED / LENGTH), the largest text length int32 [B], the stop table, and
         # the per-step k of step()
@@ -359,11 +384,30 @@ class DecodeEngine:
         # place; set_lora: True while lora_rows runs behind the four linears of every layer; the step's workspace
         self.lora_table = self.lora_ids = self._lora_step_ws = None
         self._lora = False
+        self._lora_pass = None           # admit: the adapter of every TOKEN of the ragged pass that is running int32 [T] (else None)
 
     def _single_gpu(self, what):
         """What every entry behind the un-cut fp16 lm_head asks for (sampling, penalties, shared prefixes, tree verification, drafting):
         under tensor parallelism the vocabulary-parallel greedy head stays the only one."""
         assert self.with_lm_head and not self.vocab_parallel and self.tp_world == 1, f"{what}: single GPU, with the lm_head"
+
+    # ---- the page pool (qserve_amd.paging, csrc/page_pool.hip) ---------------------------------------------------------------------
+    def _reserve(self, extra):
+        """The head of every entry that writes the cache, under a page pool: one `paging.PagePool.reserve` launch for the `extra` slots
+        the round writes behind lengths - 1, with `finished` while the stop rule is on (a refused row freezes).  No pool: nothing."""
+        if self.pager is not None:
+            self.pager.reserve(self.lengths, extra, finished=self.finished if self.stopping is not None else None)
+
+    def _prompt_pages(self, prompt_len):
+        """The head of a prefill entry under a page pool: every row gives its pages back and takes those of slots 0 .. prompt_len - 1
+        (two launches).  The reserve is given no `finished`, so the stop rule must be off: _prefill_entry sees to it for the prefill
+        entries, prefill_cache comes here directly."""
+        if self.pager is not None:
+            assert self.stopping is None, \
+                "a prompt's pages are reserved without the stop rule (a refused row could not be told through `finished`, and its " \
+                "prompt would go to the sink) - set_stopping(None) first"
+            self.pager.release(self._all_rows)
+            self.pager.reserve(self._all_rows, prompt_len)
 
     # ---- the sampling head (qserve_amd.sampling, csrc/sample_rows.hip) --------------------------------------------------------
     def set_sampling(self, temperature, top_k=0, top_p=1.0, seed=0):
@@ -423,6 +467,7 @@ class DecodeEngine:
     # ---- fill the cache for positions [0, prompt_len) through the prefill writer (random K/V source) ----------
     def prefill_cache(self, prompt_len, chunk=8):
         B = self.B
+        self._prompt_pages(prompt_len)
         gen = torch.Generator(device=self.dev).manual_seed(99)
         seq = torch.full((B,), prompt_len, dtype=torch.int32, device=self.dev)
         cu = (torch.arange(0, B + 1, device=self.dev, dtype=torch.int32) * prompt_len)
@@ -482,8 +527,8 @@ class DecodeEngine:
         def lora_add(li, name, out, xq):
             if lora is not None:
                 A, B = self.lora_table.layers[li][name]
-                loramod.lora_rows(out, xq, q_scale, A, B, self.lora_table.scaling, self.lora_ids, lora[0], self.lora_table.shapes[name][2],
-                                  workspace=lora[1])
+                loramod.lora_rows(out, xq, q_scale, A, B, self.lora_table.scaling, lora[0], lora[1], self.lora_table.shapes[name][2],
+                                  workspace=lora[2])
 
         def norm_quant(x, w):
             if fuse_sum:
@@ -609,7 +654,7 @@ class DecodeEngine:
             self._emit(logits, self.tokens)                          # (stopping is off here, by _prefill_entry)
         self.lengths.fill_(prompt_len + 1)
         self._len_bound = prompt_len + 1
-        self._text_start = prompt_len
+        self._text_start, self._text_starts = prompt_len, None
 
     def prefill(self, prompt_len, tokens=None):
         """Run the prompt through the model: per layer  norm+quant -> qkv GEMM -> apply_bias_rope_update_kv_cache
@@ -624,6 +669,7 @@ class DecodeEngine:
         if tokens is None:
             tokens = torch.randint(0, cfg["vocab"], (T,), device=dev,
                                    generator=torch.Generator(device=dev).manual_seed(7))
+        self._prompt_pages(prompt_len)
         h = torch.index_select(self.embed, 0, tokens)
         bufs = self._prompt_buffers(T)
         seq = torch.full((B,), prompt_len, dtype=torch.int32, device=dev)
@@ -658,6 +704,7 @@ class DecodeEngine:
             tokens = torch.randint(0, cfg["vocab"], (B * prompt_len,), device=dev,
                                    generator=torch.Generator(device=dev).manual_seed(7))
         chunk = min(chunk, prompt_len)
+        self._prompt_pages(prompt_len)
 
         def attend(li, qkv, cu, past, n, c0):
             return appendmod.append(qkv, cu, past, self.tables[li], self.H, self.Hkv, self.size_per_token, self.rope_base, self.int4,
@@ -693,6 +740,9 @@ class DecodeEngine:
         self._prefill_entry("prefill_shared")
         cfg, B, dev = self.cfg, self.B, self.dev
         self._single_gpu("prefill_shared")
+        assert self.pager is None, \
+            "prefill_shared: the engine runs over a page pool - the aliased prefix pages would be released once per row that names them, " \
+            "and the pool keeps no reference counts; prefill_chunked, or an engine without page_pool"
         assert not self._lora, \
             "prefill_shared: LoRA is on (set_lora) - a shared prefix under different adapters has different K / V, so its pages cannot " \
             "be computed once for the batch; set_lora(None), or prefill_chunked"
@@ -766,6 +816,7 @@ class DecodeEngine:
         self._host_walk_entry()
         max_past = int(self.lengths.max()) - 1
         self._fits("verify_tree", n, max_past)
+        self._reserve(n)
         _, toks, past, h, final, logits, am = self._verify_forward(draft_tokens, par, max_past, sampled)
         am = am.view(B, n)
         # the greedy walk, on the host (n <= 64 nodes per sequence)
@@ -870,12 +921,14 @@ class DecodeEngine:
         logits = self._head(final, am, (lambda: self._node_keys(c["depth"])) if sampled else None, draft=(toks, c["tree"]))
         return c, toks, past, h, final, logits, am
 
-    def _verify_tree_device(self, draft_tokens, par, max_past=None, out=None, sampled=False):
+    def _verify_tree_device(self, draft_tokens, par, max_past=None, out=None, sampled=False, reserved=False):
         """verify_tree(device_walk=True) behind its argument checks.  `max_past`: the planner hint (None: the host-side bound);
-        `out`: accept_greedy's four output tensors (None: fresh ones)."""
+        `out`: accept_greedy's four output tensors (None: fresh ones); `reserved`: the caller's round began with the pool's reserve."""
         from . import append as appendmod
         B, n = self.B, len(par)
         self._fits("verify_tree", n)
+        if not reserved:
+            self._reserve(n)
         hint = self._len_bound - 1 if max_past is None else int(max_past)
         c, toks, past, h, final, logits, am = self._verify_forward(draft_tokens, par, hint, sampled)
         accept_idx, accept_lens, last, nxt = appendmod.accept_greedy(toks.view(-1), am, c["parents"], c["cu"], max_accept=n, out=out)
@@ -939,17 +992,28 @@ class DecodeEngine:
         holds - the verification embeds every node, so it must be a token of the vocabulary (0 <= pad_token < vocab; checked).  A
         second call (after another prefill) refills the SAME buffers in place: graphs captured since the first call stay valid.
         `prompt_lens` int32 [B] holds P, where the generated text begins (what set_penalties counts as generated); refilled as well.
-        Single GPU, with the lm_head."""
+        `prompt_tokens=None`: the history of an EMPTY batch, after no prefill at all - lengths = 1, prompt_lens = 0, under a page pool
+        every row's pages released; a set_stopping(stop, 0) behind it freezes every row by the at-the-limit rule.  That is the state
+        admit() fills row by row and serve() starts from.  Single GPU, with the lm_head."""
         self._single_gpu("enable_drafting")
         assert 1 <= int(min_match) <= int(max_ngram) <= draftingmod.MAX_NGRAM, \
             f"enable_drafting: 1 <= min_match <= max_ngram <= {draftingmod.MAX_NGRAM}"
         assert 0 <= int(pad_token) < self.cfg["vocab"], \
             f"enable_drafting: pad_token={int(pad_token)} must be a token of the vocabulary (0 .. {self.cfg['vocab'] - 1}): pad nodes are embedded"
         B, dev = self.B, self.dev
-        prompt = prompt_tokens.to(dev).reshape(B, -1)
-        P = prompt.size(1)
-        assert P + 1 <= self.max_len and bool((self.lengths == P + 1).all()), \
-            "enable_drafting: call it right after a prefill of these prompt tokens (every sequence holds P + 1 tokens)"
+        if prompt_tokens is None:
+            # the empty batch: every row a text of one token (whatever `tokens` holds) that nobody asked for, lengths = 1, prompt_lens = 0,
+            # no page owned - a set_stopping(stop, 0) behind it freezes every row at its limit: what admit() fills and serve() starts from
+            prompt, P = None, 0
+            if self.pager is not None:
+                self.pager.release(self._all_rows)
+            self.lengths.fill_(1)
+            self._len_bound, self._text_start = 1, 0
+        else:
+            prompt = prompt_tokens.to(dev).reshape(B, -1)
+            P = prompt.size(1)
+            assert P + 1 <= self.max_len and bool((self.lengths == P + 1).all()), \
+                "enable_drafting: call it right after a prefill of these prompt tokens (every sequence holds P + 1 tokens)"
         if self.history is None:
             self.history = torch.zeros((B, self.max_len), dtype=torch.int32, device=dev)
             # what history_append needs to record ONE token per sequence (a path of the root alone): constants of step()'s record,
@@ -960,7 +1024,9 @@ class DecodeEngine:
         self.history.zero_()
         self.prompt_lens.fill_(P)
         self._prompt_len = P                                                  # (the same value on the host, for set_stopping's limits)
-        self.history[:, :P] = prompt
+        self._text_starts = None                                              # (admit: `prompt_lens` on the host, once rows differ)
+        if prompt is not None:
+            self.history[:, :P] = prompt
         self.history[:, P] = self.tokens
         self._draft_params = (int(max_ngram), int(min_match), int(pad_token))
 
@@ -1031,9 +1097,9 @@ class DecodeEngine:
         else:
             new = [int(max_new_tokens)] * B if isinstance(max_new_tokens, int) else [int(v) for v in max_new_tokens]
             assert len(new) == B and min(new) >= 0, f"set_stopping: max_new_tokens is one non-negative int, or one per sequence ({B})"
-            limits = [self._prompt_len + v for v in new]
+            limits = [p + v for p, v in zip(self._row_starts(), new)]
             assert max(limits) <= cap, \
-                f"set_stopping: prompt {self._prompt_len} + max_new_tokens {max(new)} is beyond the history's capacity {cap}"
+                f"set_stopping: text start + max_new_tokens {limits} is beyond the history's capacity {cap}"
         if self.finished is None:
             self.finished = torch.zeros((B,), dtype=torch.int32, device=dev)
             self.limit_lens = torch.zeros((B,), dtype=torch.int32, device=dev)
@@ -1098,9 +1164,9 @@ class DecodeEngine:
         assert self._text_start is not None, "logprobs: after a prefill entry (it says where the generated text begins)"
         lens = self.lengths.cpu().tolist()
         lp, rank, ids, tlp = (t.cpu() for t in (self.logprob_log, self.rank_log, self.top_ids_log, self.top_lp_log))
-        P, res = self._text_start, []
+        starts, res = self._text_starts or [self._text_start] * self.B, []   # (per row once admit has been used)
         for b in range(self.B):
-            end = min(lens[b], self.max_len)
+            P, end = starts[b], min(lens[b], self.max_len)
             res.append(dict(logprobs=lp[b, P:end].tolist(), ranks=rank[b, P:end].tolist(), top_ids=ids[b, P:end].tolist(),
                             top_logprobs=tlp[b, P:end].tolist()))
         return res
@@ -1211,14 +1277,20 @@ class DecodeEngine:
         self._lora = True
 
     def _lora_plan(self, rows):
-        """(rows_per_seq, workspace) of the lora_rows calls of a layer stack over `rows` rows: the step's persistent workspace, or a
-        fresh one sized for the largest of the four linears (inside a capture it lives in the graph's pool)."""
-        assert rows % self.B == 0
-        if rows == self.B:
-            return 1, self._lora_step_ws
+        """(adapter ids, rows_per_seq, workspace) of the lora_rows calls of a layer stack over `rows` rows: `lora_ids` with the step's
+        persistent workspace, or with a fresh one sized for the largest of the four linears (inside a capture it lives in the graph's
+        pool); a ragged pass of admit() has left its own ids in `_lora_pass`, one per token (rows_per_seq = 1)."""
         t = self.lora_table
+        if self._lora_pass is not None:
+            assert self._lora_pass.numel() == rows
+            per_seq, ids = 1, self._lora_pass
+        else:
+            assert rows % self.B == 0
+            if rows == self.B:
+                return self.lora_ids, 1, self._lora_step_ws
+            per_seq, ids = rows // self.B, self.lora_ids
         ws = max(loramod.workspace_bytes(rows, K, t.rank, len(ends)) for K, _, ends in t.shapes.values())
-        return rows // self.B, torch.empty((max(ws, 16),), dtype=torch.uint8, device=self.dev)
+        return ids, per_seq, torch.empty((max(ws, 16),), dtype=torch.uint8, device=self.dev)
 
     # ---- what the features share: the tail of a round, and what a capture freezes and keeps --------------------------------------
     def _emit(self, logits, next_token, node_tokens=None, accept_idx=None, accept_lens=None, last_row=None):
@@ -1289,24 +1361,12 @@ class DecodeEngine:
         included; reasons: `finished` as a list; rounds; read_backs) - the texts are read once, after the loop."""
         assert self.stopping is not None, "generate: set_stopping first (nothing else ends the loop)"
         assert max_rounds >= 0 and poll_every >= 1
-        if parents is None:
-            if self.graph is None or self._stale(self._step_capture):
-                self.capture(piecewise=False)
-            advance, run = 1, self.run
-        else:
-            par = self._tree_arg(parents, "generate")
-            if self.speculate_graph is None or self._stale(self._speculate_capture, tree=tuple(par), sampled=bool(sampled)):
-                self.capture_speculate(par, sampled=sampled)
-            advance, run = len(par), self.run_speculate
+        advance, run = self._round_graph("generate", parents, sampled)
         rounds = reads = 0
         while rounds < max_rounds:
-            # a round writes slots up to _len_bound - 1 + advance - 1: how many rounds fit the page tables by the bound
-            fit = (self.mb * 64 - (self._len_bound - 1)) // advance
-            burst = min(poll_every, max_rounds - rounds, fit)
+            burst = self._burst(run, advance, min(poll_every, max_rounds - rounds))
             if burst < 1:
                 break
-            for _ in range(burst):
-                run()
             rounds += burst
             state = torch.stack((self.finished, self.lengths)).cpu()         # the one read-back of the burst
             reads += 1
@@ -1314,8 +1374,301 @@ class DecodeEngine:
             if bool((state[0] != 0).all()):
                 break
         hist, lens, fin = self.history.cpu(), self.lengths.cpu().tolist(), self.finished.cpu().tolist()
-        texts = [hist[b, self._prompt_len:lens[b]].tolist() for b in range(self.B)]
+        starts = self._row_starts()
+        texts = [hist[b, starts[b]:lens[b]].tolist() for b in range(self.B)]
         return texts, fin, rounds, reads
+
+    def _round_graph(self, what, parents, sampled):
+        """The graph generate() replays: the captured step - or, with `parents`, the captured speculate round of that tree -,
+        captured first where it does not exist yet or was captured in another state -> (what a replay adds to the lengths at most, the
+        call that replays it)."""
+        if parents is None:
+            if self.graph is None or self._stale(self._step_capture):
+                self.capture(piecewise=False)
+            return 1, self.run
+        par = self._tree_arg(parents, what)
+        if self.speculate_graph is None or self._stale(self._speculate_capture, tree=tuple(par), sampled=bool(sampled)):
+            self.capture_speculate(par, sampled=sampled)
+        return len(par), self.run_speculate
+
+    def _burst(self, run, advance, count):
+        """Replay `run` up to `count` times, shortened to what fits the page tables by the host-side bound of the lengths -> the number
+        of replays.  A round writes slots up to _len_bound - 1 + advance - 1."""
+        burst = min(count, (self.mb * 64 - (self._len_bound - 1)) // advance)
+        for _ in range(burst):
+            run()
+        return max(burst, 0)
+
+    # ---- continuous batching: admission into rows of the fixed batch, and the loop over a stream of requests ----------------------
+    def _row_starts(self):
+        """Where every row's generated text begins, on the host: `prompt_lens`, per row once admit() has been used."""
+        return self._text_starts or [self._prompt_len] * self.B
+
+    def admit(self, rows, prompts, max_new_tokens=None, start_states=None, text_start=None, chunk=None):
+        """Put new texts into the rows `rows` (distinct indices) of the fixed batch, eagerly, leaving every other row's `tokens`,
+        `lengths`, `hidden`, `history`, logs, states and pages untouched byte for byte.  `prompts`: one 1-D token sequence per row,
+        ragged, 1 <= P_r and P_r + 1 <= max_len.  After enable_drafting (enable_drafting(None) for an empty batch).  A static engine's
+        rows keep their private pages; under a page pool the rows are released first and take the pages of their prompts' slots
+        0 .. P_r - 1 in one reserve (lengths 1, extra_rows P_r, 0 elsewhere).  The caller sees to it that the free pages suffice
+        (`pager.free_pages()`, or serve()'s bookkeeping): a refused row's prompt goes to the sink, and it ends with NO_PAGES while the stop
+        rule is on (check() raises while it is off).
+
+        The prompts run in passes of `chunk` tokens per sequence (None: whole) through the layer stack of the prompt path, `append.append`
+        over the named rows' table rows with a ragged cu_seqlens_q and per-row past_lens - a sequence with no token left is left out of
+        the pass.  For equal-length prompts in every row these are the calls of prefill_chunked.  Each sequence's last hidden row goes to
+        hidden[row]; the full-batch head draws the first token as a prefill head does - the constraint's mask under the row's
+        `start_states` entry (an int or one per row; default 0), sampler keys (row, P_r), no penalties - and its results are merged into
+        the admitted rows alone; the log entry lands at column P_r of that row's cleared logs, `fsm_state` advances once.  Then per
+        row: `tokens`, lengths = P_r + 1, history = the prompt and the first token behind zeros, prompt_lens = `text_start` (an int or
+        one per row, 0 .. P_r; None: P_r - the text a resumed request generated earlier counts as generated), limit_lens = prompt_lens +
+        `max_new_tokens` (an int or one per row; None: the history's capacity; needs set_stopping to have been called), finished = 0
+        followed by the root check of set_stopping while the stop rule is on.  Unlike the prefill entries it runs while stopping and
+        penalties are on, and under set_lora: a pass hands `lora.lora_rows` one adapter id per TOKEN, lora_ids[row] repeated over the
+        row's tokens of the pass (rows_per_seq = 1).  No capture is invalidated.  `start_states` needs set_constraint to be on.  Every
+        argument is checked before the first write.  Single GPU, with the lm_head."""
+        from . import append as appendmod
+        self._single_gpu("admit")
+        assert self.history is not None, "admit: enable_drafting first (enable_drafting(None) for an empty batch): it writes `history`"
+        B, dev, cap = self.B, self.dev, self.max_len
+        rows = [int(r) for r in rows]
+        R = len(rows)
+        assert R >= 1 and len(set(rows)) == R and all(0 <= r < B for r in rows), f"admit: rows {rows} - distinct row indices in 0 .. {B - 1}"
+        pl = [torch.as_tensor(p).to("cpu", torch.int64) for p in prompts]
+        assert len(pl) == R and all(p.dim() == 1 for p in pl), f"admit: one 1-D token sequence per row ({R})"
+        Ps = [p.numel() for p in pl]
+        assert min(Ps) >= 1 and max(Ps) + 1 <= cap, f"admit: prompt lengths {Ps} - 1 <= P and P + 1 <= max_len = {cap}"
+        assert all(0 <= int(p.min()) and int(p.max()) < self.cfg["vocab"] for p in pl), "admit: a prompt token is outside the vocabulary"
+        per_row = lambda v: [int(v)] * R if isinstance(v, int) else [int(x) for x in v]      # noqa: E731
+        starts = Ps if text_start is None else per_row(text_start)
+        assert len(starts) == R and all(0 <= s <= p for s, p in zip(starts, Ps)), f"admit: text_start {starts} - one per row, 0 .. P_r"
+        limits = None
+        if max_new_tokens is not None or self.limit_lens is not None:
+            assert self.limit_lens is not None, "admit: max_new_tokens needs the stop rule's limits - set_stopping first"
+            new = [cap] * R if max_new_tokens is None else per_row(max_new_tokens)
+            assert len(new) == R and min(new) >= 0, f"admit: max_new_tokens is one non-negative int, or one per row ({R})"
+            limits = [cap if max_new_tokens is None else s + v for s, v in zip(starts, new)]
+            assert max(limits) <= cap, f"admit: text_start + max_new_tokens {limits} is beyond the history's capacity {cap}"
+        assert start_states is None or self._fsm is not None, "admit: start_states are the states of a constraint - set_constraint first"
+        st = None
+        if self._fsm is not None:
+            st = [0] * R if start_states is None else per_row(start_states)
+            assert len(st) == R, f"admit: start_states is one int, or one per row ({R})"
+        maxP = max(Ps)
+        assert chunk is None or int(chunk) >= 1, f"admit: chunk={chunk} (None, or at least one token per sequence and pass)"
+        chunk = maxP if chunk is None else min(int(chunk), maxP)
+        i32 = dict(dtype=torch.int32, device=dev)
+        rows_t = torch.tensor(rows, dtype=torch.int64, device=dev)
+        P_t = torch.tensor(Ps, **i32)
+        # ---- the rows' state that the pass does not compute: text, where it begins, its limit; live again
+        text = torch.zeros((R, cap), dtype=torch.int32)
+        for i, p in enumerate(pl):
+            text[i, :Ps[i]] = p.to(torch.int32)
+        self.history[rows_t] = text.to(dev)
+        self.prompt_lens[rows_t] = torch.tensor(starts, **i32)
+        if self._text_starts is None:
+            self._text_starts = [self._prompt_len] * B
+        for r, s in zip(rows, starts):
+            self._text_starts[r] = s
+        if limits is not None:
+            self.limit_lens[rows_t] = torch.tensor(limits, **i32)
+        if self.finished is not None:
+            self.finished[rows_t] = 0
+        if st is not None:
+            self.fsm_state[rows_t] = torch.tensor(st, **i32)
+        # ---- pages: the rows give back what they own and take their prompts' (two launches)
+        if self.pager is not None:
+            extra = torch.zeros((B,), **i32)
+            extra[rows_t] = P_t
+            self.pager.release(self.pager.rows_mask(rows))
+            self.pager.reserve(self._all_rows, 0, extra_rows=extra, finished=self.finished if self.stopping is not None else None)
+        # ---- the prompts, in passes of `chunk` tokens per sequence, over the rows' table rows (read AFTER the reserve filled them)
+        tabs = [t[rows_t] for t in self.tables]
+        bufs = self._prompt_buffers(R * chunk)
+        last = torch.empty((R, self.hid), dtype=torch.float16, device=dev)
+        row_lora = torch.index_select(self.lora_ids, 0, rows_t) if self._lora else None
+        for c0 in range(0, maxP, chunk):
+            live = [i for i in range(R) if Ps[i] > c0]
+            ns = [min(chunk, Ps[i] - c0) for i in live]
+            cu_h = [0]
+            for n in ns:
+                cu_h.append(cu_h[-1] + n)
+            T = cu_h[-1]
+            h = torch.index_select(self.embed, 0, torch.cat([pl[i][c0:c0 + n] for i, n in zip(live, ns)]).to(dev))
+            cu, past = torch.tensor(cu_h, **i32), torch.full((len(live),), c0, **i32)
+            if len(live) == R:
+                tl = tabs
+            else:
+                live_t = torch.tensor(live, dtype=torch.int64, device=dev)
+                tl = [t[live_t] for t in tabs]
+            if row_lora is not None:                                        # set_lora: the adapter of every token of this pass
+                self._lora_pass = torch.repeat_interleave(torch.index_select(row_lora, 0, torch.tensor(live, dtype=torch.int64, device=dev)),
+                                                          torch.tensor(ns, dtype=torch.int64, device=dev))
+            try:
+                self._prompt_layers(h, bufs, lambda li, qkv: appendmod.append(
+                    qkv, cu, past, tl[li], self.H, self.Hkv, self.size_per_token, self.rope_base, self.int4, max_seqlen_q=max(ns),
+                    max_past=c0).reshape(T, -1))
+            finally:
+                self._lora_pass = None
+            ended = [(i, cu_h[j + 1] - 1) for j, (i, n) in enumerate(zip(live, ns)) if c0 + n == Ps[i]]
+            if ended:
+                last[torch.tensor([i for i, _ in ended], dtype=torch.int64, device=dev)] = \
+                    torch.index_select(h, 0, torch.tensor([e for _, e in ended], dtype=torch.int64, device=dev))
+        # ---- the full-batch head on copies, merged into the admitted rows: k = 1 there, 0 elsewhere
+        hidden = self.hidden.clone()
+        hidden[rows_t] = last
+        final = torch.empty_like(hidden)
+        layernorm_ops.rms_norm(final, hidden, self.norm_w, self.cfg["eps"])
+        logits = torch.matmul(final, self.lm_head.t())
+        if self._fsm is not None:
+            self._constrain(logits)
+        pos = self.lengths.clone()
+        pos[rows_t] = P_t                                                   # the first new token will hold position P_r
+        out = self.tokens.clone()
+        if self.sampling is not None:
+            self._sample(logits, out, samplingmod.position_keys(self._samp_ids, pos))
+        else:
+            argmax_rows_(logits, out)
+        k = torch.zeros((B,), **i32)
+        k[rows_t] = 1
+        if self._logprobs is not None:
+            top, tempered = self._logprobs
+            self.logprob_log[rows_t] = float("nan")
+            self.rank_log[rows_t] = 0
+            self.top_ids_log[rows_t] = -1
+            self.top_lp_log[rows_t] = float("nan")
+            logprobsmod.logprob_path(logits, None, None, k, out, pos, temperature=self._samp_t[:B] if tempered else 1.0, top=top,
+                                     out=(self.logprob_log, self.rank_log, self.top_ids_log, self.top_lp_log))
+        if self._fsm is not None:
+            constraintsmod.advance(self.fsm_state, out, *self._fsm, accept_lens=k)
+        first = torch.index_select(out, 0, rows_t)
+        self.hidden[rows_t] = last
+        self.final[rows_t] = torch.index_select(final, 0, rows_t)
+        self.tokens[rows_t] = first
+        self.lengths[rows_t] = P_t + 1
+        self.history[rows_t, P_t.to(torch.int64)] = first.to(torch.int32)
+        self._len_bound = max(self._len_bound, maxP + 1)
+        if self.stopping is not None:                                       # the root check of set_stopping: a first token that is a
+            self._stop_k.zero_()                                            # stop, or a row at its limit; every other row's current
+            self._stop_update(self.tokens, accept_lens=self._stop_k, check_root=True)   # token was looked at when it was emitted
+
+    def serve(self, requests, stop=(), parents=None, sampled=False, poll_every=8, chunk=None):
+        """Serve a stream of requests through the fixed batch: `requests` is a list of (prompt_tokens, max_new_tokens), first come first
+        served.  Starts from the empty batch (enable_drafting(None), set_stopping(stop, 0): every row frozen), then loops:
+          1. the rows that finished hand their texts over (a device copy of their history rows; the texts are read once, at the end),
+          2. their pages are released,
+          3. waiting requests are admitted into free rows, in order, while the pool's free count covers ceil((P + 1) / 64) pages each,
+          4. the captured step graph - with `parents`, the captured speculate graph - is replayed `poll_every` times (generate()'s
+             burst),
+          5. (`finished`, `lengths`, the pool's `count` and `owned`) are read back in one copy.
+        A row that ended with NO_PAGES is PREEMPTED: its request returns to the front of the queue with prompt := its text so far and
+        text_start := the original prompt length, so its length limit and penalty window are unchanged; the prompt is recomputed.  Reading
+        that text is one more read-back for the bursts that preempt.  A resumed text need not be bit-identical to an un-preempted one:
+        prompt and decode attention round differently, sampler keys follow the row, and log entries from before a preemption are lost.
+        Raises before anything runs for a request that can never fit max_len (P + max_new > max_len) or the pool
+        (ceil((P + max_new - 1 + n) / 64) > N, n the round's tokens: 1, or the tree's nodes).
+        -> (per request, in order, dict(tokens: the generated text, reason: 1 a stop / 2 the length, preempted_at: the generated
+        tokens it held at each preemption), stats dict(rounds, read_backs, admitted, preempted, peak_pages: the most pages in use at a
+        read-back - the static batch * mb without a pool))."""
+        from collections import deque
+        self._single_gpu("serve")
+        assert poll_every >= 1
+        B, dev, cap = self.B, self.dev, self.max_len
+        adv = 1 if parents is None else len(self._tree_arg(parents, "serve", drafting=False))
+        reqs = []
+        for i, (p, m) in enumerate(requests):
+            p, m = [int(t) for t in (p.tolist() if hasattr(p, "tolist") else p)], int(m)
+            assert len(p) >= 1 and m >= 1, f"serve: request {i} - a prompt of at least one token and max_new_tokens >= 1"
+            assert len(p) + m <= cap, f"serve: request {i} can never fit max_len: prompt {len(p)} + max_new_tokens {m} > {cap}"
+            assert self.pager is None or (len(p) + m - 1 + adv + 63) // 64 <= self.pager.N, \
+                f"serve: request {i} can never fit the pool: prompt {len(p)} + max_new_tokens {m} need " \
+                f"{(len(p) + m - 1 + adv + 63) // 64} pages, the pool has {self.pager.N}"
+            reqs.append(dict(i=i, prompt=p, start=len(p), max_new=m, preempted_at=[]))
+        self.set_stopping(None)
+        self.enable_drafting(None, *(self._draft_params or ()))
+        self.set_stopping(stop, 0)
+        advance, run = self._round_graph("serve", parents, sampled)
+        queue, slots, results = deque(reqs), [None] * B, [None] * len(reqs)
+        done = torch.zeros((max(len(reqs), 1), cap), dtype=torch.int32, device=dev)   # the finished texts, read once at the end
+        stats = dict(rounds=0, read_backs=0, admitted=0, preempted=0, peak_pages=B * self.mb if self.pager is None else 0)
+        fin, lens = [stoppingmod.LENGTH] * B, [1] * B
+        free, owned = (None, [0] * B) if self.pager is None else (self.pager.N, [0] * B)
+        while True:
+            # 1., 2. harvest and release
+            ended = [b for b in range(B) if slots[b] is not None and fin[b] != 0]
+            starved = [b for b in ended if fin[b] == stoppingmod.NO_PAGES]
+            if starved:
+                texts = self.history[torch.tensor(starved, dtype=torch.int64, device=dev)].cpu()
+                stats["read_backs"] += 1
+                back = []
+                for j, b in enumerate(starved):
+                    q = slots[b]
+                    q["prompt"] = texts[j, :lens[b]].tolist()
+                    q["preempted_at"].append(lens[b] - q["start"])
+                    back.append(q)
+                queue.extendleft(reversed(back))                            # to the front, in row order
+                stats["preempted"] += len(starved)
+            for b in ended:
+                q = slots[b]
+                if fin[b] != stoppingmod.NO_PAGES:
+                    done[q["i"]].copy_(self.history[b])
+                    results[q["i"]] = dict(length=lens[b], reason=fin[b])
+                slots[b] = None
+            if ended:
+                # a harvested row goes back to what enable_drafting(None) left: a one-token text at its limit, frozen, owning nothing -
+                # the bound of the lengths then follows the running texts alone
+                ended_t = torch.tensor(ended, dtype=torch.int64, device=dev)
+                self.lengths[ended_t] = 1
+                self.prompt_lens[ended_t] = 0
+                self.limit_lens[ended_t] = 0
+                self.finished[ended_t] = stoppingmod.LENGTH
+                self.history[ended_t, 0] = self.tokens[ended_t].to(torch.int32)
+                for b in ended:
+                    fin[b], lens[b], self._text_starts[b] = stoppingmod.LENGTH, 1, 0
+                if self.pager is not None:
+                    self.pager.release(self.pager.rows_mask(ended))
+                    free += sum(owned[b] for b in ended)
+                    for b in ended:
+                        owned[b] = 0
+            # 3. admit, first come first served
+            rows, batch = [], []
+            for b in range(B):
+                if slots[b] is not None or not queue:
+                    continue
+                need = (len(queue[0]["prompt"]) + 1 + 63) // 64
+                if free is not None and need > free:
+                    break
+                q = queue.popleft()
+                slots[b] = q
+                rows.append(b)
+                batch.append(q)
+                if free is not None:
+                    free -= need
+            if rows:
+                self.admit(rows, [q["prompt"] for q in batch], max_new_tokens=[q["max_new"] for q in batch],
+                           text_start=[q["start"] for q in batch], chunk=chunk)
+                stats["admitted"] += len(rows)
+            if all(s is None for s in slots):
+                # (nothing runs and nothing could be admitted: with every page free a request fits - checked above -, so the queue is empty)
+                assert not queue, "serve: a waiting request does not fit the empty pool"
+                break
+            # 4., 5. a burst, and the one read-back
+            burst = self._burst(run, advance, poll_every)
+            assert burst >= 1, "serve: a round does not fit the page tables"
+            stats["rounds"] += burst
+            parts = [self.finished, self.lengths] + ([] if self.pager is None else [self.pager.count, self.pager.owned])
+            state = torch.cat(parts).cpu().tolist()
+            stats["read_backs"] += 1
+            fin, lens = state[:B], state[B:2 * B]
+            self._len_bound = max(lens)
+            if self.pager is not None:
+                free, owned = state[2 * B], state[2 * B + 1:]
+                stats["peak_pages"] = max(stats["peak_pages"], self.pager.N - free)
+        texts = done.cpu()
+        stats["read_backs"] += 1
+        out = []
+        for q, r in zip(reqs, results):
+            out.append(dict(tokens=texts[q["i"], q["start"]:r["length"]].tolist(), reason=r["reason"], preempted_at=q["preempted_at"]))
+        return out, stats
 
     def _record_step(self, emitted=None):
         """history[b, lengths[b] - 1] = tokens[b], after step() advanced the lengths: history_append with a path of the root alone at
@@ -1353,9 +1706,10 @@ class DecodeEngine:
     def _speculate(self, draft, par, max_past=None, out=None, sampled=False):
         """speculate() behind its argument checks.  `draft`: the [B, n] buffer the drafter fills (None: a fresh one); `max_past`, `out`:
         as for _verify_tree_device."""
+        self._reserve(len(par))
         draft = self.draft_tree(par, out=draft)
         past = self.lengths - 1                                             # before the verification advances the lengths
-        res = self._verify_tree_device(draft, par, max_past=max_past, out=out, sampled=sampled)
+        res = self._verify_tree_device(draft, par, max_past=max_past, out=out, sampled=sampled, reserved=True)
         draftingmod.history_append(self.history, past, draft, res[0], res[1], self.tokens)
         return res
 
@@ -1385,6 +1739,7 @@ class DecodeEngine:
         """The step as a generator: yields the row-parallel partial output wherever tensor parallelism needs its sum
         all-reduce (2 per layer), so that the caller decides how the collective is issued (eagerly between hipGraph
         pieces, inside one graph, or not at all at world size 1)."""
+        self._reserve(1)
         if self.with_lm_head:
             torch.index_select(self.embed, 0, self.tokens, out=self.hidden)
         bufs = dict(qa=self.q_act, qo=self.q_attn, q_mlp=self.q_mlp, q_scale=self.q_scale, q_sum=self.q_sum, qkv=self.qkv_buf,
@@ -1511,7 +1866,10 @@ class DecodeEngine:
     def check(self):
         """Raise if a bounded in-launch wait gave up since the last call (the library's direct all-reduce waiting for a
         peer): the tensors of that step are undefined.  Synchronises the device - call it once per batch of steps, not
-        per step."""
+        per step.  Under a page pool also: raise if a reserve or release met a broken invariant, or - while the stop rule is off, when
+        nothing else would tell - if a row was refused pages."""
+        if self.pager is not None:
+            self.pager.check(starved=self.stopping is None)
         if self.ar is not None and self.ar.error():
             raise RuntimeError("direct all-reduce: a wait for a peer rank timed out (ranks more than a few seconds apart, or "
                                "a peer died); the communicators' epochs no longer match - re-create them")

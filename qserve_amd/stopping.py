@@ -7,7 +7,8 @@ stop sequences, per-sequence length limits and frozen rows for a decode loop tha
                   (`qs_stop_update`) has the rule, in exact integers.
     stop_table    a list of token ids and / or id sequences -> the padded (stop_seqs, stop_lens) pair of the rule.
     MAX_STOPS, MAX_STOP_LEN   rows of a stop table, tokens per row.
-    LIVE, STOPPED, LENGTH     the values of `finished`.
+    LIVE, STOPPED, LENGTH, NO_PAGES   the values of `finished` (NO_PAGES: set by the page pool's reserve, qserve_amd.paging - never by
+                  stop_update, which treats it like any other non-zero value: the row is frozen).
 
 Backed by qserve_amd/csrc/stop_update.hip.  DecodeEngine.set_stopping puts it behind the engine's heads; DecodeEngine.generate is the
 loop."""
@@ -19,6 +20,7 @@ from .drafting import MAX_TREE, _history, _rows, _typed
 MAX_STOPS = 32                  # rows of a stop table
 MAX_STOP_LEN = 8                # tokens per row
 LIVE, STOPPED, LENGTH = 0, 1, 2  # `finished`: live, a stop sequence, the length limit
+NO_PAGES = 3                    # ... refused pages by the page pool (paging.PagePool.reserve)
 
 
 def stop_table(stops, device=None, num_rows=None, width=None):
