@@ -38,6 +38,7 @@ from . import paging as pagingmod
 from . import penalties as penaltiesmod
 from . import rope as ropemod
 from . import sampling as samplingmod
+from . import serving as servingmod
 from . import stopping as stoppingmod
 from . import tp as tpmod
 from ._lib import device_status as _device_status
@@ -384,7 +385,6 @@ class DecodeEngine:
         # place; set_lora: True while lora_rows runs behind the four linears of every layer; the step's workspace
         self.lora_table = self.lora_ids = self._lora_step_ws = None
         self._lora = False
-        self._lora_pass = None           # admit: the adapter of every TOKEN of the ragged pass that is running int32 [T] (else None)
 
     def _single_gpu(self, what):
         """What every entry behind the un-cut fp16 lm_head asks for (sampling, penalties, shared prefixes, tree verification, drafting):
@@ -445,16 +445,17 @@ class DecodeEngine:
         """The keys of the tokens the head is about to draw: (b, lengths[b]) - the position the new token will hold."""
         return samplingmod.position_keys(self._samp_ids, self.lengths)
 
-    def _head(self, final, out, keys=None, draft=()):
+    def _head(self, final, out, keys=None, draft=(), penalise=True):
         """The head of every path but the vocabulary-parallel one: the un-quantised fp16 lm_head on the normed rows `final`
         (llama_w4a8_unpad.py:392,476), the penalty launch while set_penalties is on (`draft`: the drafted tokens and the tree of a
         verification; a step's context is the text alone; the prefill entries and the host-walk verify_tree refuse to run while penalties
-        are on, so their heads never penalise), then out[r] = the arg-max of row r or, with `keys`, the token drawn under the
+        are on, so their heads never penalise; `penalise=False`: the head of an admission, which runs while they are on and draws its
+        token before the new text's history is complete), then out[r] = the arg-max of row r or, with `keys`, the token drawn under the
         Philox keys keys() - computed behind the logits, from the lengths as they stand then.  While set_constraint is on the mask
         launch runs behind the penalties: every row under the automaton state of its own node - `fsm_state` for a step and for the
         prompt head, the states along the draft's paths for a verification.  -> the logits (penalised and masked, while on)."""
         logits = torch.matmul(final, self.lm_head.t())
-        if self.penalties is not None:
+        if penalise and self.penalties is not None:
             self._penalize(logits, *draft)
         if self._fsm is not None:
             self._constrain(logits, *draft)
@@ -507,14 +508,14 @@ class DecodeEngine:
         else:
             fused_kernels.invoke_quant(out, x, q_scale)
 
-    def _layer_stack(self, h, bufs, attention, planes):
+    def _layer_stack(self, h, bufs, attention, planes, lora_ids=None):
         """THE transformer layer body (llama_w4a8_unpad.py:330-361 per layer), in place on the fp16 rows h - every path of the engine
         runs this one generator.  `bufs`: the activation buffers under the keys of _prompt_buffers, of exactly h's rows, plus "proj_res",
         where the sum of the row-parallel partial "proj" over the ranks is read from (the same tensor unless a collective writes
         elsewhere).  attention(li, qkv): cache write + attention of layer li on its packed qkv rows, leaving the QUANTISED output in
         bufs["qo"] / ["q_scale"] / ["q_sum"].  `planes`: name -> K-slice plane buffer of the row-parallel projections that run as
         planes (the decode step's; empty elsewhere).  Yields the partial wherever tensor parallelism needs its sum all-reduce (2 per
-        layer; nothing at world size 1), so that the caller decides how the collective is issued."""
+        layer; nothing at world size 1), so that the caller decides how the collective is issued.  `lora_ids`: as for _lora_plan."""
         eps = self.cfg["eps"]
         fuse_sum, fuse = self.group_size == -1, self.fuse_pairs
         qa, qo, q_mlp, q_scale, q_sum, qkv, proj, proj_res, gate_up, mlp_act = (
@@ -522,7 +523,7 @@ class DecodeEngine:
         sums = q_sum if fuse_sum else None
         # set_lora: lora_rows behind every base GEMM (and its bias), on that GEMM's quantised input.  A linear with an adapter takes the
         # path a linear with a bias takes: no planes form, no silu * mul epilogue - the delta has to be added in between
-        lora = self._lora_plan(h.size(0)) if self._lora else None
+        lora = self._lora_plan(h.size(0), lora_ids) if self._lora else None
 
         def lora_add(li, name, out, xq):
             if lora is not None:
@@ -609,11 +610,11 @@ class DecodeEngine:
             else:
                 residual_add_(h, res)
 
-    def _prompt_layers(self, h, bufs, attend):
+    def _prompt_layers(self, h, bufs, attend, lora_ids=None):
         """The layer stack of the is_prompt path, in place on h (fp16 [T, hid]); `bufs`: _prompt_buffers of >= T rows.
         attend(li, qkv) -> fp16 [T, H * 128]: cache write + attention of layer li on its packed qkv rows (prefill: writer + flash
         over the call's own k / v; prefill_chunked: append attention over the pages + the chunk).  The row-parallel partials are
-        summed through the process group, in place."""
+        summed through the process group, in place.  `lora_ids`: as for _lora_plan."""
         b = {k: v[:h.size(0)] for k, v in bufs.items() if k != "moe"}
         b["proj_res"] = b["proj"]
         if self.moe is not None:
@@ -622,7 +623,7 @@ class DecodeEngine:
         def attention(li, qkv):
             self._quant(b["qo"], attend(li, qkv), b["q_sum"], b["q_scale"])
 
-        for partial in self._layer_stack(h, b, attention, {}):
+        for partial in self._layer_stack(h, b, attention, {}, lora_ids):
             tpmod.all_reduce_sum_(partial)
 
     def _prefill_entry(self, what):
@@ -635,26 +636,39 @@ class DecodeEngine:
             f"{what}: the stop rule reads the history of the prompt it was switched on for - set_stopping(None), prefill, " \
             "enable_drafting, then set_stopping again"
 
-    def _prompt_head(self, last_rows, prompt_len):
-        """Last-token states -> `hidden`, first sampled token -> `tokens`, lengths = prompt_len + 1."""
-        self.hidden.copy_(last_rows)
-        layernorm_ops.rms_norm(self.final, self.hidden, self.norm_w, self.cfg["eps"])
-        if self.vocab_parallel:
+    def _prompt_head(self, last_rows, prompt_len, rows=None):
+        """The head behind a prompt pass: last-token states -> `hidden`, first sampled token -> `tokens`, lengths = prompt_len + 1.
+        `rows` None: every row, a prefill entry - written in place, `prompt_len` an int.  Else (admit): the rows `rows` (int64 [R]) alone,
+        `prompt_len` int32 [R]: the full-batch head runs on copies with k = 1 on those rows and 0 elsewhere, and its results are merged
+        into them - every other row keeps its bytes.  Either way: the constraint's mask under `fsm_state`, sampler keys (row, prompt
+        length), no penalties; the tail records the token at column prompt_len of the rows' cleared logs and advances `fsm_state` once;
+        the stop rule does not run here (admit's root check follows it)."""
+        if rows is None:
+            hidden, final, out, pos, k = self.hidden, self.final, self.tokens, self.lengths, None
+            hidden.copy_(last_rows)
+            pos.fill_(prompt_len)                                    # the first new token will hold position prompt_len
+        else:
+            hidden, final, out, pos = self.hidden.clone(), torch.empty_like(self.final), self.tokens.clone(), self.lengths.clone()
+            hidden[rows], pos[rows] = last_rows, prompt_len
+            k = torch.zeros_like(pos)
+            k[rows] = 1
+        layernorm_ops.rms_norm(final, hidden, self.norm_w, self.cfg["eps"])
+        if self.vocab_parallel:                                      # (a prefill entry: admit is single GPU)
             tpmod.all_reduce_sum_(self._head_local())                # in place, through the process group
             self._head_finish(self.head_cand)
         else:
-            def keys():
-                self.lengths.fill_(prompt_len)                       # the first new token will hold position prompt_len
-                return self._step_keys()
-
-            logits = self._head(self.final, self.tokens, keys if self.sampling is not None else None)
+            keys = (lambda: samplingmod.position_keys(self._samp_ids, pos)) if self.sampling is not None else None
+            logits = self._head(final, out, keys, penalise=False)
             if self._logprobs is not None:                           # a new text: the first token's entry lands at column prompt_len
-                self._clear_logprob_logs()
-                self.lengths.fill_(prompt_len)
-            self._emit(logits, self.tokens)                          # (stopping is off here, by _prefill_entry)
-        self.lengths.fill_(prompt_len + 1)
-        self._len_bound = prompt_len + 1
-        self._text_start, self._text_starts = prompt_len, None
+                self._clear_logprob_logs(rows)
+            self._emit(logits, out, lengths=pos, k=k)                # (a prefill entry: stopping is off, by _prefill_entry)
+        if rows is None:
+            self.lengths.fill_(prompt_len + 1)
+            self._len_bound = prompt_len + 1
+            self._text_start, self._text_starts = prompt_len, None
+        else:
+            self.hidden[rows], self.final[rows], self.tokens[rows] = last_rows, torch.index_select(final, 0, rows), torch.index_select(out, 0, rows)
+            self.lengths[rows] = prompt_len + 1
 
     def prefill(self, prompt_len, tokens=None):
         """Run the prompt through the model: per layer  norm+quant -> qkv GEMM -> apply_bias_rope_update_kv_cache
@@ -695,8 +709,6 @@ class DecodeEngine:
         (the chunk's K / V go into the pages, its queries attend to the pages of the earlier chunks and, in fp16, to the chunk
         itself); lm_head and sampling once, after the last chunk.  Ends in the state `prefill` ends in.  `tokens`: as for
         `prefill`, [B * prompt_len], sequence-major."""
-        from . import append as appendmod      # (looked up per call: `appendmod.append` is the seam tests wrap)
-        # (max_past = c0, known on the host: a long past at a small batch is cut into page ranges - append_attention_split.hip)
         self._prefill_entry("prefill_chunked")
         cfg, B, dev = self.cfg, self.B, self.dev
         assert self.with_lm_head and prompt_len + 1 <= self.max_len and chunk >= 1
@@ -705,26 +717,47 @@ class DecodeEngine:
                                    generator=torch.Generator(device=dev).manual_seed(7))
         chunk = min(chunk, prompt_len)
         self._prompt_pages(prompt_len)
+        last = self._prompt_pass(tokens.view(B, prompt_len), [prompt_len] * B, chunk, self._prompt_buffers(B * chunk), 0,
+                                 self._append_over(self.tables))
+        self._prompt_head(last, prompt_len)
 
-        def attend(li, qkv, cu, past, n, c0):
-            return appendmod.append(qkv, cu, past, self.tables[li], self.H, self.Hkv, self.size_per_token, self.rope_base, self.int4,
-                                    max_seqlen_q=n, max_past=c0)
+    def _append_over(self, tables):
+        """The `attend` of a _prompt_pass that is `append.append` over the pass's sequences' rows of tables[li]."""
+        from . import append as appendmod      # (looked up per call: `appendmod.append` is the seam tests wrap)
+        # (max_past = c0, known on the host: a long past at a small batch is cut into page ranges - append_attention_split.hip)
+        def attend(li, qkv, cu, past, n, c0, live):
+            return appendmod.append(qkv, cu, past, tables[li] if live is None else tables[li][live], self.H, self.Hkv, self.size_per_token,
+                                    self.rope_base, self.int4, max_seqlen_q=n, max_past=c0)
+        return attend
 
-        h = self._prompt_chunks(tokens.view(B, prompt_len), chunk, self._prompt_buffers(B * chunk), 0, attend)
-        self._prompt_head(h.view(B, -1, self.hid)[:, -1], prompt_len)
-
-    def _prompt_chunks(self, tokens, chunk, bufs, base, attend):
-        """The layer stack over `tokens` [rows, L], `chunk` columns per pass (the last pass may be shorter), sequence `r` of a pass being
-        tokens[r, c0 : c0 + n] behind a past of base + c0.  attend(li, qkv, cu_seqlens, past_lens, n, c0) -> fp16 [rows * n, H, 128]:
-        the append attention of layer li.  -> the hidden rows of the last pass, [rows * n, hid] sequence-major."""
-        rows, dev, h = tokens.size(0), self.dev, None
-        for c0 in range(0, tokens.size(1), chunk):
-            n = min(chunk, tokens.size(1) - c0)
-            h = torch.index_select(self.embed, 0, tokens[:, c0:c0 + n].reshape(-1))
-            cu = torch.arange(0, rows + 1, device=dev, dtype=torch.int32) * n
-            past = torch.full((rows,), base + c0, dtype=torch.int32, device=dev)
-            self._prompt_layers(h, bufs, lambda li, qkv: attend(li, qkv, cu, past, n, c0).reshape(rows * n, -1))
-        return h
+    def _prompt_pass(self, tokens, lens, chunk, bufs, base, attend, lora_ids=None):
+        """THE chunked prompt pass: the layer stack over R sequences of possibly different lengths, `tokens` [R, >= max(lens)] on the
+        device (padded; sequence r is tokens[r, :lens[r]]) and `lens` a host list, in passes of `chunk` columns: pass c0 runs
+        tokens[r, c0 : c0 + chunk] of every sequence that has a token left - one with none is left out -, behind a past of base + c0,
+        with cu_seqlens from the pass's lengths.  attend(li, qkv, cu_seqlens, past_lens, n, c0, live) -> fp16 [T, H, 128]: the append
+        attention of layer li over the pass's T rows; n: the longest sequence of the pass; `live`: the sequences in it, int64 indices
+        on the device, or None when all are.  `bufs`: _prompt_buffers of at least R * chunk rows.  `lora_ids`: the adapter of every
+        SEQUENCE int32 [R], handed on per token (None: the engine's, which needs equal lengths).  -> every sequence's last hidden row,
+        gathered where the sequence ends, [R, hid]."""
+        R, dev = len(lens), self.dev
+        last = torch.empty((R, self.hid), dtype=torch.float16, device=dev)
+        for c0 in range(0, max(lens), chunk):
+            live = [r for r in range(R) if lens[r] > c0]
+            ns = [min(chunk, lens[r] - c0) for r in live]
+            cu_h = [sum(ns[:j]) for j in range(len(ns) + 1)]
+            T, n = cu_h[-1], max(ns)
+            h = torch.index_select(self.embed, 0, torch.cat([tokens[r, c0:c0 + m] for r, m in zip(live, ns)]))
+            cu = torch.tensor(cu_h, dtype=torch.int32, device=dev)
+            past = torch.full((len(live),), base + c0, dtype=torch.int32, device=dev)
+            live_t = None if len(live) == R else torch.tensor(live, dtype=torch.int64, device=dev)
+            ids = None if lora_ids is None else torch.repeat_interleave(     # the adapter of every token of this pass
+                lora_ids if live_t is None else torch.index_select(lora_ids, 0, live_t), torch.tensor(ns, dtype=torch.int64, device=dev), output_size=T)
+            self._prompt_layers(h, bufs, lambda li, qkv: attend(li, qkv, cu, past, n, c0, live_t).reshape(T, -1), ids)
+            ended = [(r, cu_h[j + 1] - 1) for j, r in enumerate(live) if c0 + ns[j] == lens[r]]
+            if ended:
+                last[torch.tensor([r for r, _ in ended], dtype=torch.int64, device=dev)] = \
+                    torch.index_select(h, 0, torch.tensor([e for _, e in ended], dtype=torch.int64, device=dev))
+        return last
 
     def prefill_shared(self, prefix_tokens, suffix_tokens, chunk=None):
         """`prefill_chunked` for B prompts that begin with the SAME `prefix_tokens` [P] and go on with their own `suffix_tokens`
@@ -757,23 +790,18 @@ class DecodeEngine:
         chunk = max(P64, R) if chunk is None else min(chunk, max(P64, R))
         bufs = self._prompt_buffers(max(B * min(chunk, R), min(chunk, P64)))
         # 1. the whole pages of the prefix, once, through row 0 of the tables
-        def attend_prefix(li, qkv, cu, past, n, c0):
-            return appendmod.append(qkv, cu, past, self.tables[li][0:1], self.H, self.Hkv, self.size_per_token, self.rope_base,
-                                    self.int4, max_seqlen_q=n, max_past=c0)
-
-        self._prompt_chunks(prefix_tokens[:P64].unsqueeze(0), chunk, bufs, 0, attend_prefix)
+        self._prompt_pass(prefix_tokens[:P64].unsqueeze(0), [P64], chunk, bufs, 0, self._append_over([t[0:1] for t in self.tables]))
         # 2. every sequence names sequence 0's prefix pages
         for t in self.tables:
             t[:, :, :P64 // 64] = t[0:1, :, :P64 // 64]
         # 3. the rest of every prompt, the shared pages read once for the batch
         groups = appendmod.shared_prefix_groups([B], [P64], dev, batch=B)
 
-        def attend_own(li, qkv, cu, past, n, c0):
+        def attend_own(li, qkv, cu, past, n, c0, live):
             return appendmod.append_shared(qkv, cu, past, self.tables[li], self.H, self.Hkv, self.size_per_token, self.rope_base,
                                            self.int4, groups, max_seqlen_q=n, max_group_tokens=B * n, max_prefix=P64, max_suffix_past=c0)
 
-        h = self._prompt_chunks(own, chunk, bufs, P64, attend_own)
-        self._prompt_head(h.view(B, -1, self.hid)[:, -1], P + S)
+        self._prompt_head(self._prompt_pass(own, [R] * B, chunk, bufs, P64, attend_own), P + S)
 
     # ---- verification of a draft tree (no reference counterpart; qserve_amd.append, csrc/append_tree.hip) ---------------------
     def verify_tree(self, draft_tokens, parents, device_walk=False, sampled=False):
@@ -1149,11 +1177,10 @@ class DecodeEngine:
         self._logprobs = (top, bool(tempered))
         self._clear_logprob_logs()
 
-    def _clear_logprob_logs(self):
-        self.logprob_log.fill_(float("nan"))
-        self.rank_log.zero_()
-        self.top_ids_log.fill_(-1)
-        self.top_lp_log.fill_(float("nan"))
+    def _clear_logprob_logs(self, rows=None):
+        """Empty the logs of the rows `rows` (int64 indices; None: of every row)."""
+        for log, empty in ((self.logprob_log, float("nan")), (self.rank_log, 0), (self.top_ids_log, -1), (self.top_lp_log, float("nan"))):
+            log[slice(None) if rows is None else rows] = empty
 
     def logprobs(self):
         """Read the logs of set_logprobs once -> per sequence a dict of lists over its generated text, positions prompt_len ..
@@ -1276,24 +1303,22 @@ class DecodeEngine:
         self.lora_ids.copy_(ids.to(torch.int32))
         self._lora = True
 
-    def _lora_plan(self, rows):
+    def _lora_plan(self, rows, ids=None):
         """(adapter ids, rows_per_seq, workspace) of the lora_rows calls of a layer stack over `rows` rows: `lora_ids` with the step's
         persistent workspace, or with a fresh one sized for the largest of the four linears (inside a capture it lives in the graph's
-        pool); a ragged pass of admit() has left its own ids in `_lora_pass`, one per token (rows_per_seq = 1)."""
-        t = self.lora_table
-        if self._lora_pass is not None:
-            assert self._lora_pass.numel() == rows
-            per_seq, ids = 1, self._lora_pass
-        else:
-            assert rows % self.B == 0
+        pool).  `ids`: the adapter of every TOKEN of a ragged pass int32 [rows] (rows_per_seq = 1); None: `lora_ids`, rows / B rows per
+        sequence."""
+        t, per_seq = self.lora_table, 1
+        if ids is None:
             if rows == self.B:
                 return self.lora_ids, 1, self._lora_step_ws
             per_seq, ids = rows // self.B, self.lora_ids
+        assert ids.numel() * per_seq == rows
         ws = max(loramod.workspace_bytes(rows, K, t.rank, len(ends)) for K, _, ends in t.shapes.values())
         return ids, per_seq, torch.empty((max(ws, 16),), dtype=torch.uint8, device=self.dev)
 
     # ---- what the features share: the tail of a round, and what a capture freezes and keeps --------------------------------------
-    def _emit(self, logits, next_token, node_tokens=None, accept_idx=None, accept_lens=None, last_row=None):
+    def _emit(self, logits, next_token, node_tokens=None, accept_idx=None, accept_lens=None, last_row=None, lengths=None, k=None):
         """THE tail of a round, on what it is about to emit, at the lengths as they stand (not yet advanced): behind the head of step()
         (hence capture() / run()) and of a prefill entry (where stopping is off), between the walk and the commit of
         verify_tree(device_walk=True) (hence capture_verify, speculate, capture_speculate).  `logits`: the rows the head saw;
@@ -1304,14 +1329,16 @@ class DecodeEngine:
           2. set_logprobs: `logprobs.logprob_path` scores the (clipped) path's rows, each for the token behind it - k = 0 writes nothing;
           3. set_constraint: `constraints.advance` moves `fsm_state` from the state of the (clipped) path's last row - under a draft its
              node's, of `_fsm_node_state` - over the token it emitted; k = 0 keeps the state.
-        -> k while stopping is on (what the lengths advance by), else None."""
-        k = accept_lens
-        if self.stopping is not None:
-            k = self._stop_update(next_token, node_tokens=node_tokens, accept_idx=accept_idx, accept_lens=accept_lens, last_row=last_row,
-                                  out_lens=self._stop_k if accept_lens is None else None)
+        -> k while stopping is on (what the lengths advance by), else None.  The head of an admission (`_prompt_head` over some rows)
+        hands over `k` - 1 on the admitted rows, 0 elsewhere - in place of step 1, and `lengths`, the position of every row's token."""
+        if k is None:
+            k = accept_lens
+            if self.stopping is not None:
+                k = self._stop_update(next_token, node_tokens=node_tokens, accept_idx=accept_idx, accept_lens=accept_lens, last_row=last_row,
+                                      out_lens=self._stop_k if accept_lens is None else None)
         if self._logprobs is not None:
             top, tempered = self._logprobs
-            logprobsmod.logprob_path(logits, node_tokens, accept_idx, k, next_token, self.lengths,
+            logprobsmod.logprob_path(logits, node_tokens, accept_idx, k, next_token, self.lengths if lengths is None else lengths,
                                      temperature=self._samp_t[:self.B] if tempered else 1.0, top=top,
                                      out=(self.logprob_log, self.rank_log, self.top_ids_log, self.top_lp_log))
         if self._fsm is not None:
@@ -1413,20 +1440,15 @@ class DecodeEngine:
         (`pager.free_pages()`, or serve()'s bookkeeping): a refused row's prompt goes to the sink, and it ends with NO_PAGES while the stop
         rule is on (check() raises while it is off).
 
-        The prompts run in passes of `chunk` tokens per sequence (None: whole) through the layer stack of the prompt path, `append.append`
-        over the named rows' table rows with a ragged cu_seqlens_q and per-row past_lens - a sequence with no token left is left out of
-        the pass.  For equal-length prompts in every row these are the calls of prefill_chunked.  Each sequence's last hidden row goes to
-        hidden[row]; the full-batch head draws the first token as a prefill head does - the constraint's mask under the row's
-        `start_states` entry (an int or one per row; default 0), sampler keys (row, P_r), no penalties - and its results are merged into
-        the admitted rows alone; the log entry lands at column P_r of that row's cleared logs, `fsm_state` advances once.  Then per
-        row: `tokens`, lengths = P_r + 1, history = the prompt and the first token behind zeros, prompt_lens = `text_start` (an int or
-        one per row, 0 .. P_r; None: P_r - the text a resumed request generated earlier counts as generated), limit_lens = prompt_lens +
-        `max_new_tokens` (an int or one per row; None: the history's capacity; needs set_stopping to have been called), finished = 0
-        followed by the root check of set_stopping while the stop rule is on.  Unlike the prefill entries it runs while stopping and
-        penalties are on, and under set_lora: a pass hands `lora.lora_rows` one adapter id per TOKEN, lora_ids[row] repeated over the
-        row's tokens of the pass (rows_per_seq = 1).  No capture is invalidated.  `start_states` needs set_constraint to be on.  Every
-        argument is checked before the first write.  Single GPU, with the lm_head."""
-        from . import append as appendmod
+        The prompts, uploaded once, run through `_prompt_pass` in passes of `chunk` tokens per sequence (None: whole), `append.append`
+        over the named rows' table rows - for equal-length prompts in every row the calls of prefill_chunked -, under set_lora with
+        lora_ids[row] for every token of a row; `_prompt_head` over `rows` draws the first tokens, the constraint's mask under the
+        row's `start_states` entry (an int or one per row; default 0; needs set_constraint to be on).  Then per row: history = the
+        prompt and the first token behind zeros, prompt_lens = `text_start` (an int or one per row, 0 .. P_r; None: P_r - the text a
+        resumed request generated earlier counts as generated), limit_lens = prompt_lens + `max_new_tokens` (an int or one per row;
+        None: the history's capacity; needs set_stopping to have been called), finished = 0 followed by the root check of
+        set_stopping while the stop rule is on.  Unlike the prefill entries it runs while stopping and penalties are on, and under
+        set_lora.  No capture is invalidated.  Every argument is checked before the first write.  Single GPU, with the lm_head."""
         self._single_gpu("admit")
         assert self.history is not None, "admit: enable_drafting first (enable_drafting(None) for an empty batch): it writes `history`"
         B, dev, cap = self.B, self.dev, self.max_len
@@ -1463,10 +1485,10 @@ class DecodeEngine:
         text = torch.zeros((R, cap), dtype=torch.int32)
         for i, p in enumerate(pl):
             text[i, :Ps[i]] = p.to(torch.int32)
-        self.history[rows_t] = text.to(dev)
+        text_d = text.to(dev)                                               # the one upload of the prompts
+        self.history[rows_t] = text_d
         self.prompt_lens[rows_t] = torch.tensor(starts, **i32)
-        if self._text_starts is None:
-            self._text_starts = [self._prompt_len] * B
+        self._text_starts = self._row_starts()
         for r, s in zip(rows, starts):
             self._text_starts[r] = s
         if limits is not None:
@@ -1482,70 +1504,12 @@ class DecodeEngine:
             self.pager.release(self.pager.rows_mask(rows))
             self.pager.reserve(self._all_rows, 0, extra_rows=extra, finished=self.finished if self.stopping is not None else None)
         # ---- the prompts, in passes of `chunk` tokens per sequence, over the rows' table rows (read AFTER the reserve filled them)
-        tabs = [t[rows_t] for t in self.tables]
-        bufs = self._prompt_buffers(R * chunk)
-        last = torch.empty((R, self.hid), dtype=torch.float16, device=dev)
-        row_lora = torch.index_select(self.lora_ids, 0, rows_t) if self._lora else None
-        for c0 in range(0, maxP, chunk):
-            live = [i for i in range(R) if Ps[i] > c0]
-            ns = [min(chunk, Ps[i] - c0) for i in live]
-            cu_h = [0]
-            for n in ns:
-                cu_h.append(cu_h[-1] + n)
-            T = cu_h[-1]
-            h = torch.index_select(self.embed, 0, torch.cat([pl[i][c0:c0 + n] for i, n in zip(live, ns)]).to(dev))
-            cu, past = torch.tensor(cu_h, **i32), torch.full((len(live),), c0, **i32)
-            if len(live) == R:
-                tl = tabs
-            else:
-                live_t = torch.tensor(live, dtype=torch.int64, device=dev)
-                tl = [t[live_t] for t in tabs]
-            if row_lora is not None:                                        # set_lora: the adapter of every token of this pass
-                self._lora_pass = torch.repeat_interleave(torch.index_select(row_lora, 0, torch.tensor(live, dtype=torch.int64, device=dev)),
-                                                          torch.tensor(ns, dtype=torch.int64, device=dev))
-            try:
-                self._prompt_layers(h, bufs, lambda li, qkv: appendmod.append(
-                    qkv, cu, past, tl[li], self.H, self.Hkv, self.size_per_token, self.rope_base, self.int4, max_seqlen_q=max(ns),
-                    max_past=c0).reshape(T, -1))
-            finally:
-                self._lora_pass = None
-            ended = [(i, cu_h[j + 1] - 1) for j, (i, n) in enumerate(zip(live, ns)) if c0 + n == Ps[i]]
-            if ended:
-                last[torch.tensor([i for i, _ in ended], dtype=torch.int64, device=dev)] = \
-                    torch.index_select(h, 0, torch.tensor([e for _, e in ended], dtype=torch.int64, device=dev))
-        # ---- the full-batch head on copies, merged into the admitted rows: k = 1 there, 0 elsewhere
-        hidden = self.hidden.clone()
-        hidden[rows_t] = last
-        final = torch.empty_like(hidden)
-        layernorm_ops.rms_norm(final, hidden, self.norm_w, self.cfg["eps"])
-        logits = torch.matmul(final, self.lm_head.t())
-        if self._fsm is not None:
-            self._constrain(logits)
-        pos = self.lengths.clone()
-        pos[rows_t] = P_t                                                   # the first new token will hold position P_r
-        out = self.tokens.clone()
-        if self.sampling is not None:
-            self._sample(logits, out, samplingmod.position_keys(self._samp_ids, pos))
-        else:
-            argmax_rows_(logits, out)
-        k = torch.zeros((B,), **i32)
-        k[rows_t] = 1
-        if self._logprobs is not None:
-            top, tempered = self._logprobs
-            self.logprob_log[rows_t] = float("nan")
-            self.rank_log[rows_t] = 0
-            self.top_ids_log[rows_t] = -1
-            self.top_lp_log[rows_t] = float("nan")
-            logprobsmod.logprob_path(logits, None, None, k, out, pos, temperature=self._samp_t[:B] if tempered else 1.0, top=top,
-                                     out=(self.logprob_log, self.rank_log, self.top_ids_log, self.top_lp_log))
-        if self._fsm is not None:
-            constraintsmod.advance(self.fsm_state, out, *self._fsm, accept_lens=k)
-        first = torch.index_select(out, 0, rows_t)
-        self.hidden[rows_t] = last
-        self.final[rows_t] = torch.index_select(final, 0, rows_t)
-        self.tokens[rows_t] = first
-        self.lengths[rows_t] = P_t + 1
-        self.history[rows_t, P_t.to(torch.int64)] = first.to(torch.int32)
+        last = self._prompt_pass(text_d[:, :maxP].to(torch.int64), Ps, chunk, self._prompt_buffers(R * chunk), 0,
+                                 self._append_over([t[rows_t] for t in self.tables]),
+                                 torch.index_select(self.lora_ids, 0, rows_t) if self._lora else None)
+        # ---- the head and the tail over the admitted rows, then what they leave to the text
+        self._prompt_head(last, P_t, rows_t)
+        self.history[rows_t, P_t.to(torch.int64)] = torch.index_select(self.tokens, 0, rows_t).to(torch.int32)
         self._len_bound = max(self._len_bound, maxP + 1)
         if self.stopping is not None:                                       # the root check of set_stopping: a first token that is a
             self._stop_k.zero_()                                            # stop, or a row at its limit; every other row's current
@@ -1560,115 +1524,58 @@ class DecodeEngine:
           4. the captured step graph - with `parents`, the captured speculate graph - is replayed `poll_every` times (generate()'s
              burst),
           5. (`finished`, `lengths`, the pool's `count` and `owned`) are read back in one copy.
-        A row that ended with NO_PAGES is PREEMPTED: its request returns to the front of the queue with prompt := its text so far and
-        text_start := the original prompt length, so its length limit and penalty window are unchanged; the prompt is recomputed.  Reading
-        that text is one more read-back for the bursts that preempt.  A resumed text need not be bit-identical to an un-preempted one:
+        Every decision is a `serving.Scheduler`'s - which rows ended, what a row that ended with NO_PAGES is PREEMPTED to, what is placed
+        where, the page accounting, `stats`, the end; this loop performs them.  A preempted request's prompt is recomputed; reading its
+        text is one more read-back for the bursts that preempt.  A resumed text need not be bit-identical to an un-preempted one:
         prompt and decode attention round differently, sampler keys follow the row, and log entries from before a preemption are lost.
         Raises before anything runs for a request that can never fit max_len (P + max_new > max_len) or the pool
         (ceil((P + max_new - 1 + n) / 64) > N, n the round's tokens: 1, or the tree's nodes).
         -> (per request, in order, dict(tokens: the generated text, reason: 1 a stop / 2 the length, preempted_at: the generated
         tokens it held at each preemption), stats dict(rounds, read_backs, admitted, preempted, peak_pages: the most pages in use at a
         read-back - the static batch * mb without a pool))."""
-        from collections import deque
         self._single_gpu("serve")
         assert poll_every >= 1
-        B, dev, cap = self.B, self.dev, self.max_len
+        B, dev = self.B, self.dev
         adv = 1 if parents is None else len(self._tree_arg(parents, "serve", drafting=False))
-        reqs = []
-        for i, (p, m) in enumerate(requests):
-            p, m = [int(t) for t in (p.tolist() if hasattr(p, "tolist") else p)], int(m)
-            assert len(p) >= 1 and m >= 1, f"serve: request {i} - a prompt of at least one token and max_new_tokens >= 1"
-            assert len(p) + m <= cap, f"serve: request {i} can never fit max_len: prompt {len(p)} + max_new_tokens {m} > {cap}"
-            assert self.pager is None or (len(p) + m - 1 + adv + 63) // 64 <= self.pager.N, \
-                f"serve: request {i} can never fit the pool: prompt {len(p)} + max_new_tokens {m} need " \
-                f"{(len(p) + m - 1 + adv + 63) // 64} pages, the pool has {self.pager.N}"
-            reqs.append(dict(i=i, prompt=p, start=len(p), max_new=m, preempted_at=[]))
+        sched = servingmod.Scheduler(requests, B, self.max_len, stoppingmod.NO_PAGES, pool_pages=None if self.pager is None else self.pager.N,
+                                     advance=adv, static_pages=B * self.mb)
         self.set_stopping(None)
         self.enable_drafting(None, *(self._draft_params or ()))
         self.set_stopping(stop, 0)
         advance, run = self._round_graph("serve", parents, sampled)
-        queue, slots, results = deque(reqs), [None] * B, [None] * len(reqs)
-        done = torch.zeros((max(len(reqs), 1), cap), dtype=torch.int32, device=dev)   # the finished texts, read once at the end
-        stats = dict(rounds=0, read_backs=0, admitted=0, preempted=0, peak_pages=B * self.mb if self.pager is None else 0)
-        fin, lens = [stoppingmod.LENGTH] * B, [1] * B
-        free, owned = (None, [0] * B) if self.pager is None else (self.pager.N, [0] * B)
+        done = torch.zeros((max(len(sched.reqs), 1), self.max_len), dtype=torch.int32, device=dev)   # the finished texts, read once at the end
         while True:
             # 1., 2. harvest and release
-            ended = [b for b in range(B) if slots[b] is not None and fin[b] != 0]
-            starved = [b for b in ended if fin[b] == stoppingmod.NO_PAGES]
-            if starved:
-                texts = self.history[torch.tensor(starved, dtype=torch.int64, device=dev)].cpu()
-                stats["read_backs"] += 1
-                back = []
-                for j, b in enumerate(starved):
-                    q = slots[b]
-                    q["prompt"] = texts[j, :lens[b]].tolist()
-                    q["preempted_at"].append(lens[b] - q["start"])
-                    back.append(q)
-                queue.extendleft(reversed(back))                            # to the front, in row order
-                stats["preempted"] += len(starved)
-            for b in ended:
-                q = slots[b]
-                if fin[b] != stoppingmod.NO_PAGES:
-                    done[q["i"]].copy_(self.history[b])
-                    results[q["i"]] = dict(length=lens[b], reason=fin[b])
-                slots[b] = None
+            ended, starved = sched.ended()
+            texts = self.history[torch.tensor(starved, dtype=torch.int64, device=dev)].cpu().tolist() if starved else []
+            for b, i in sched.retire(texts):
+                done[i].copy_(self.history[b])
             if ended:
                 # a harvested row goes back to what enable_drafting(None) left: a one-token text at its limit, frozen, owning nothing -
                 # the bound of the lengths then follows the running texts alone
                 ended_t = torch.tensor(ended, dtype=torch.int64, device=dev)
-                self.lengths[ended_t] = 1
-                self.prompt_lens[ended_t] = 0
-                self.limit_lens[ended_t] = 0
-                self.finished[ended_t] = stoppingmod.LENGTH
+                for t, v in ((self.lengths, 1), (self.prompt_lens, 0), (self.limit_lens, 0), (self.finished, stoppingmod.LENGTH)):
+                    t[ended_t] = v
                 self.history[ended_t, 0] = self.tokens[ended_t].to(torch.int32)
                 for b in ended:
-                    fin[b], lens[b], self._text_starts[b] = stoppingmod.LENGTH, 1, 0
+                    self._text_starts[b] = 0
                 if self.pager is not None:
                     self.pager.release(self.pager.rows_mask(ended))
-                    free += sum(owned[b] for b in ended)
-                    for b in ended:
-                        owned[b] = 0
-            # 3. admit, first come first served
-            rows, batch = [], []
-            for b in range(B):
-                if slots[b] is not None or not queue:
-                    continue
-                need = (len(queue[0]["prompt"]) + 1 + 63) // 64
-                if free is not None and need > free:
-                    break
-                q = queue.popleft()
-                slots[b] = q
-                rows.append(b)
-                batch.append(q)
-                if free is not None:
-                    free -= need
+            # 3. admit what the scheduler placed
+            rows, batch = sched.place()
             if rows:
                 self.admit(rows, [q["prompt"] for q in batch], max_new_tokens=[q["max_new"] for q in batch],
                            text_start=[q["start"] for q in batch], chunk=chunk)
-                stats["admitted"] += len(rows)
-            if all(s is None for s in slots):
-                # (nothing runs and nothing could be admitted: with every page free a request fits - checked above -, so the queue is empty)
-                assert not queue, "serve: a waiting request does not fit the empty pool"
+            if sched.idle():
                 break
             # 4., 5. a burst, and the one read-back
             burst = self._burst(run, advance, poll_every)
             assert burst >= 1, "serve: a round does not fit the page tables"
-            stats["rounds"] += burst
             parts = [self.finished, self.lengths] + ([] if self.pager is None else [self.pager.count, self.pager.owned])
             state = torch.cat(parts).cpu().tolist()
-            stats["read_backs"] += 1
-            fin, lens = state[:B], state[B:2 * B]
-            self._len_bound = max(lens)
-            if self.pager is not None:
-                free, owned = state[2 * B], state[2 * B + 1:]
-                stats["peak_pages"] = max(stats["peak_pages"], self.pager.N - free)
-        texts = done.cpu()
-        stats["read_backs"] += 1
-        out = []
-        for q, r in zip(reqs, results):
-            out.append(dict(tokens=texts[q["i"], q["start"]:r["length"]].tolist(), reason=r["reason"], preempted_at=q["preempted_at"]))
-        return out, stats
+            sched.observe(burst, state[:B], state[B:2 * B], *(() if self.pager is None else (state[2 * B], state[2 * B + 1:])))
+            self._len_bound = max(sched.lens)
+        return sched.output(done.cpu().tolist())
 
     def _record_step(self, emitted=None):
         """history[b, lengths[b] - 1] = tokens[b], after step() advanced the lengths: history_append with a path of the root alone at

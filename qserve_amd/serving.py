@@ -1,0 +1,92 @@
+"""What `DecodeEngine.serve` decides, on the host alone: no engine, no device tensor, no kernel binding - the engine's loop performs what
+a `Scheduler` says and tells it what it read back.  The policy: first come first served with head-of-line blocking; a row that ended
+for want of pages is preempted, back to the FRONT of the queue; the pool's pages are accounted from the read-backs."""
+from collections import deque
+
+
+class Scheduler:
+    """`requests`: (prompt_tokens, max_new_tokens) in order of arrival, for `batch` rows of `max_len` slots.  `starved`: the `finished`
+    code of a row that was refused pages (stopping.NO_PAGES).  `pool_pages`: the pool's N (None: static pages, `static_pages` of them,
+    and no accounting); `advance`: the tokens a round writes at most (1, or the tree's nodes).  Refuses, before any state exists, a
+    request that can never fit.  A request is dict(i, prompt, start, max_new, preempted_at); `slots[b]` is the request in row b."""
+
+    def __init__(self, requests, batch, max_len, starved, pool_pages=None, advance=1, static_pages=0):
+        reqs = []
+        for i, (p, m) in enumerate(requests):
+            p, m = [int(t) for t in (p.tolist() if hasattr(p, "tolist") else p)], int(m)
+            assert len(p) >= 1 and m >= 1, f"serve: request {i} - a prompt of at least one token and max_new_tokens >= 1"
+            assert len(p) + m <= max_len, f"serve: request {i} can never fit max_len: prompt {len(p)} + max_new_tokens {m} > {max_len}"
+            assert pool_pages is None or (len(p) + m - 1 + advance + 63) // 64 <= pool_pages, \
+                f"serve: request {i} can never fit the pool: prompt {len(p)} + max_new_tokens {m} need " \
+                f"{(len(p) + m - 1 + advance + 63) // 64} pages, the pool has {pool_pages}"
+            reqs.append(dict(i=i, prompt=p, start=len(p), max_new=m, preempted_at=[]))
+        self.B, self.N, self.starved, self.reqs = batch, pool_pages, starved, reqs
+        self.queue, self.slots, self.results = deque(reqs), [None] * batch, [None] * len(reqs)
+        self.fin, self.lens = [0] * batch, [1] * batch                   # the last observation
+        self.free, self.owned = pool_pages, [0] * batch                  # free pages (None without a pool), pages per row
+        self.stats = dict(rounds=0, read_backs=0, admitted=0, preempted=0, peak_pages=static_pages if pool_pages is None else 0)
+
+    def ended(self):
+        """-> (the occupied rows that ended by the last observation, those of them that starved), ascending."""
+        ended = [b for b in range(self.B) if self.slots[b] is not None and self.fin[b] != 0]
+        return ended, [b for b in ended if self.fin[b] == self.starved]
+
+    def retire(self, texts=()):
+        """Free the rows of ended(), giving their pages back.  A starved row's request is preempted: `texts` has its text row (one per
+        starved row, in row order - reading them is one read-back) and the request returns to the front of the queue, in row order, with
+        prompt := the text so far; `start` and `max_new` stay, so its length limit and penalty window do; `preempted_at` gains the
+        generated tokens it held.  Any other row's request is done: results[i] = dict(length, reason).  -> those (row, i)."""
+        ended, starved = self.ended()
+        assert len(texts) == len(starved)
+        for b, text in zip(starved, texts):
+            self.slots[b]["prompt"] = [int(t) for t in text[:self.lens[b]]]
+            self.slots[b]["preempted_at"].append(self.lens[b] - self.slots[b]["start"])
+        self.queue.extendleft(self.slots[b] for b in reversed(starved))
+        self.stats["preempted"] += len(starved)
+        self.stats["read_backs"] += 1 if starved else 0
+        done = [(b, self.slots[b]["i"]) for b in ended if b not in starved]
+        for b, i in done:
+            self.results[i] = dict(length=self.lens[b], reason=self.fin[b])
+        for b in ended:
+            self.slots[b] = None
+            if self.free is not None:
+                self.free, self.owned[b] = self.free + self.owned[b], 0
+        return done
+
+    def place(self):
+        """Waiting requests into free rows, rows ascending, in order of arrival, while the free pages cover the ceil((P + 1) / 64) of
+        each; the first that they do not cover blocks the queue, whatever is behind it.  -> (rows, their requests): what to admit."""
+        rows = []
+        for b in range(self.B):
+            if self.slots[b] is not None or not self.queue:
+                continue
+            need = (len(self.queue[0]["prompt"]) + 1 + 63) // 64
+            if self.free is not None:
+                if need > self.free:
+                    break
+                self.free -= need
+            self.slots[b] = self.queue.popleft()
+            rows.append(b)
+        self.stats["admitted"] += len(rows)
+        return rows, [self.slots[b] for b in rows]
+
+    def idle(self):
+        """Nothing runs, so nothing waits (with every page free a request fits - checked on entry): the loop is over."""
+        assert self.slots.count(None) < self.B or not self.queue, "serve: a waiting request does not fit the empty pool"
+        return self.slots.count(None) == self.B
+
+    def observe(self, rounds, finished, lengths, free=None, owned=None):
+        """The one read-back behind a burst of `rounds` rounds: `finished` and `lengths` per row and, under a pool, its free count and
+        the pages every row owns - which replace the scheduler's own estimate."""
+        self.stats["rounds"] += rounds
+        self.stats["read_backs"] += 1
+        self.fin, self.lens = list(finished), list(lengths)
+        if self.N is not None:
+            self.free, self.owned = int(free), list(owned)
+            self.stats["peak_pages"] = max(self.stats["peak_pages"], self.N - self.free)
+
+    def output(self, texts):
+        """`texts[i]`: the text row of request i (read once, one read-back) -> serve()'s return value."""
+        self.stats["read_backs"] += 1
+        return [dict(tokens=list(texts[q["i"]][q["start"]:r["length"]]), reason=r["reason"], preempted_at=q["preempted_at"])
+                for q, r in zip(self.reqs, self.results)], self.stats

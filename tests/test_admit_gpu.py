@@ -8,7 +8,8 @@
      later texts are those of a twin that admitted nothing;
   4. with sampling, a constraint with per-row start states and top-5 log-probabilities on, the admitted row's first token, state and
      log entry at column P_r are those of a uniform prefill_chunked of that prompt in the same row of a twin;
-  5. under set_lora every admitted row runs under its own adapter: a ragged admit against uniform prefill_chunked twins."""
+  5. under set_lora every admitted row runs under its own adapter: a ragged admit against uniform prefill_chunked twins;
+  6. while penalties are on the admission head does not penalise: the admitted row against a twin whose penalties are off."""
 import numpy as np
 import pytest
 import torch
@@ -192,4 +193,43 @@ def test_an_admit_under_lora_runs_every_row_under_its_own_adapter(gpu):
         for i, (x, y) in enumerate(zip(E.row_slots(a, r, n), E.row_slots(twin, r, n))):
             assert torch.equal(x, y), f"row {r}: slots differ (piece {i})"
         assert torch.equal(a.hidden[r], base.hidden[r]) == (ids[r] < 0), f"row {r}: adapter {ids[r]} against the base model"
+    a.check()
+
+
+def test_an_admit_while_penalties_are_on_does_not_penalise(gpu, monkeypatch):
+    """Two engines in the same mid-generation state, `a` then with set_penalties(1.3, 0.2, 0.2) on: both admit the same 9 tokens (in
+    passes of 4) into the finished row 0.  The row's first token, hidden row and pages are equal byte for byte and the admit launches
+    no penalize_rows - the step behind it does -; rows 1 and 2 of `a` keep their bytes."""
+    import _page_engine as E
+    from qserve_amd import penalties
+    P, n = 20, 9
+    toks, prompt = _tokens(B * P, 3).to(gpu), _tokens(5, 8).repeat(2)[:n]       # (a prompt that repeats itself: penalties would bite)
+    a, twin = _engine(page_pool=12), _engine(page_pool=12)
+    for e in (a, twin):
+        e.prefill_chunked(P, 16, toks)
+        e.enable_drafting(toks)
+        e.set_stopping((), [2, 30, 30])
+        for _ in range(3):
+            e.step()
+    a.set_penalties(1.3, 0.2, 0.2)
+    assert a.finished.tolist() == twin.finished.tolist() == [2, 0, 0]
+    keep = STATE + ("finished", "limit_lens")
+    before = {k: getattr(a, k)[1:].clone() for k in keep}
+    slots = [E.row_slots(a, r, P + 3) for r in (1, 2)]
+    real, calls = penalties.penalize_rows, []
+    monkeypatch.setattr(penalties, "penalize_rows", lambda *args, **kw: (calls.append(1), real(*args, **kw))[1])
+    for e in (a, twin):
+        e.admit([0], [prompt], max_new_tokens=10, chunk=4)
+    torch.cuda.synchronize()
+    assert not calls, "the admission head penalised"
+    assert int(a.tokens[0]) == int(twin.tokens[0]) and a.lengths.tolist() == [n + 1, P + 4, P + 4]
+    assert torch.equal(a.hidden[0].view(torch.int16), twin.hidden[0].view(torch.int16)), "row 0: hidden"
+    for i, (x, y) in enumerate(zip(E.row_slots(a, 0, n), E.row_slots(twin, 0, n))):
+        assert torch.equal(x, y), f"row 0: slots differ (piece {i})"
+    for k in keep:
+        assert torch.equal(getattr(a, k)[1:], before[k]), f"rows 1, 2: {k} changed"
+    for r, old in zip((1, 2), slots):
+        assert all(torch.equal(x, y) for x, y in zip(E.row_slots(a, r, P + 3), old)), f"row {r}: slots changed"
+    a.step()
+    assert len(calls) == 1                                                    # (the penalties ARE on: the step's head penalises)
     a.check()

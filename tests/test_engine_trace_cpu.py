@@ -303,19 +303,73 @@ def _generate(D, rec):
     captures(0, 1, parents=[-1, 0, 1], sampled=True)
 
 
-def _lora(D, rec):
-    """The `lora_rows` calls of a prefill, a step and a device-walk verification, at the Python seam."""
+def _lora_seam(D, rec):
+    """Record the `lora_rows` calls at the Python seam."""
     def lora_rows(out, x, x_scale, A, B, scaling, seq_adapter, rows_per_seq, seg_ends, workspace=None):
         ranges = rec._ranges()
         rec.lines.append("lora_rows " + " ".join(rec.pointer(t.data_ptr(), ranges) for t in (out, x, workspace)) + f" {rows_per_seq}")
 
     rec.monkeypatch.setattr(D.loramod, "lora_rows", lora_rows)
+
+
+def _lora(D, rec):
+    """The `lora_rows` calls of a prefill, a step and a device-walk verification, at the Python seam."""
+    _lora_seam(D, rec)
     eng = _engine(D, rec)
     eng.enable_lora(2, 8)
     eng.set_lora([0, -1])
     eng.prefill(5)
     eng.step()
     eng.verify_tree(torch.zeros((2, len(PAR)), dtype=torch.int64), PAR, device_walk=True)
+
+
+def _pool_stand_ins(rec):
+    """The page entries on the host: the stand-ins of tests/test_page_pool_contracts.py under the recorder, `paging` on the host seams."""
+    import qserve_amd.backend._util as U
+    import test_page_pool_contracts as C
+    from qserve_amd import paging
+    from qserve_amd._lib import SIGNATURES, lib
+    for attr in ("stream", "expect", "guard"):
+        rec.monkeypatch.setattr(paging, attr, getattr(U, attr))
+    for symbol, fn in (("qs_pages_reserve", C._fake_reserve), ("qs_pages_release", C._fake_release)):
+        rec.monkeypatch.setattr(lib, symbol, rec.wrap(symbol, fn, SIGNATURES[symbol][1]))
+
+
+def _admit_prompts():
+    g = torch.Generator().manual_seed(4)
+    return [torch.randint(0, 512, (n,), generator=g) for n in (3, 9)]
+
+
+def _admit(D, rec, featured=False):
+    """One ragged admit into rows [2, 0] of an empty batch of three: prompts of 3 and 9 tokens in passes of 4 - three passes, the short
+    sequence leaves after the first.  `featured`: under a page pool with sampling, log-probabilities, a constraint, penalties and
+    stopping all on - the admission head does not penalise -, and one step() behind it."""
+    if featured:
+        _pool_stand_ins(rec)
+    eng = _engine(D, rec, batch=3, prompt_len=9, max_new=4, page_pool=5 if featured else None)
+    eng.enable_drafting(None, max_ngram=3, min_match=1, pad_token=7)
+    if featured:
+        eng.set_sampling(0.8, top_k=5, top_p=0.9, seed=11)
+        eng.set_logprobs(top=3)
+        eng.set_constraint(_dfa(), [0, -1, 1])
+        eng.set_penalties(1.2, 0.1, 0.1)
+    eng.set_stopping([3], 0)
+    at = len(rec.lines)
+    eng.admit([2, 0], _admit_prompts(), max_new_tokens=[2, 3], text_start=[2, 9], chunk=4, **(dict(start_states=[1, 0]) if featured else {}))
+    assert not any(line.startswith("penalize_rows") for line in rec.lines[at:])
+    if featured:
+        eng.step()
+        assert any(line.startswith("penalize_rows") for line in rec.lines[at:])
+
+
+def _admit_lora(D, rec):
+    """The `lora_rows` calls of a ragged admit (9 and 3 tokens in passes of 4) under per-sequence adapters: one id per token."""
+    _lora_seam(D, rec)
+    eng = _engine(D, rec, batch=3, prompt_len=9, max_new=4)
+    eng.enable_lora(2, 8)
+    eng.enable_drafting(None)
+    eng.set_lora([0, 1, -1])
+    eng.admit([1, 0], _admit_prompts()[::-1], chunk=4)
 
 
 SCENARIOS = {
@@ -339,6 +393,9 @@ SCENARIOS = {
     "stopping_logprobs_constraint_sampled_penalised": lambda D, rec: _featured(D, rec, True, True, True, sampled=True),
     "generate_recaptures": _generate,
     "lora_prefill_step_verify": _lora,
+    "admit_ragged": _admit,
+    "admit_pooled_featured": lambda D, rec: _admit(D, rec, featured=True),
+    "admit_lora": _admit_lora,
 }
 
 
