@@ -1,4 +1,9 @@
-"""Seeded synthetic inputs for the hot path.  TEST INFRASTRUCTURE (see oracle/__init__.py)."""
+"""Seeded synthetic inputs for the hot path.  TEST INFRASTRUCTURE (see oracle/__init__.py).
+
+The GEMM problems here are uniform random: the activations never contain -128, and with zero-mean operands |acc| stays near
+sqrt(K) * 340 (about 4e4 at the project's K), three orders of magnitude below 2^24 - where integer and fp32 combination of K slices,
+and every way of rounding (float)acc, give the same number.  The complement is tests/_gemm_extreme_cases.py: accumulators of 2^24 and
+beyond that fp32 cannot hold, -128 on both operands, K slices that are large and cancel, a_ssums = +-inf and w_sz = 0."""
 import numpy as np
 
 from . import w4a8
@@ -6,7 +11,8 @@ from . import w4a8
 
 def per_channel_problem(M, N, K, seed=0):
     """A ~ U{-127..127}; Q ~ U{0..15}; z ~ U{0..15}; s1 ~ U(0.002, 0.02); ascales ~ U(0.005, 0.05);
-    a_ssums = half(ascale * sum_k A) (consistent with a real quantiser)."""
+    a_ssums = half(ascale * sum_k A) (consistent with a real quantiser).  No -128 in A, |acc| far below 2^24, every value
+    finite: the extreme cases are tests/_gemm_extreme_cases.py."""
     r = np.random.default_rng(seed)
     A = r.integers(-127, 128, (M, K), dtype=np.int8)
     q = r.integers(0, 16, (N, K), dtype=np.uint8)
@@ -20,7 +26,8 @@ def per_channel_problem(M, N, K, seed=0):
 
 def per_group_problem(M, N, K, seed=0, G=128, valid=True):
     """QoQ-style two-level weights inside the protective range (q*s2 <= 255, (q-z)*s2 in [-128,127]).
-    valid=False draws s2 up to 40 so that byte products overflow (exercises the wrap/carry semantics)."""
+    valid=False draws s2 up to 40 so that byte products overflow (exercises the wrap/carry semantics).  No -128 in A, the weight
+    byte -128 only by chance (valid=False), |acc| far below 2^24: the extreme cases are tests/_gemm_extreme_cases.py."""
     r = np.random.default_rng(seed)
     A = r.integers(-127, 128, (M, K), dtype=np.int8)
     ng = K // G

@@ -9,7 +9,8 @@ It issues exactly the op sequence of the reference's model code for `is_prompt=F
 
 With `fuse_pairs=True` (default) the adjacent pairs (attention, quant of its output), (residual add, layer norm) and
 (gate_up GEMM, silu_and_mul) are issued as one launch each (qserve_amd/fused.py) - same arithmetic, same intermediate fp16 roundings, bit-identical tensors
-(tests/test_fused_gpu.py, tests/test_decode_gpu.py); `fuse_pairs=False` issues the reference's ops one by one.
+(tests/test_fused_gpu.py::test_decode_step_fused_pairs_equals_op_by_op; against the oracle's engine:
+tests/test_loader.py::test_device_engine_matches_oracle_engine); `fuse_pairs=False` issues the reference's ops one by one.
 
 Weights are synthetic (random packed nibbles / scales of the right shapes, distinct per layer so nothing is
 served from cache); the KV cache is filled by the prefill writer.  Tensor parallelism: rank r owns

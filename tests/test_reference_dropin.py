@@ -12,7 +12,9 @@ composition of the oracle functions written from the model's mathematics (no shi
 arithmetic, so they must agree BIT FOR BIT (hidden states, logits, every byte of the KV pools).
 
 Skipped where /root/reference is absent (the GPU box): tests/test_callsites.py then still binds every recorded call site
-against the mirror's signatures, and tests/test_decode_gpu.py runs the same op sequence on the device.
+against the mirror's signatures, and the same op sequence runs on the device in
+tests/test_loader.py::test_device_engine_matches_oracle_engine (against the oracle's engine) and
+tests/test_fused_gpu.py::test_decode_step_fused_pairs_equals_op_by_op (fused pairs against the ops one by one).
 """
 import os
 import sys
