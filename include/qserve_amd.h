@@ -1020,6 +1020,52 @@ int qs_pages_release(int32_t* free_list, int32_t* count, int32_t* page_ids, int3
                      const int64_t* layer_tables, const int64_t* layer_bases, const int32_t* rows_mask, int batch, int max_blocks,
                      int num_layers, int num_pages, int64_t page_bytes, qs_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------------------------
+ * Reference counts over the page pool: a page may have more than one HOLDER, so that rows can share the whole pages of a common
+ * prefix (qserve_amd/prefix.py).  A holder is a (row, column) of page_ids that names the page, or the prefix cache (at most one hold
+ * per page).  Two more state tensors, filled in place: refs int32 [N]: the holders of page id - 0 means free, i.e. on the free stack
+ * -; scratch int32 [2 * N]: all zero between launches (every launch leaves it as it found it).  A pool either runs the three entries
+ * below and never qs_pages_reserve / qs_pages_release, or the other way round.  One launch of ONE workgroup each, capturable.
+ *
+ * qs_pages_reserve_refs.  The rule of qs_pages_reserve, and refs[id] = 1 for every popped id; a popped id with refs[id] != 0 is a
+ * broken invariant.  The same kernel (qs_pages_reserve runs it without refs).
+ *
+ * qs_pages_hold.  take int32 [batch]; src int32 [batch, max_blocks]; hold_ids int32 [num_hold] (null when num_hold == 0).  For every
+ * row b with take[b] > 0: page_ids[b, j] = src[b, j] for 0 <= j < take[b], entry (b, kv, j) of the K and V tables of all layers
+ * becomes that page's address, owned[b] = take[b].  refs[id] += the number of (b, j), j < take[b], with src[b, j] == id, + the number
+ * of k with hold_ids[k] == id.  The same page may be mapped into several rows in one launch.  Broken invariants: take[b] outside
+ * 0 .. max_blocks; take[b] > 0 where owned[b] != 0; a named id (src[b, j] with j < take[b], hold_ids[k]) outside 0 .. N - 1 or with
+ * refs[id] == 0 (a free page cannot be shared); an id twice in hold_ids.
+ *
+ * qs_pages_unhold.  rows_mask int32 [batch] (non-zero: MASKED); drop_ids int32 [num_drop] (null when num_drop == 0).  H, the list of
+ * holds given up, is page_ids[b, j] for the masked rows b in row order, 0 <= j < owned[b] in logical page order, followed by
+ * drop_ids in order; g(id) is the number of positions of H that hold id.  refs[id] -= g(id); a page whose count reaches 0 is FREED.
+ * With f_0 < f_1 < .. the positions of H that are the FIRST occurrence of a freed page: free_list[count + i] = H[f_i], and count
+ * rises by their number.  The masked rows end as after qs_pages_release: page_ids[b, j] = -1, the table entries the sink's address,
+ * owned[b] = starved[b] = 0.  Broken invariants: count outside 0 .. N; an owned[b] outside 0 .. max_blocks; an id of H outside
+ * 0 .. N - 1; g(id) > refs[id]; count rising above N.
+ *
+ * A broken invariant: error[0] = 1 and the launch changes NOTHING else (the scratch is zero again).  The state after a launch is a
+ * function of the state before it, the order of the free stack included: the only atomics are integer add and max on refs and the
+ * scratch, whose result no arrival order changes.  Vector stores only; no address is formed from an unchecked or unclamped index.
+ *
+ * QS_EINVAL before any device call: what qs_pages_reserve / qs_pages_release refuse (take, src and rows_mask may not be null); refs
+ * null; scratch null (hold, unhold); num_hold / num_drop outside 0 .. num_pages; a null id list with a positive number; an int32
+ * array not 4-byte aligned.  batch == 0 (and, for hold and unhold, no ids): QS_OK, no launch.
+ * ---------------------------------------------------------------------------------------------------------- */
+int qs_pages_reserve_refs(int32_t* free_list, int32_t* count, int32_t* page_ids, int32_t* owned, int32_t* starved, int32_t* error,
+                          const int64_t* layer_tables, const int64_t* layer_bases, int32_t* refs, const int32_t* lengths,
+                          const int32_t* extra_rows, int32_t* finished, int batch, int max_blocks, int num_layers, int num_pages,
+                          int64_t page_bytes, int extra, qs_stream_t stream);
+int qs_pages_hold(int32_t* free_list, int32_t* count, int32_t* page_ids, int32_t* owned, int32_t* starved, int32_t* error,
+                  const int64_t* layer_tables, const int64_t* layer_bases, int32_t* refs, int32_t* scratch, const int32_t* take,
+                  const int32_t* src, const int32_t* hold_ids, int num_hold, int batch, int max_blocks, int num_layers, int num_pages,
+                  int64_t page_bytes, qs_stream_t stream);
+int qs_pages_unhold(int32_t* free_list, int32_t* count, int32_t* page_ids, int32_t* owned, int32_t* starved, int32_t* error,
+                    const int64_t* layer_tables, const int64_t* layer_bases, int32_t* refs, int32_t* scratch, const int32_t* rows_mask,
+                    const int32_t* drop_ids, int num_drop, int batch, int max_blocks, int num_layers, int num_pages, int64_t page_bytes,
+                    qs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,7 @@
 // page_pool.hip -- the device-side page allocator of the paged KV cache, for MI355X (gfx950): a free stack of page indices that is
 // common to the K and V pools of every layer, and the two launches that move pages between the stack and the rows of the per-layer
 // pointer tables without the host knowing a length.  DESIGN.md 10 ("Page pool and admission"); the rules are the header comment of
-// qs_pages_reserve / qs_pages_release in include/qserve_amd.h, in exact integers.  This file holds TWO kernels.
+// qs_pages_reserve / qs_pages_release in include/qserve_amd.h, in exact integers.  This file holds FOUR kernels.
 //
 //   pages_reserve_kernel   ONE workgroup of POOL_THREADS threads; rows are walked in chunks of POOL_THREADS (batch <= MAX_ROWS).
 //                1. per row: owned (checked, clamped), need, grow -> LDS;
@@ -14,7 +14,15 @@
 //                6. per row: owned += grow, or starved / finished; thread 0: count -= popped.
 //   pages_release_kernel   the same shape: prefix of `owned` over the masked rows, ids checked, then the strided loop pushes the ids,
 //                clears page_ids and points the table entries at the sink; owned = starved = 0; count += the total.
-// No atomics, no cross-workgroup traffic, vector stores only.  Every index is clamped before an address is formed from it.
+//   pages_hold_kernel      (reference counts, qs_pages_hold) rows map pages that already have a holder: the prefix of `take` in row order,
+//                every named id checked (range, refs != 0, hold_ids distinct through a mark per id in `scratch`), then the strided loop
+//                writes page_ids and the tables and adds 1 to refs per naming entry; owned = take.
+//   pages_unhold_kernel    (qs_pages_unhold) the list H of holds given up = the masked rows' pages, then drop_ids: per id its occurrences
+//                (atomic add) and its first position in H (atomic max of len(H) - p) in `scratch`; the pages whose count reaches 0 are
+//                pushed in the order of their first occurrence - a chunked scan over H of "first occurrence of a freed page" -, then
+//                refs -= g, the rows end as after a release, and the scratch is zero again.
+// The two uncounted entries use no atomics; the counted ones only integer add / max, whose result no arrival order changes.  No
+// cross-workgroup traffic, vector stores only.  Every index is clamped before an address is formed from it.
 #include "common.h"
 
 namespace {
@@ -36,7 +44,13 @@ struct PoolArgs {
     const int* lengths;                              // [batch]            (reserve)
     const int* extra_rows;                           // [batch] or null    (reserve)
     int* finished;                                   // [batch] or null    (reserve)
-    const int* rows_mask;                            // [batch]            (release)
+    const int* rows_mask;                            // [batch]            (release, unhold)
+    int* refs;                                       // [N] or null        (holders per page; null: the uncounted reserve)
+    int* scratch;                                    // [2 * N]            (hold, unhold: zero on entry, zero again on exit)
+    const int* take;                                 // [batch]            (hold)
+    const int* src;                                  // [batch, mb]        (hold)
+    const int* extra_ids;                            // [num_extra] or null (hold: hold_ids; unhold: drop_ids)
+    int num_extra;
     long long page_bytes;
     int batch, mb, L, N, extra;
 };
@@ -134,6 +148,7 @@ __global__ __launch_bounds__(POOL_THREADS) void pages_reserve_kernel(const PoolA
     for (int s = tid; s < popped; s += POOL_THREADS) {
         const int id = a.free_list[clamp_index((long long)cnt - 1 - s, a.N)];
         bad = bad || id < 0 || id >= a.N;
+        if (a.refs) bad = bad || a.refs[clamp_index(id, a.N)] != 0;         // (counted: a free page has no holder)
     }
     if (block_any(sh, bad)) {                                               // (workgroup-uniform)
         if (tid == 0) a.error[0] = 1;
@@ -147,7 +162,10 @@ __global__ __launch_bounds__(POOL_THREADS) void pages_reserve_kernel(const PoolA
         const int j = s - (sh.S[b] - sh.grow[b]);
         const int col = clamp_index((long long)sh.own[b] + j, a.mb);
         const int id = a.free_list[clamp_index((long long)cnt - 1 - s, a.N)];
-        if (w == 0) a.page_ids[(size_t)b * a.mb + col] = id;
+        if (w == 0) {
+            a.page_ids[(size_t)b * a.mb + col] = id;
+            if (a.refs) a.refs[id] = 1;                                     // (counted: the row is the page's one holder)
+        }
         long long* table = reinterpret_cast<long long*>(a.layer_tables[w >> 1]);
         table[((size_t)b * 2 + (w & 1)) * a.mb + col] = a.layer_bases[w] + (long long)id * a.page_bytes;
     }
@@ -210,7 +228,195 @@ __global__ __launch_bounds__(POOL_THREADS) void pages_release_kernel(const PoolA
     if (tid == 0) a.count[0] = cnt + total;
 }
 
-// what both entries ask for -> QS_OK, or QS_EINVAL with the message set
+// sum of v over the workgroup; every thread calls it, every thread gets the result
+__device__ __forceinline__ int block_sum(PoolShared& sh, int v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    if ((threadIdx.x & 63) == 0) sh.wave[threadIdx.x >> 6] = v;
+    __syncthreads();
+    v = 0;
+#pragma unroll
+    for (int w = 0; w < POOL_WAVES; ++w) v += sh.wave[w];
+    __syncthreads();
+    return v;
+}
+
+// a scratch word that another thread of the workgroup changed by an atomic: read past the vector cache
+__device__ __forceinline__ int scratch_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__global__ __launch_bounds__(POOL_THREADS) void pages_hold_kernel(const PoolArgs a) {
+    __shared__ PoolShared sh;
+    const int tid = threadIdx.x;
+    bool bad = false;
+    for (int b = tid; b < a.batch; b += POOL_THREADS) {
+        const int t = a.take[b];
+        bad = bad || t < 0 || t > a.mb || (t > 0 && a.owned[b] != 0);
+        const int tc = t < 0 ? 0 : t > a.mb ? a.mb : t;
+        sh.grow[b] = tc;
+        for (int j = 0; j < tc; ++j) {
+            const int id = a.src[(size_t)b * a.mb + j];
+            bad = bad || id < 0 || id >= a.N || a.refs[clamp_index(id, a.N)] == 0;
+        }
+    }
+    __syncthreads();
+    const int total = scan_rows(sh, a.batch);
+    for (int k = tid; k < a.num_extra; k += POOL_THREADS) {
+        const int id = a.extra_ids[k];
+        const bool in = id >= 0 && id < a.N;
+        bad = bad || !in || a.refs[clamp_index(id, a.N)] == 0;
+        if (in) bad = bad || atomicAdd(&a.scratch[id], 1) != 0;             // (twice in hold_ids: whoever comes second sees it)
+    }
+    const bool any = block_any(sh, bad);                                    // (a barrier: every mark is set)
+    for (int k = tid; k < a.num_extra; k += POOL_THREADS) {
+        const int id = a.extra_ids[k];
+        if (id >= 0 && id < a.N) a.scratch[id] = 0;
+    }
+    if (any) {                                                              // (workgroup-uniform)
+        if (tid == 0) a.error[0] = 1;
+        return;
+    }
+    const int lk = 2 * a.L;
+    const long long items = (long long)total * lk;
+    for (long long it = tid; it < items; it += POOL_THREADS) {
+        const int s = (int)(it / lk), w = (int)(it - (long long)s * lk);
+        const int b = row_of_slot(sh, a.batch, s);
+        const int col = clamp_index((long long)s - (sh.S[b] - sh.grow[b]), a.mb);
+        const int id = clamp_index(a.src[(size_t)b * a.mb + col], a.N);
+        if (w == 0) {
+            a.page_ids[(size_t)b * a.mb + col] = id;
+            atomicAdd(&a.refs[id], 1);
+        }
+        long long* table = reinterpret_cast<long long*>(a.layer_tables[w >> 1]);
+        table[((size_t)b * 2 + (w & 1)) * a.mb + col] = a.layer_bases[w] + (long long)id * a.page_bytes;
+    }
+    for (int k = tid; k < a.num_extra; k += POOL_THREADS) atomicAdd(&a.refs[clamp_index(a.extra_ids[k], a.N)], 1);
+    for (int b = tid; b < a.batch; b += POOL_THREADS) {
+        if (sh.grow[b] > 0) a.owned[b] = sh.grow[b];
+    }
+}
+
+// the id at position p of H (the masked rows' pages, then drop_ids), clamped; total = the rows' part
+__device__ __forceinline__ int unhold_id(const PoolArgs& a, const PoolShared& sh, int total, int p) {
+    if (p >= total) return clamp_index(a.extra_ids[p - total], a.N);
+    const int b = row_of_slot(sh, a.batch, p);
+    const int col = clamp_index((long long)p - (sh.S[b] - sh.grow[b]), a.mb);
+    return clamp_index(a.page_ids[(size_t)b * a.mb + col], a.N);
+}
+
+__global__ __launch_bounds__(POOL_THREADS) void pages_unhold_kernel(const PoolArgs a) {
+    __shared__ PoolShared sh;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int* occ = a.scratch;                                                   // [N]: g(id), the occurrences of id in H
+    int* first = a.scratch + a.N;                                           // [N]: len(H) - the first position of id in H
+    const int count = a.count[0];
+    bool bad = count < 0 || count > a.N;
+    const int cnt = count < 0 ? 0 : count > a.N ? a.N : count;
+    for (int b = tid; b < a.batch; b += POOL_THREADS) {
+        const int own = a.owned[b];
+        bad = bad || own < 0 || own > a.mb;
+        const int ownc = own < 0 ? 0 : own > a.mb ? a.mb : own;
+        const bool masked = a.rows_mask[b] != 0;
+        sh.grow[b] = masked ? ownc : 0;
+        sh.own[b] = masked ? 1 : 0;
+        if (masked) {
+            for (int j = 0; j < ownc; ++j) {
+                const int id = a.page_ids[(size_t)b * a.mb + j];
+                bad = bad || id < 0 || id >= a.N;
+            }
+        }
+    }
+    for (int k = tid; k < a.num_extra; k += POOL_THREADS) {
+        const int id = a.extra_ids[k];
+        bad = bad || id < 0 || id >= a.N;
+    }
+    __syncthreads();
+    const int total = scan_rows(sh, a.batch);
+    if (block_any(sh, bad)) {                                               // (workgroup-uniform; the scratch is untouched)
+        if (tid == 0) a.error[0] = 1;
+        return;
+    }
+    const int H = total + a.num_extra;
+    // g(id) and the first occurrence of every id of H
+    for (int p = tid; p < H; p += POOL_THREADS) {
+        const int id = unhold_id(a, sh, total, p);
+        atomicAdd(&occ[id], 1);
+        atomicMax(&first[id], H - p);
+    }
+    __syncthreads();
+    // more holds given up than there are; the pages that become free, counted
+    int frees = 0;
+    for (int p = tid; p < H; p += POOL_THREADS) {
+        const int id = unhold_id(a, sh, total, p);
+        const int g = scratch_load(&occ[id]), r = a.refs[id];
+        bad = bad || g > r;
+        frees += g == r && scratch_load(&first[id]) == H - p ? 1 : 0;
+    }
+    const int freed = block_sum(sh, frees);
+    bad = bad || (long long)cnt + freed > a.N;
+    if (block_any(sh, bad)) {                                               // (workgroup-uniform)
+        for (int p = tid; p < H; p += POOL_THREADS) {
+            const int id = unhold_id(a, sh, total, p);
+            occ[id] = 0, first[id] = 0;
+        }
+        if (tid == 0) a.error[0] = 1;
+        return;
+    }
+    // the freed pages onto the stack, in the order of their first occurrence in H: a scan over H in chunks
+    int carry = 0;
+    for (int p0 = 0; p0 < H; p0 += POOL_THREADS) {                          // (workgroup-uniform)
+        const int p = p0 + tid;
+        int id = 0, f = 0;
+        if (p < H) {
+            id = unhold_id(a, sh, total, p);
+            f = scratch_load(&occ[id]) == a.refs[id] && scratch_load(&first[id]) == H - p ? 1 : 0;
+        }
+        int x = f;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int t = __shfl_up(x, o, 64);
+            if (lane >= o) x += t;
+        }
+        if (lane == 63) sh.wave[wave] = x;
+        __syncthreads();
+        int before = carry, all = 0;
+#pragma unroll
+        for (int w = 0; w < POOL_WAVES; ++w) {
+            const int t = sh.wave[w];
+            before += w < wave ? t : 0;
+            all += t;
+        }
+        if (f) a.free_list[clamp_index((long long)cnt + before + x - 1, a.N)] = id;
+        carry += all;
+        __syncthreads();
+    }
+    // refs -= g, by the thread of the first occurrence (the others only read occ / first: barriers on both sides)
+    for (int p = tid; p < H; p += POOL_THREADS) {
+        const int id = unhold_id(a, sh, total, p);
+        if (scratch_load(&first[id]) == H - p) a.refs[id] -= scratch_load(&occ[id]);
+    }
+    __syncthreads();
+    for (int p = tid; p < H; p += POOL_THREADS) {
+        const int id = unhold_id(a, sh, total, p);
+        occ[id] = 0, first[id] = 0;
+    }
+    __syncthreads();                                                        // (unhold_id reads page_ids: cleared only now)
+    const int lk = 2 * a.L;
+    const long long items = (long long)total * lk;
+    for (long long it = tid; it < items; it += POOL_THREADS) {
+        const int s = (int)(it / lk), w = (int)(it - (long long)s * lk);
+        const int b = row_of_slot(sh, a.batch, s);
+        const int col = clamp_index((long long)s - (sh.S[b] - sh.grow[b]), a.mb);
+        if (w == 0) a.page_ids[(size_t)b * a.mb + col] = -1;
+        long long* table = reinterpret_cast<long long*>(a.layer_tables[w >> 1]);
+        table[((size_t)b * 2 + (w & 1)) * a.mb + col] = a.layer_bases[w] + (long long)a.N * a.page_bytes;   // the sink
+    }
+    for (int b = tid; b < a.batch; b += POOL_THREADS) {
+        if (sh.own[b]) a.owned[b] = 0, a.starved[b] = 0;
+    }
+    if (tid == 0) a.count[0] = cnt + freed;
+}
+
+// what every entry asks for -> QS_OK, or QS_EINVAL with the message set
 int pool_arguments(const char* what, const int32_t* free_list, const int32_t* count, const int32_t* page_ids, const int32_t* owned,
                    const int32_t* starved, const int32_t* error, const int64_t* layer_tables, const int64_t* layer_bases, const void* rows,
                    const void* opt1, const void* opt2, int batch, int max_blocks, int num_layers, int num_pages, int64_t page_bytes) {
@@ -269,4 +475,64 @@ extern "C" int qs_pages_release(int32_t* free_list, int32_t* count, int32_t* pag
     a.rows_mask = rows_mask;
     hipLaunchKernelGGL(pages_release_kernel, dim3(1), dim3(POOL_THREADS), 0, (hipStream_t)stream, a);
     return qs_launch_status("pages_release");
+}
+
+// what the counted entries ask for on top of pool_arguments
+static int refs_arguments(const char* what, const int32_t* refs, const int32_t* scratch, bool with_scratch, const int32_t* ids, int num_ids,
+                          int num_pages) {
+    QS_REQUIRE(refs && (scratch || !with_scratch), "%s: null pointer (refs%s)", what, with_scratch ? ", scratch" : "");
+    QS_REQUIRE(num_ids >= 0 && num_ids <= num_pages, "%s: %d ids (0 .. num_pages = %d)", what, num_ids, num_pages);
+    QS_REQUIRE(ids || num_ids == 0, "%s: null id list of %d entries", what, num_ids);
+    QS_REQUIRE((((uintptr_t)refs | (uintptr_t)scratch | (uintptr_t)ids) & 3) == 0, "%s: an int32 array is not 4-byte aligned", what);
+    return QS_OK;
+}
+
+extern "C" int qs_pages_reserve_refs(int32_t* free_list, int32_t* count, int32_t* page_ids, int32_t* owned, int32_t* starved, int32_t* error,
+                                     const int64_t* layer_tables, const int64_t* layer_bases, int32_t* refs, const int32_t* lengths,
+                                     const int32_t* extra_rows, int32_t* finished, int batch, int max_blocks, int num_layers, int num_pages,
+                                     int64_t page_bytes, int extra, qs_stream_t stream) {
+    int rc = pool_arguments("pages_reserve_refs", free_list, count, page_ids, owned, starved, error, layer_tables, layer_bases, lengths,
+                            extra_rows, finished, batch, max_blocks, num_layers, num_pages, page_bytes);
+    if (rc != QS_OK) return rc;
+    if ((rc = refs_arguments("pages_reserve_refs", refs, nullptr, false, nullptr, 0, num_pages)) != QS_OK) return rc;
+    QS_REQUIRE(extra >= 0, "pages_reserve_refs: extra=%d (>= 0: the tokens the round is about to write)", extra);
+    if (batch == 0) return QS_OK;
+    PoolArgs a = pool_args(free_list, count, page_ids, owned, starved, error, layer_tables, layer_bases, batch, max_blocks, num_layers,
+                           num_pages, page_bytes);
+    a.lengths = lengths, a.extra_rows = extra_rows, a.finished = finished, a.extra = extra, a.refs = refs;
+    hipLaunchKernelGGL(pages_reserve_kernel, dim3(1), dim3(POOL_THREADS), 0, (hipStream_t)stream, a);
+    return qs_launch_status("pages_reserve_refs");
+}
+
+extern "C" int qs_pages_hold(int32_t* free_list, int32_t* count, int32_t* page_ids, int32_t* owned, int32_t* starved, int32_t* error,
+                             const int64_t* layer_tables, const int64_t* layer_bases, int32_t* refs, int32_t* scratch, const int32_t* take,
+                             const int32_t* src, const int32_t* hold_ids, int num_hold, int batch, int max_blocks, int num_layers,
+                             int num_pages, int64_t page_bytes, qs_stream_t stream) {
+    int rc = pool_arguments("pages_hold", free_list, count, page_ids, owned, starved, error, layer_tables, layer_bases, take, src, nullptr,
+                            batch, max_blocks, num_layers, num_pages, page_bytes);
+    if (rc != QS_OK) return rc;
+    QS_REQUIRE(src, "pages_hold: null pointer (src)");
+    if ((rc = refs_arguments("pages_hold", refs, scratch, true, hold_ids, num_hold, num_pages)) != QS_OK) return rc;
+    if (batch == 0 && num_hold == 0) return QS_OK;
+    PoolArgs a = pool_args(free_list, count, page_ids, owned, starved, error, layer_tables, layer_bases, batch, max_blocks, num_layers,
+                           num_pages, page_bytes);
+    a.refs = refs, a.scratch = scratch, a.take = take, a.src = src, a.extra_ids = hold_ids, a.num_extra = num_hold;
+    hipLaunchKernelGGL(pages_hold_kernel, dim3(1), dim3(POOL_THREADS), 0, (hipStream_t)stream, a);
+    return qs_launch_status("pages_hold");
+}
+
+extern "C" int qs_pages_unhold(int32_t* free_list, int32_t* count, int32_t* page_ids, int32_t* owned, int32_t* starved, int32_t* error,
+                               const int64_t* layer_tables, const int64_t* layer_bases, int32_t* refs, int32_t* scratch,
+                               const int32_t* rows_mask, const int32_t* drop_ids, int num_drop, int batch, int max_blocks, int num_layers,
+                               int num_pages, int64_t page_bytes, qs_stream_t stream) {
+    int rc = pool_arguments("pages_unhold", free_list, count, page_ids, owned, starved, error, layer_tables, layer_bases, rows_mask, nullptr,
+                            nullptr, batch, max_blocks, num_layers, num_pages, page_bytes);
+    if (rc != QS_OK) return rc;
+    if ((rc = refs_arguments("pages_unhold", refs, scratch, true, drop_ids, num_drop, num_pages)) != QS_OK) return rc;
+    if (batch == 0 && num_drop == 0) return QS_OK;
+    PoolArgs a = pool_args(free_list, count, page_ids, owned, starved, error, layer_tables, layer_bases, batch, max_blocks, num_layers,
+                           num_pages, page_bytes);
+    a.refs = refs, a.scratch = scratch, a.rows_mask = rows_mask, a.extra_ids = drop_ids, a.num_extra = num_drop;
+    hipLaunchKernelGGL(pages_unhold_kernel, dim3(1), dim3(POOL_THREADS), 0, (hipStream_t)stream, a);
+    return qs_launch_status("pages_unhold");
 }

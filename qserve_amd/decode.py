@@ -37,6 +37,7 @@ from . import lora as loramod
 from . import moe as moemod
 from . import paging as pagingmod
 from . import penalties as penaltiesmod
+from . import prefix as prefixmod
 from . import rope as ropemod
 from . import sampling as samplingmod
 from . import serving as servingmod
@@ -170,7 +171,7 @@ class W4A8Linear:
 class DecodeEngine:
     def __init__(self, cfg, batch, prompt_len, max_new, group_size=-1, int4_kv=True, device="cuda:0", seed=0,
                  tp_rank=0, tp_world=1, with_lm_head=True, fuse_pairs=True, weights=None, vocab_parallel=True, planes=None,
-                 direct_allreduce=None, page_pool=None):
+                 direct_allreduce=None, page_pool=None, prefix_cache=False):
         """weights: None = synthetic random-quantised tensors of the right shapes; otherwise this rank's tensors as
         qserve_amd.loader.load_llama_w4a8 returns them (checkpoint path).  A config with `experts` and `experts_per_token`
         (MIXTRAL_8X7B, TINY_MOE) builds mixture-of-experts layers: a router `gate` fp16 [E, hid] and two `moe.MoELinear`s in place of
@@ -187,7 +188,13 @@ class DecodeEngine:
         What a frozen row guarantees under a pool is the bytes of its slots < lengths - 1: its rewrite of slot lengths - 1, and a frozen
         verification's parked nodes, may land in the sink - valid memory that only ever takes validly quantised K / V, so it stays
         finite.  Single GPU; prefill_shared refuses to run (aliased prefix pages would be released twice - the pool keeps no reference
-        counts)."""
+        counts).
+
+        `prefix_cache` (needs `page_pool`, one GPU): the pool counts the holders of every page (`paging.PagePool(refcounts=True)`: every
+        reserve and release of the engine goes through the counted entries) and `self.prefix`, a `prefix.PrefixCache`, remembers which
+        whole pages of 64 prompt tokens sit where: admit() maps the cached pages of a prompt's beginning into the row instead of
+        recomputing them, and enters what it computed; serve() keeps a preempted row's text in the cache.  Only pages that no writer
+        touches again are shared ("Prefix cache"), so there is no copy-on-write.  Off: everything launches what it did."""
         self.cfg, self.B, self.dev = cfg, batch, torch.device(device)
         # mixture of experts: (experts, experts per token), or None for a dense model - which launches exactly what it always did
         self.moe = (int(cfg["experts"]), int(cfg["experts_per_token"])) if cfg.get("experts") else None
@@ -271,6 +278,9 @@ class DecodeEngine:
         assert page_pool is None or (tp_world == 1 and int(page_pool) >= 1), \
             f"DecodeEngine: page_pool={page_pool} - a page pool has at least one page and runs on one GPU (its allocator is one launch " \
             "on one device; tensor parallelism under a pool is not built)"
+        assert not prefix_cache or (page_pool is not None and tp_world == 1), \
+            "DecodeEngine: prefix_cache=True shares pages of a page pool - give page_pool=N; it runs on one GPU (the allocator is one " \
+            "launch on one device; tensor parallelism under a pool is not built)"
         nblocks = batch * self.mb if page_pool is None else int(page_pool) + 1       # (+ 1: the sink)
         perm = torch.randperm(batch * self.mb, generator=torch.Generator().manual_seed(seed)).reshape(batch, self.mb)
         self.pools, self.tables = [], []
@@ -285,9 +295,12 @@ class DecodeEngine:
             self.tables.append(t.to(self.dev))
         # page_pool: the allocator over these tables and pools (every entry the sink until a reserve), and the all-ones rows that are
         # the lengths of a prompt's reserve and the mask of a release of every row
-        self.pager = self._all_rows = None
+        # prefix_cache: the host's record of the cached token chains, and per row the cached pages it holds (what `row_released` is told)
+        self.pager = self._all_rows = self.prefix = None
+        self._row_cached = {}
         if page_pool is not None:
-            self.pager = pagingmod.PagePool(self.tables, self.pools, self.page_bytes)
+            self.pager = pagingmod.PagePool(self.tables, self.pools, self.page_bytes, refcounts=bool(prefix_cache))
+            self.prefix = prefixmod.PrefixCache() if prefix_cache else None
             self._all_rows = torch.ones((batch,), dtype=torch.int32, device=self.dev)
         # ---- activation buffers (ActivationBuffer, input_metadata.py:71-109)
         B = batch
@@ -407,8 +420,28 @@ class DecodeEngine:
             assert self.stopping is None, \
                 "a prompt's pages are reserved without the stop rule (a refused row could not be told through `finished`, and its " \
                 "prompt would go to the sink) - set_stopping(None) first"
-            self.pager.release(self._all_rows)
+            self.release_rows(None)
             self.pager.reserve(self._all_rows, prompt_len)
+
+    def release_rows(self, rows, drop_ids=()):
+        """Give back the pages of the rows `rows` (indices; None: every row) - one launch.  Under a prefix cache the rows give up their
+        HOLDS, the cache is told which cached pages they held, and `drop_ids` are the cache's own holds to drop in the same launch."""
+        assert self.pager is not None, "release_rows: the engine has no page pool"
+        mask = self._all_rows if rows is None else self.pager.rows_mask(rows)
+        rows = list(range(self.B)) if rows is None else [int(r) for r in rows]
+        if self.prefix is not None:
+            for r in rows:
+                self.prefix.row_released(self._row_cached.pop(r, ()))
+        self.pager.release(mask, drop_ids)
+
+    def evict_prefixes(self, pages, keep=()):
+        """Evict up to `pages` cached pages that no row holds, least recently used leaves first (`prefix.PrefixCache.evict`; `keep`: ids
+        to spare), and drop the cache's holds of them in one launch: each goes back to the free stack.  -> the evicted ids."""
+        assert self.prefix is not None, "evict_prefixes: the engine has no prefix cache - DecodeEngine(page_pool=N, prefix_cache=True)"
+        ids = self.prefix.evict(int(pages), keep)
+        if ids:
+            self.pager.release(torch.zeros((self.B,), dtype=torch.int32, device=self.dev), ids)
+        return ids
 
     # ---- the sampling head (qserve_amd.sampling, csrc/sample_rows.hip) --------------------------------------------------------
     def set_sampling(self, temperature, top_k=0, top_p=1.0, seed=0):
@@ -722,19 +755,21 @@ class DecodeEngine:
                                  self._append_over(self.tables))
         self._prompt_head(last, prompt_len)
 
-    def _append_over(self, tables):
-        """The `attend` of a _prompt_pass that is `append.append` over the pass's sequences' rows of tables[li]."""
+    def _append_over(self, tables, past0=0):
+        """The `attend` of a _prompt_pass that is `append.append` over the pass's sequences' rows of tables[li]; `past0`: the largest
+        `base` of the pass's sequences (the hint is a bound of base + c0)."""
         from . import append as appendmod      # (looked up per call: `appendmod.append` is the seam tests wrap)
         # (max_past = c0, known on the host: a long past at a small batch is cut into page ranges - append_attention_split.hip)
         def attend(li, qkv, cu, past, n, c0, live):
             return appendmod.append(qkv, cu, past, tables[li] if live is None else tables[li][live], self.H, self.Hkv, self.size_per_token,
-                                    self.rope_base, self.int4, max_seqlen_q=n, max_past=c0)
+                                    self.rope_base, self.int4, max_seqlen_q=n, max_past=past0 + c0)
         return attend
 
     def _prompt_pass(self, tokens, lens, chunk, bufs, base, attend, lora_ids=None):
         """THE chunked prompt pass: the layer stack over R sequences of possibly different lengths, `tokens` [R, >= max(lens)] on the
         device (padded; sequence r is tokens[r, :lens[r]]) and `lens` a host list, in passes of `chunk` columns: pass c0 runs
-        tokens[r, c0 : c0 + chunk] of every sequence that has a token left - one with none is left out -, behind a past of base + c0,
+        tokens[r, c0 : c0 + chunk] of every sequence that has a token left - one with none is left out -, behind a past of base + c0
+        (`base`: an int, or one int per sequence - what already sits in its pages),
         with cu_seqlens from the pass's lengths.  attend(li, qkv, cu_seqlens, past_lens, n, c0, live) -> fp16 [T, H, 128]: the append
         attention of layer li over the pass's T rows; n: the longest sequence of the pass; `live`: the sequences in it, int64 indices
         on the device, or None when all are.  `bufs`: _prompt_buffers of at least R * chunk rows.  `lora_ids`: the adapter of every
@@ -749,7 +784,8 @@ class DecodeEngine:
             T, n = cu_h[-1], max(ns)
             h = torch.index_select(self.embed, 0, torch.cat([tokens[r, c0:c0 + m] for r, m in zip(live, ns)]))
             cu = torch.tensor(cu_h, dtype=torch.int32, device=dev)
-            past = torch.full((len(live),), base + c0, dtype=torch.int32, device=dev)
+            past = torch.full((len(live),), base + c0, dtype=torch.int32, device=dev) if isinstance(base, int) else \
+                torch.tensor([base[r] + c0 for r in live], dtype=torch.int32, device=dev)
             live_t = None if len(live) == R else torch.tensor(live, dtype=torch.int64, device=dev)
             ids = None if lora_ids is None else torch.repeat_interleave(     # the adapter of every token of this pass
                 lora_ids if live_t is None else torch.index_select(lora_ids, 0, live_t), torch.tensor(ns, dtype=torch.int64, device=dev), output_size=T)
@@ -1035,7 +1071,7 @@ class DecodeEngine:
             # no page owned - a set_stopping(stop, 0) behind it freezes every row at its limit: what admit() fills and serve() starts from
             prompt, P = None, 0
             if self.pager is not None:
-                self.pager.release(self._all_rows)
+                self.release_rows(None)
             self.lengths.fill_(1)
             self._len_bound, self._text_start = 1, 0
         else:
@@ -1449,8 +1485,17 @@ class DecodeEngine:
         resumed request generated earlier counts as generated), limit_lens = prompt_lens + `max_new_tokens` (an int or one per row;
         None: the history's capacity; needs set_stopping to have been called), finished = 0 followed by the root check of
         set_stopping while the stop rule is on.  Unlike the prefill entries it runs while stopping and penalties are on, and under
-        set_lora.  No capture is invalidated.  Every argument is checked before the first write.  Single GPU, with the lm_head."""
+        set_lora.  No capture is invalidated.  Every argument is checked before the first write.  Single GPU, with the lm_head.
+
+        Under a prefix cache (prefix_cache=True) the whole pages of a prompt's beginning that are cached, below its last token, are
+        mapped into the row by one hold launch between the release and the reserve, the passes run tokens[c_r:] at past c_r + c0 only,
+        and - behind one read-back of the rows' page ids - the floor(P_r / 64) whole pages the prompt filled are entered into the cache,
+        which takes its holds in one more launch.  Requests of ONE admit do not share what none of them found cached.  admit never
+        evicts (`evict_prefixes`).  Refused while set_lora is on."""
         self._single_gpu("admit")
+        assert self.prefix is None or not self._lora, \
+            "admit: the engine has a prefix cache and LoRA is on (set_lora) - K / V under an adapter differ from the base model's, and a " \
+            "slot can be reloaded under the same id, so its pages cannot be keyed by tokens alone; set_lora(None) before admitting"
         assert self.history is not None, "admit: enable_drafting first (enable_drafting(None) for an empty batch): it writes `history`"
         B, dev, cap = self.B, self.dev, self.max_len
         rows = [int(r) for r in rows]
@@ -1498,16 +1543,43 @@ class DecodeEngine:
             self.finished[rows_t] = 0
         if st is not None:
             self.fsm_state[rows_t] = torch.tensor(st, **i32)
-        # ---- pages: the rows give back what they own and take their prompts' (two launches)
+        # ---- pages: the rows give back what they own and take their prompts' (two launches).  Under a prefix cache the whole pages of
+        # a prompt's beginning that are cached - at most those below its last token, which is always recomputed: the head needs its
+        # hidden row - are mapped into the row by a hold between the two, and the reserve grows the row behind them.  What a request
+        # of THIS admit computes is entered at the end: two requests with the same new prefix in one admit do not share
+        cached = [[] for _ in rows]
         if self.pager is not None:
             extra = torch.zeros((B,), **i32)
             extra[rows_t] = P_t
-            self.pager.release(self.pager.rows_mask(rows))
+            if self.prefix is not None:
+                cached = [self.prefix.match(p.tolist(), limit=P - 1) for p, P in zip(pl, Ps)]
+            self.release_rows(rows)
+            if any(cached):
+                self.pager.hold({r: ids for r, ids in zip(rows, cached) if ids})
             self.pager.reserve(self._all_rows, 0, extra_rows=extra, finished=self.finished if self.stopping is not None else None)
         # ---- the prompts, in passes of `chunk` tokens per sequence, over the rows' table rows (read AFTER the reserve filled them)
-        last = self._prompt_pass(text_d[:, :maxP].to(torch.int64), Ps, chunk, self._prompt_buffers(R * chunk), 0,
-                                 self._append_over([t[rows_t] for t in self.tables]),
-                                 torch.index_select(self.lora_ids, 0, rows_t) if self._lora else None)
+        lora_ids = torch.index_select(self.lora_ids, 0, rows_t) if self._lora else None
+        if not any(cached):
+            last = self._prompt_pass(text_d[:, :maxP].to(torch.int64), Ps, chunk, self._prompt_buffers(R * chunk), 0,
+                                     self._append_over([t[rows_t] for t in self.tables]), lora_ids)
+        else:                                                               # only what is not cached: tokens[c_r:] at past c_r + c0
+            cs = [64 * len(ids) for ids in cached]
+            rest = torch.zeros((R, maxP), dtype=torch.int64)
+            for i, p in enumerate(pl):
+                rest[i, :Ps[i] - cs[i]] = p[cs[i]:]
+            lens = [P - c for P, c in zip(Ps, cs)]
+            chunk = min(chunk, max(lens))
+            last = self._prompt_pass(rest.to(dev), lens, chunk, self._prompt_buffers(R * chunk), cs,
+                                     self._append_over([t[rows_t] for t in self.tables], max(cs)), lora_ids)
+        if self.prefix is not None:                                         # one read-back: where the rows' pages are
+            page_ids = torch.index_select(self.pager.page_ids, 0, rows_t).cpu().tolist()
+            new = []
+            for r, p, P, ids, row_ids in zip(rows, pl, Ps, cached, page_ids):
+                fresh = self.prefix.insert(p.tolist(), row_ids[:P // 64]) if min(row_ids[:P // 64], default=0) >= 0 else []   # (a starved row: nothing)
+                self._row_cached[r] = ids + fresh
+                new += fresh
+            if new:
+                self.pager.hold({}, hold_ids=new)
         # ---- the head and the tail over the admitted rows, then what they leave to the text
         self._prompt_head(last, P_t, rows_t)
         self.history[rows_t, P_t.to(torch.int64)] = torch.index_select(self.tokens, 0, rows_t).to(torch.int32)
@@ -1529,6 +1601,9 @@ class DecodeEngine:
         where, the page accounting, `stats`, the end; this loop performs them.  A preempted request's prompt is recomputed; reading its
         text is one more read-back for the bursts that preempt.  A resumed text need not be bit-identical to an un-preempted one:
         prompt and decode attention round differently, sampler keys follow the row, and log entries from before a preemption are lost.
+        Under a prefix cache a request is charged only the pages its prompt cannot map, cached pages no row holds are evicted (one
+        launch) when the free ones do not cover an admission, and a preempted row's whole pages are entered into the cache before it
+        lets go, so the resumed request maps them again; stats gains hit_tokens, evicted, inserted_pages, every result hit_tokens.
         Raises before anything runs for a request that can never fit max_len (P + max_new > max_len) or the pool
         (ceil((P + max_new - 1 + n) / 64) > N, n the round's tokens: 1, or the tree's nodes).
         -> (per request, in order, dict(tokens: the generated text, reason: 1 a stop / 2 the length, preempted_at: the generated
@@ -1539,7 +1614,7 @@ class DecodeEngine:
         B, dev = self.B, self.dev
         adv = 1 if parents is None else len(self._tree_arg(parents, "serve", drafting=False))
         sched = servingmod.Scheduler(requests, B, self.max_len, stoppingmod.NO_PAGES, pool_pages=None if self.pager is None else self.pager.N,
-                                     advance=adv, static_pages=B * self.mb)
+                                     advance=adv, static_pages=B * self.mb, prefix=self.prefix)
         self.set_stopping(None)
         self.enable_drafting(None, *(self._draft_params or ()))
         self.set_stopping(stop, 0)
@@ -1548,8 +1623,27 @@ class DecodeEngine:
         while True:
             # 1., 2. harvest and release
             ended, starved = sched.ended()
-            texts = self.history[torch.tensor(starved, dtype=torch.int64, device=dev)].cpu().tolist() if starved else []
-            for b, i in sched.retire(texts):
+            texts, kept = [], []
+            if starved:
+                starved_t = torch.tensor(starved, dtype=torch.int64, device=dev)
+                texts = self.history[starved_t]
+                if self.prefix is not None:                                 # the rows' pages join the one read-back of their texts
+                    texts = torch.cat((texts, self.pager.page_ids[starved_t]), dim=1)
+                texts = texts.cpu().tolist()
+                if self.prefix is not None:
+                    # a preempted row's text stays cached: its slots < lengths - 1 are valid, so the whole pages of text[:L - 1] are
+                    # entered before the row lets go, and the resumed request maps them again unless they were evicted meanwhile
+                    for b, row in zip(starved, texts):
+                        text, ids = row[:self.max_len], row[self.max_len:]
+                        n = (sched.lens[b] - 1) // 64
+                        fresh = self.prefix.insert(text[:sched.lens[b] - 1], ids[:n]) if min(ids[:n], default=0) >= 0 else []
+                        self._row_cached[b] = list(self._row_cached.get(b, ())) + fresh
+                        kept += fresh
+                    texts = [row[:self.max_len] for row in texts]
+                    sched.stats["inserted_pages"] += len(kept)
+            if kept:
+                self.pager.hold({}, hold_ids=kept)                          # (the cache's holds, before the rows let go)
+            for b, i in sched.retire(texts, {b: len(self._row_cached.get(b, ())) for b in ended} if self.prefix is not None else None):
                 done[i].copy_(self.history[b])
             if ended:
                 # a harvested row goes back to what enable_drafting(None) left: a one-token text at its limit, frozen, owning nothing -
@@ -1561,12 +1655,17 @@ class DecodeEngine:
                 for b in ended:
                     self._text_starts[b] = 0
                 if self.pager is not None:
-                    self.pager.release(self.pager.rows_mask(ended))
-            # 3. admit what the scheduler placed
-            rows, batch = sched.place()
+                    self.release_rows(ended)
+            # 3. admit what the scheduler placed, behind the eviction it asks for (one launch)
+            rows, batch, *evict = sched.place()
+            if evict and evict[0][0]:
+                self.evict_prefixes(*evict[0])
             if rows:
+                before = len(self.prefix) if self.prefix is not None else 0
                 self.admit(rows, [q["prompt"] for q in batch], max_new_tokens=[q["max_new"] for q in batch],
                            text_start=[q["start"] for q in batch], chunk=chunk)
+                if self.prefix is not None:
+                    sched.stats["inserted_pages"] += len(self.prefix) - before
             if sched.idle():
                 break
             # 4., 5. a burst, and the one read-back

@@ -8,9 +8,14 @@ class Scheduler:
     """`requests`: (prompt_tokens, max_new_tokens) in order of arrival, for `batch` rows of `max_len` slots.  `starved`: the `finished`
     code of a row that was refused pages (stopping.NO_PAGES).  `pool_pages`: the pool's N (None: static pages, `static_pages` of them,
     and no accounting); `advance`: the tokens a round writes at most (1, or the tree's nodes).  Refuses, before any state exists, a
-    request that can never fit.  A request is dict(i, prompt, start, max_new, preempted_at); `slots[b]` is the request in row b."""
+    request that can never fit.  A request is dict(i, prompt, start, max_new, preempted_at); `slots[b]` is the request in row b.
 
-    def __init__(self, requests, batch, max_len, starved, pool_pages=None, advance=1, static_pages=0):
+    `prefix`: a `prefix.PrefixCache` (needs a pool) - place() then charges a request only the pages its prompt cannot map from the cache
+    (`peek`: the scheduler never changes the cache), counts the cached pages no row holds as obtainable, and says how many of them
+    must be evicted before the admit; a request also carries `hit_tokens`, the cached tokens of each of its placements."""
+
+    def __init__(self, requests, batch, max_len, starved, pool_pages=None, advance=1, static_pages=0, prefix=None):
+        assert prefix is None or pool_pages is not None, "serve: a prefix cache shares the pages of a pool"
         reqs = []
         for i, (p, m) in enumerate(requests):
             p, m = [int(t) for t in (p.tolist() if hasattr(p, "tolist") else p)], int(m)
@@ -25,17 +30,24 @@ class Scheduler:
         self.fin, self.lens = [0] * batch, [1] * batch                   # the last observation
         self.free, self.owned = pool_pages, [0] * batch                  # free pages (None without a pool), pages per row
         self.stats = dict(rounds=0, read_backs=0, admitted=0, preempted=0, peak_pages=static_pages if pool_pages is None else 0)
+        self.prefix = prefix
+        if prefix is not None:
+            self.stats.update(hit_tokens=0, evicted=0, inserted_pages=0)
+            for q in reqs:
+                q["hit_tokens"] = []
 
     def ended(self):
         """-> (the occupied rows that ended by the last observation, those of them that starved), ascending."""
         ended = [b for b in range(self.B) if self.slots[b] is not None and self.fin[b] != 0]
         return ended, [b for b in ended if self.fin[b] == self.starved]
 
-    def retire(self, texts=()):
+    def retire(self, texts=(), cached=None):
         """Free the rows of ended(), giving their pages back.  A starved row's request is preempted: `texts` has its text row (one per
         starved row, in row order - reading them is one read-back) and the request returns to the front of the queue, in row order, with
         prompt := the text so far; `start` and `max_new` stay, so its length limit and penalty window do; `preempted_at` gains the
-        generated tokens it held.  Any other row's request is done: results[i] = dict(length, reason).  -> those (row, i)."""
+        generated tokens it held.  Any other row's request is done: results[i] = dict(length, reason).  -> those (row, i).
+        `cached` (with a prefix cache): row -> how many of its pages the cache holds too - those stay where they are when the row lets
+        go, so only the others count as free again."""
         ended, starved = self.ended()
         assert len(texts) == len(starved)
         for b, text in zip(starved, texts):
@@ -50,25 +62,41 @@ class Scheduler:
         for b in ended:
             self.slots[b] = None
             if self.free is not None:
-                self.free, self.owned[b] = self.free + self.owned[b], 0
+                self.free, self.owned[b] = self.free + self.owned[b] - (cached or {}).get(b, 0), 0
         return done
 
     def place(self):
         """Waiting requests into free rows, rows ascending, in order of arrival, while the free pages cover the ceil((P + 1) / 64) of
-        each; the first that they do not cover blocks the queue, whatever is behind it.  -> (rows, their requests): what to admit."""
-        rows = []
+        each; the first that they do not cover blocks the queue, whatever is behind it.  -> (rows, their requests): what to admit.
+
+        With a prefix cache a request is charged ceil((P + 1) / 64) - len(peek(prompt, P - 1)) pages, against the free pages and the
+        cached pages that can be evicted without touching what this call peeked.  -> (rows, their requests, (n, keep)): evict n
+        cached pages first, sparing the ids `keep` - n is 0 while the free pages cover the charge."""
+        rows, charged, keep = [], 0, []
         for b in range(self.B):
             if self.slots[b] is not None or not self.queue:
                 continue
-            need = (len(self.queue[0]["prompt"]) + 1 + 63) // 64
-            if self.free is not None:
+            P = len(self.queue[0]["prompt"])
+            need = (P + 1 + 63) // 64
+            if self.prefix is not None:
+                hits = self.prefix.peek(self.queue[0]["prompt"], P - 1)
+                if charged + need - len(hits) > self.free + self.prefix.evictable(keep + hits):
+                    break
+                keep, charged = keep + hits, charged + need - len(hits)
+                self.queue[0]["hit_tokens"].append(64 * len(hits))
+                self.stats["hit_tokens"] += 64 * len(hits)
+            elif self.free is not None:
                 if need > self.free:
                     break
                 self.free -= need
             self.slots[b] = self.queue.popleft()
             rows.append(b)
         self.stats["admitted"] += len(rows)
-        return rows, [self.slots[b] for b in rows]
+        if self.prefix is None:
+            return rows, [self.slots[b] for b in rows]
+        evict = max(charged - self.free, 0)
+        self.free, self.stats["evicted"] = self.free + evict - charged, self.stats["evicted"] + evict
+        return rows, [self.slots[b] for b in rows], (evict, keep)
 
     def idle(self):
         """Nothing runs, so nothing waits (with every page free a request fits - checked on entry): the loop is over."""
@@ -88,5 +116,6 @@ class Scheduler:
     def output(self, texts):
         """`texts[i]`: the text row of request i (read once, one read-back) -> serve()'s return value."""
         self.stats["read_backs"] += 1
-        return [dict(tokens=list(texts[q["i"]][q["start"]:r["length"]]), reason=r["reason"], preempted_at=q["preempted_at"])
+        more = (lambda q: dict(hit_tokens=q["hit_tokens"])) if self.prefix is not None else (lambda q: {})
+        return [dict(tokens=list(texts[q["i"]][q["start"]:r["length"]]), reason=r["reason"], preempted_at=q["preempted_at"], **more(q))
                 for q, r in zip(self.reqs, self.results)], self.stats
