@@ -78,15 +78,33 @@ def block_order_row_sum(contrib):
     return _wave64_butterfly_sum(lanes)
 
 
+def running_amax(a, start):
+    """The row maximum of |a| as the reference forms it: a RUNNING maximum that a candidate replaces only where
+    `candidate > maximum` holds - false for a NaN candidate, so a NaN never enters it.
+      * quant_kernel(_fuse_sum), fused_kernels.cu:65-67 / :111-113: `val = val > zero ? val : -val; if (val > amax_val) amax_val =
+        val;` from amax_val = 0.0f; blockReduceMax then only meets the threads' (never NaN) maxima;
+      * generalLayerNorm(_fuse_sum), layernorm_kernels.cu:274,285: `amax = cuda_max(cuda_max<T_scalar, T>(cuda_abs(val)), amax)`
+        from amax = 1e-6f, with T = half: cuda_abs = __habs (utils.cuh:442-445; clears the sign bit, NaN stays NaN), the unary
+        cuda_max a cast (utils.cuh:387-391) and the binary one `(val1 > val2) ? val1 : val2` (utils.cuh:416-420) with the
+        candidate as val1 - a NaN candidate leaves amax as it is.
+    np.fmax returns the other operand where one is NaN: the same value for every row, and np.max's for NaN-free rows (|a| >= 0,
+    start >= 0).  The HIP kernels' fmaxf chains and wave_max (common.h) drop NaN in the same way."""
+    a = np.abs(np.asarray(a))
+    return np.fmax.reduce(a, axis=-1, initial=a.dtype.type(start))
+
+
+@np.errstate(divide="ignore", invalid="ignore", over="ignore")
 def quant_per_token(x, with_sum=False, sum_order="exact"):
     """fused_kernels.cu:58-82 / :106-130: amax over the row (fp32), scale = half_rn(amax/127),
-    q = rni_sat_s8(x * (127/amax)) with the UNROUNDED fp32 amax, sum = half_rn(fp32 row sum)."""
+    q = rni_sat_s8(x * (127/amax)) with the UNROUNDED fp32 amax, sum = half_rn(fp32 row sum).
+    A NaN element never enters amax (running_amax): the finite elements quantise as if it were absent, the NaN itself becomes
+    0 (cvt.rni.sat.s8 of NaN) and the row sum is NaN.  An inf element makes amax = scale = inf and 127/amax = 0: the whole row
+    quantises to 0 (inf * 0 = NaN -> 0)."""
     xf = np.asarray(x, np.float16).astype(np.float32)
-    amax = np.abs(xf).max(axis=-1)
+    amax = running_amax(xf, 0.0)
     scale = (amax / np.float32(127.0)).astype(np.float32).astype(np.float16)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        tmp = (np.float32(127.0) / amax).astype(np.float32)
-        pre = (xf * tmp[..., None]).astype(np.float32)
+    tmp = (np.float32(127.0) / amax).astype(np.float32)
+    pre = (xf * tmp[..., None]).astype(np.float32)
     q = rni_sat_s8(pre)
     if with_sum:
         # the reference sums in fp32 (fused_kernels.cu:104-122; its own association: 1024 strided threads + warp butterflies);
@@ -134,12 +152,15 @@ def reference_order_row_sum(val16):
     return _butterfly_sum32(slots).astype(np.float16)
 
 
+@np.errstate(divide="ignore", invalid="ignore", over="ignore")
 def rms_norm_general(x, gamma, eps, with_sum=False, sum_order="reference", stats_order="exact"):
     """generalLayerNorm(_fuse_sum), per-token dynamic scaling branch (layernorm_kernels.cu:207-326).
 
     mean = sum(x)/H; var = sum((x-mean)^2)/H; rstd = rsqrt(var+eps);
     val  = half_rn((x-mean)*rstd*gamma)         (compute_layernorm in fp32, cast to T=half)
-    amax = max(|val|, 1e-6) kept in half; sum accumulated PER THREAD in a half variable over that thread's
+    amax = max(|val|, 1e-6) kept in half, a running maximum that a NaN never enters (running_amax; a NaN or inf element makes the
+    mean, and with it every normalised value, NaN: amax stays half(1e-6), scale = half(half(1e-6) / 127) = 0, the int8 row is 0 and
+    the sum NaN); sum accumulated PER THREAD in a half variable over that thread's
     strided elements, then reduced over the block in fp32 (:275,:286) and stored as half;
     q = rni_sat_s8( ((x-mean)*rstd*gamma) * (127/amax) )  - the un-rounded fp32 value is re-computed (:312);
     scale = half_rn(amax/127).
@@ -165,7 +186,7 @@ def rms_norm_general(x, gamma, eps, with_sum=False, sum_order="reference", stats
     rstd = (np.float32(1.0) / np.sqrt((var + np.float32(eps)).astype(np.float32))).astype(np.float32)
     valf = ((diff * rstd[:, None]).astype(np.float32) * g[None, :]).astype(np.float32)
     val16 = valf.astype(np.float16)
-    amax = np.maximum(np.abs(val16).max(axis=-1), np.float16(1e-6)).astype(np.float32)
+    amax = running_amax(val16, 1e-6).astype(np.float32)              # layernorm_kernels.cu:274,285: from half(1e-6), NaN never enters
     scale = (amax / np.float32(127.0)).astype(np.float32).astype(np.float16)
     dyn = (np.float32(127.0) / amax).astype(np.float32)
     pre = (valf * dyn[:, None]).astype(np.float32)
@@ -191,6 +212,7 @@ def rms_norm(x, weight, eps):
     return (t.astype(np.float32) * np.asarray(weight, np.float16).astype(np.float32)).astype(np.float16)
 
 
+@np.errstate(over="ignore", invalid="ignore")
 def silu_and_mul(x):
     """activation_kernels.cu:9-30: out = half( half(x/(1+exp(-x))) * y ), x = in[:, :d], y = in[:, d:]."""
     xin = np.asarray(x, np.float16)

@@ -117,8 +117,8 @@ def test_rms_norm_general_fuse_sum(gpu, T, H):
 def test_rms_norm_general_reference_order_sum(gpu, T, H):
     """qs_set_row_sum_order(1): `a_ssums` in the reference's own order - per-thread HALF accumulators over the min(H, 1024)-thread
     stride partition, fp32 warp butterflies (layernorm_kernels.cu:275-306, reduction_utils.cuh:25-30,68-85) - BIT-EQUAL to
-    oracle.fused.rms_norm_general(sum_order="reference"), in the stand-alone op, the add + norm pair fusion and the K-slice planes
-    form; int8 rows and scales are the default order's, bit for bit (the switch touches nothing else)."""
+    oracle.fused.rms_norm_general(sum_order="reference"), in the stand-alone op and the add + norm pair fusion (the K-slice planes
+    form: tests/test_row_extremes_gpu.py); int8 rows and scales are the default order's, bit for bit (the switch touches nothing else)."""
     import qserve_backend.layernorm_ops as op
     from qserve_amd import fused as fz
     from qserve_amd._lib import lib
