@@ -1024,7 +1024,7 @@ int qs_pages_release(int32_t* free_list, int32_t* count, int32_t* page_ids, int3
  * Reference counts over the page pool: a page may have more than one HOLDER, so that rows can share the whole pages of a common
  * prefix (qserve_amd/prefix.py).  A holder is a (row, column) of page_ids that names the page, or the prefix cache (at most one hold
  * per page).  Two more state tensors, filled in place: refs int32 [N]: the holders of page id - 0 means free, i.e. on the free stack
- * -; scratch int32 [2 * N]: all zero between launches (every launch leaves it as it found it).  A pool either runs the three entries
+ * -; scratch int32 [2 * N]: all zero between launches (every launch leaves it as it found it).  A pool either runs the four entries
  * below and never qs_pages_reserve / qs_pages_release, or the other way round.  One launch of ONE workgroup each, capturable.
  *
  * qs_pages_reserve_refs.  The rule of qs_pages_reserve, and refs[id] = 1 for every popped id; a popped id with refs[id] != 0 is a
@@ -1045,13 +1045,36 @@ int qs_pages_release(int32_t* free_list, int32_t* count, int32_t* page_ids, int3
  * owned[b] = starved[b] = 0.  Broken invariants: count outside 0 .. N; an owned[b] outside 0 .. max_blocks; an id of H outside
  * 0 .. N - 1; g(id) > refs[id]; count rising above N.
  *
+ * qs_pages_fork.  src_rows int32 [batch]; lengths int32 [batch]; finished int32 [batch] or null, in and out.  Rows branch off running
+ * texts: they share the whole pages of their source and get a copy of its partly filled tail page.  TWO launches on the stream, no
+ * scratch.  Row d is a DESTINATION iff s = src_rows[d] >= 0 (any negative value: the row is not touched).  For a destination:
+ *     len = max(lengths[s], 1);  w = (len - 1) / 64;  t = (len - 1) % 64;  need = w + (t > 0 ? 1 : 0)
+ * - slot len - 1 is the first slot any writer of the text still writes, so pages 0 .. w - 1 are never written again and page w, if t
+ * > 0, holds t slots that both texts read.  The source COVERS the fork iff need <= max_blocks and owned[s] >= need.  A destination
+ * whose source does not cover it is REFUSED.  Every other destination asks for grow_d = (t > 0 ? 1 : 0) fresh pages; with S_d the
+ * inclusive prefix of grow in row order (0 for rows that ask nothing), it is SERVED iff grow_d == 0 or S_d <= count, otherwise
+ * REFUSED; the s-th popped id is free_list[count - 1 - s], and count drops by the largest served S_d.  A served destination:
+ * page_ids[d, j] = page_ids[s, j] for 0 <= j < w, with refs += 1 per naming (d, j) (several destinations may name one page);
+ * page_ids[d, w] = free_list[count - S_d] with refs = 1, if t > 0; entry (d, kv, j) of the K and V tables of all layers becomes the
+ * page's address for 0 <= j < need; owned[d] = need.  A refused destination holds nothing: starved[d] = 1, and finished[d] = 3 where
+ * finished is given and finished[d] == 0.  Broken invariants: count outside 0 .. N; an owned[b] outside 0 .. max_blocks; s >= batch;
+ * s == d; src_rows[s] >= 0 (a source is no destination of the same launch); owned[d] != 0; page_ids[s, j] for j < min(need,
+ * owned[s]) outside 0 .. N - 1 or with refs == 0; a popped id outside 0 .. N - 1 or with refs != 0.
+ * The second launch, a grid over (row, layer x K / V), copies the page_bytes bytes of page page_ids[s, w] to page page_ids[d, w] in
+ * every pool, for every destination that the first launch served with t > 0 - which it reads from the state: error[0] == 0,
+ * starved[d] == 0 (so a destination still marked by an EARLIER refusal is mapped but not copied: release a row before it becomes
+ * one), owned[d] == need <= owned[s], the two ids in range and different, the two table entries those pages' addresses.  The whole
+ * page is copied: the allocator does not know a page's layout, and readers mask the slots beyond a text.  16-byte vectors where
+ * page_bytes and both addresses are multiples of 16, bytes otherwise.
+ *
  * A broken invariant: error[0] = 1 and the launch changes NOTHING else (the scratch is zero again).  The state after a launch is a
  * function of the state before it, the order of the free stack included: the only atomics are integer add and max on refs and the
  * scratch, whose result no arrival order changes.  Vector stores only; no address is formed from an unchecked or unclamped index.
  *
  * QS_EINVAL before any device call: what qs_pages_reserve / qs_pages_release refuse (take, src and rows_mask may not be null); refs
  * null; scratch null (hold, unhold); num_hold / num_drop outside 0 .. num_pages; a null id list with a positive number; an int32
- * array not 4-byte aligned.  batch == 0 (and, for hold and unhold, no ids): QS_OK, no launch.
+ * array not 4-byte aligned.  batch == 0 (and, for hold and unhold, no ids): QS_OK, no launch.  qs_pages_fork: src_rows and lengths
+ * may not be null, finished may.
  * ---------------------------------------------------------------------------------------------------------- */
 int qs_pages_reserve_refs(int32_t* free_list, int32_t* count, int32_t* page_ids, int32_t* owned, int32_t* starved, int32_t* error,
                           const int64_t* layer_tables, const int64_t* layer_bases, int32_t* refs, const int32_t* lengths,
@@ -1065,6 +1088,10 @@ int qs_pages_unhold(int32_t* free_list, int32_t* count, int32_t* page_ids, int32
                     const int64_t* layer_tables, const int64_t* layer_bases, int32_t* refs, int32_t* scratch, const int32_t* rows_mask,
                     const int32_t* drop_ids, int num_drop, int batch, int max_blocks, int num_layers, int num_pages, int64_t page_bytes,
                     qs_stream_t stream);
+int qs_pages_fork(int32_t* free_list, int32_t* count, int32_t* page_ids, int32_t* owned, int32_t* starved, int32_t* error,
+                  const int64_t* layer_tables, const int64_t* layer_bases, int32_t* refs, const int32_t* src_rows,
+                  const int32_t* lengths, int32_t* finished, int batch, int max_blocks, int num_layers, int num_pages, int64_t page_bytes,
+                  qs_stream_t stream);
 
 #ifdef __cplusplus
 }

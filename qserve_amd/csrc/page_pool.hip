@@ -1,7 +1,7 @@
 // page_pool.hip -- the device-side page allocator of the paged KV cache, for MI355X (gfx950): a free stack of page indices that is
 // common to the K and V pools of every layer, and the two launches that move pages between the stack and the rows of the per-layer
 // pointer tables without the host knowing a length.  DESIGN.md 10 ("Page pool and admission"); the rules are the header comment of
-// qs_pages_reserve / qs_pages_release in include/qserve_amd.h, in exact integers.  This file holds FOUR kernels.
+// qs_pages_reserve / qs_pages_release in include/qserve_amd.h, in exact integers.  This file holds SIX kernels.
 //
 //   pages_reserve_kernel   ONE workgroup of POOL_THREADS threads; rows are walked in chunks of POOL_THREADS (batch <= MAX_ROWS).
 //                1. per row: owned (checked, clamped), need, grow -> LDS;
@@ -21,6 +21,12 @@
 //                (atomic add) and its first position in H (atomic max of len(H) - p) in `scratch`; the pages whose count reaches 0 are
 //                pushed in the order of their first occurrence - a chunked scan over H of "first occurrence of a freed page" -, then
 //                refs -= g, the rows end as after a release, and the scratch is zero again.
+//   pages_fork_kernel      (qs_pages_fork, launch 1) destination rows branch off a source row: the whole pages below the source's last
+//                written slot are mapped and counted as in a hold, one fresh page per destination is popped for the partly filled
+//                tail - the prefix of `grow` (0 or 1) in row order, as the reserve serves -; a destination that cannot be served is
+//                marked as the reserve marks a refused row.
+//   pages_fork_copy_kernel (launch 2) a grid over (row, layer x K / V): the source's tail page, page_bytes bytes, into the fresh page
+//                of every served destination - 16-byte vectors where the pages allow, bytes otherwise.
 // The two uncounted entries use no atomics; the counted ones only integer add / max, whose result no arrival order changes.  No
 // cross-workgroup traffic, vector stores only.  Every index is clamped before an address is formed from it.
 #include "common.h"
@@ -50,6 +56,7 @@ struct PoolArgs {
     const int* take;                                 // [batch]            (hold)
     const int* src;                                  // [batch, mb]        (hold)
     const int* extra_ids;                            // [num_extra] or null (hold: hold_ids; unhold: drop_ids)
+    const int* src_rows;                             // [batch]            (fork: the row a destination branches off, or < 0)
     int num_extra;
     long long page_bytes;
     int batch, mb, L, N, extra;
@@ -416,6 +423,132 @@ __global__ __launch_bounds__(POOL_THREADS) void pages_unhold_kernel(const PoolAr
     if (tid == 0) a.count[0] = cnt + freed;
 }
 
+// what a fork asks of its source row, in the header's words: the page w and slot t of the last written position, and the pages to cover
+struct ForkNeed {
+    long long w, need;
+    int t;
+};
+__device__ __forceinline__ ForkNeed fork_need(int length) {
+    const long long len = length < 1 ? 1 : length;
+    ForkNeed f;
+    f.w = (len - 1) / 64, f.t = (int)((len - 1) % 64), f.need = f.w + (f.t > 0 ? 1 : 0);
+    return f;
+}
+
+// (qs_pages_fork, launch 1) destinations map the whole pages of their source and pop one fresh page for its tail.  sh.own holds a
+// destination's case: 0 no destination, 1 refused by its source (the source does not cover the fork), 2 asks (grow = 0 or 1).
+__global__ __launch_bounds__(POOL_THREADS) void pages_fork_kernel(const PoolArgs a) {
+    __shared__ PoolShared sh;
+    const int tid = threadIdx.x;
+    const int count = a.count[0];
+    bool bad = count < 0 || count > a.N;
+    const int cnt = count < 0 ? 0 : count > a.N ? a.N : count;
+    for (int d = tid; d < a.batch; d += POOL_THREADS) {
+        const int own = a.owned[d];
+        bad = bad || own < 0 || own > a.mb;
+        const int s = a.src_rows[d];
+        int state = 0, grow = 0;
+        if (s >= 0) {
+            const int sc = clamp_index(s, a.batch);
+            bad = bad || s >= a.batch || s == d || a.src_rows[sc] >= 0 || own != 0;
+            const ForkNeed f = fork_need(a.lengths[sc]);
+            const int own_s = a.owned[sc], osc = own_s < 0 ? 0 : own_s > a.mb ? a.mb : own_s;
+            const bool covered = f.need <= a.mb && osc >= f.need;
+            const int named = f.need < osc ? (int)f.need : osc;              // <= mb
+            for (int j = 0; j < named; ++j) {
+                const int id = a.page_ids[(size_t)sc * a.mb + j];
+                bad = bad || id < 0 || id >= a.N || a.refs[clamp_index(id, a.N)] == 0;
+            }
+            state = covered ? 2 : 1;
+            grow = covered && f.t > 0 ? 1 : 0;
+        }
+        sh.own[d] = state;
+        sh.grow[d] = grow;
+    }
+    __syncthreads();
+    scan_rows(sh, a.batch);
+    int mine = 0;
+    for (int d = tid; d < a.batch; d += POOL_THREADS) {
+        const int S = sh.S[d];
+        mine = S <= cnt && S > mine ? S : mine;
+    }
+    const int popped = block_max(sh, mine);                                 // <= cnt <= N
+    for (int s = tid; s < popped; s += POOL_THREADS) {
+        const int id = a.free_list[clamp_index((long long)cnt - 1 - s, a.N)];
+        bad = bad || id < 0 || id >= a.N || a.refs[clamp_index(id, a.N)] != 0;
+    }
+    if (block_any(sh, bad)) {                                               // (workgroup-uniform)
+        if (tid == 0) a.error[0] = 1;
+        return;
+    }
+    // the fill, a strided loop over (destination, layer, K / V): the thread walks the row's columns (a source is no destination of
+    // this launch: its page_ids are only read)
+    const int lk = 2 * a.L;
+    const long long items = (long long)a.batch * lk;
+    for (long long it = tid; it < items; it += POOL_THREADS) {
+        const int d = (int)(it / lk), w = (int)(it - (long long)d * lk);
+        if (sh.own[d] != 2 || (sh.grow[d] != 0 && sh.S[d] > cnt)) continue;
+        const int sc = clamp_index(a.src_rows[d], a.batch);
+        const ForkNeed f = fork_need(a.lengths[sc]);                        // (covered: need <= mb)
+        long long* table = reinterpret_cast<long long*>(a.layer_tables[w >> 1]);
+        for (int j = 0; j < (int)f.need; ++j) {
+            const int col = clamp_index(j, a.mb);
+            const bool fresh = j == (int)f.w;                               // (only with t > 0: need = w + 1)
+            const int id = fresh ? a.free_list[clamp_index((long long)cnt - sh.S[d], a.N)]
+                                 : clamp_index(a.page_ids[(size_t)sc * a.mb + col], a.N);
+            if (w == 0) {
+                a.page_ids[(size_t)d * a.mb + col] = id;
+                if (fresh) a.refs[id] = 1; else atomicAdd(&a.refs[id], 1);
+            }
+            table[((size_t)d * 2 + (w & 1)) * a.mb + col] = a.layer_bases[w] + (long long)id * a.page_bytes;
+        }
+    }
+    for (int d = tid; d < a.batch; d += POOL_THREADS) {
+        const int state = sh.own[d];
+        if (state == 0) continue;
+        if (state == 2 && (sh.grow[d] == 0 || sh.S[d] <= cnt)) {
+            const int sc = clamp_index(a.src_rows[d], a.batch);
+            a.owned[d] = (int)fork_need(a.lengths[sc]).need;
+        } else {
+            a.starved[d] = 1;
+            if (a.finished && a.finished[d] == 0) a.finished[d] = NO_PAGES;
+        }
+    }
+    if (tid == 0) a.count[0] = cnt - popped;
+}
+
+constexpr int COPY_THREADS = 256;
+constexpr int COPY_SPLIT = 1;                        // workgroups per page (grid z): each copies one contiguous piece of it
+
+// (qs_pages_fork, launch 2) workgroup (d, layer x K / V) copies the source's tail page to the fresh page of a served destination.
+// Whether d is one is read from what launch 1 left: no index or address is formed from anything unchecked or unclamped, and the
+// addresses are the two table entries launch 1 wrote - so the launch is safe behind an errored launch 1, and copies nothing then.
+__global__ __launch_bounds__(COPY_THREADS) void pages_fork_copy_kernel(const PoolArgs a) {
+    const int d = blockIdx.x, w = blockIdx.y;
+    const int s = a.src_rows[d];
+    if (s < 0 || s >= a.batch || s == d || a.error[0] != 0 || a.starved[d] != 0) return;
+    const ForkNeed f = fork_need(a.lengths[s]);
+    if (f.t == 0 || f.need > a.mb || a.owned[d] != (int)f.need || a.owned[s] < (int)f.need) return;
+    const int col = clamp_index(f.w, a.mb);
+    const int from = a.page_ids[(size_t)s * a.mb + col], to = a.page_ids[(size_t)d * a.mb + col];
+    if (from == to || from < 0 || from >= a.N || to < 0 || to >= a.N) return;
+    const long long* table = reinterpret_cast<const long long*>(a.layer_tables[w >> 1]);
+    const long long src = table[((size_t)s * 2 + (w & 1)) * a.mb + col], dst = table[((size_t)d * 2 + (w & 1)) * a.mb + col];
+    if (src != a.layer_bases[w] + (long long)from * a.page_bytes || dst != a.layer_bases[w] + (long long)to * a.page_bytes) return;
+    const bool vectors = ((src | dst | a.page_bytes) & 15) == 0;
+    const long long n = vectors ? a.page_bytes / 16 : a.page_bytes;          // this workgroup's piece: [lo, hi) of n vectors or bytes
+    const long long piece = (n + gridDim.z - 1) / gridDim.z, lo = piece * blockIdx.z, hi = lo + piece < n ? lo + piece : n;
+    if (vectors) {
+        const uint4* p = reinterpret_cast<const uint4*>(src);
+        uint4* q = reinterpret_cast<uint4*>(dst);
+        for (long long i = lo + threadIdx.x; i < hi; i += COPY_THREADS) q[i] = p[i];
+    } else {
+        const unsigned char* p = reinterpret_cast<const unsigned char*>(src);
+        unsigned char* q = reinterpret_cast<unsigned char*>(dst);
+        for (long long i = lo + threadIdx.x; i < hi; i += COPY_THREADS) q[i] = p[i];
+    }
+}
+
 // what every entry asks for -> QS_OK, or QS_EINVAL with the message set
 int pool_arguments(const char* what, const int32_t* free_list, const int32_t* count, const int32_t* page_ids, const int32_t* owned,
                    const int32_t* starved, const int32_t* error, const int64_t* layer_tables, const int64_t* layer_bases, const void* rows,
@@ -535,4 +668,27 @@ extern "C" int qs_pages_unhold(int32_t* free_list, int32_t* count, int32_t* page
     a.refs = refs, a.scratch = scratch, a.rows_mask = rows_mask, a.extra_ids = drop_ids, a.num_extra = num_drop;
     hipLaunchKernelGGL(pages_unhold_kernel, dim3(1), dim3(POOL_THREADS), 0, (hipStream_t)stream, a);
     return qs_launch_status("pages_unhold");
+}
+
+extern "C" int qs_pages_fork(int32_t* free_list, int32_t* count, int32_t* page_ids, int32_t* owned, int32_t* starved, int32_t* error,
+                             const int64_t* layer_tables, const int64_t* layer_bases, int32_t* refs, const int32_t* src_rows,
+                             const int32_t* lengths, int32_t* finished, int batch, int max_blocks, int num_layers, int num_pages,
+                             int64_t page_bytes, qs_stream_t stream) {
+    int rc = pool_arguments("pages_fork", free_list, count, page_ids, owned, starved, error, layer_tables, layer_bases, src_rows, lengths,
+                            finished, batch, max_blocks, num_layers, num_pages, page_bytes);
+    if (rc != QS_OK) return rc;
+    QS_REQUIRE(lengths, "pages_fork: null pointer (lengths)");
+    if ((rc = refs_arguments("pages_fork", refs, nullptr, false, nullptr, 0, num_pages)) != QS_OK) return rc;
+    if (batch == 0) return QS_OK;
+    PoolArgs a = pool_args(free_list, count, page_ids, owned, starved, error, layer_tables, layer_bases, batch, max_blocks, num_layers,
+                           num_pages, page_bytes);
+    a.refs = refs, a.src_rows = src_rows, a.lengths = lengths, a.finished = finished;
+    hipLaunchKernelGGL(pages_fork_kernel, dim3(1), dim3(POOL_THREADS), 0, (hipStream_t)stream, a);
+    if ((rc = qs_launch_status("pages_fork")) != QS_OK) return rc;
+    int split = COPY_SPLIT;
+#ifdef QS_TIMING
+    if (const char* e = getenv("QS_FORK_COPY_SPLIT")) split = atoi(e) < 1 ? 1 : atoi(e) > 64 ? 64 : atoi(e);   // (scripts/bench_fork.py)
+#endif
+    hipLaunchKernelGGL(pages_fork_copy_kernel, dim3(batch, 2 * num_layers, split), dim3(COPY_THREADS), 0, (hipStream_t)stream, a);
+    return qs_launch_status("pages_fork (copy)");
 }

@@ -171,7 +171,7 @@ class W4A8Linear:
 class DecodeEngine:
     def __init__(self, cfg, batch, prompt_len, max_new, group_size=-1, int4_kv=True, device="cuda:0", seed=0,
                  tp_rank=0, tp_world=1, with_lm_head=True, fuse_pairs=True, weights=None, vocab_parallel=True, planes=None,
-                 direct_allreduce=None, page_pool=None, prefix_cache=False):
+                 direct_allreduce=None, page_pool=None, prefix_cache=False, share_pages=False):
         """weights: None = synthetic random-quantised tensors of the right shapes; otherwise this rank's tensors as
         qserve_amd.loader.load_llama_w4a8 returns them (checkpoint path).  A config with `experts` and `experts_per_token`
         (MIXTRAL_8X7B, TINY_MOE) builds mixture-of-experts layers: a router `gate` fp16 [E, hid] and two `moe.MoELinear`s in place of
@@ -194,7 +194,11 @@ class DecodeEngine:
         reserve and release of the engine goes through the counted entries) and `self.prefix`, a `prefix.PrefixCache`, remembers which
         whole pages of 64 prompt tokens sit where: admit() maps the cached pages of a prompt's beginning into the row instead of
         recomputing them, and enters what it computed; serve() keeps a preempted row's text in the cache.  Only pages that no writer
-        touches again are shared ("Prefix cache"), so there is no copy-on-write.  Off: everything launches what it did."""
+        touches again are shared ("Prefix cache"), so there is no copy-on-write.  Off: everything launches what it did.
+
+        `share_pages` (needs `page_pool`, one GPU): the pool counts holders as under `prefix_cache`, without a `PrefixCache` - what
+        fork() and admit(copy_rows=) need to let several rows share the whole pages of one text ("Forks").  With both off
+        the pool is uncounted and everything launches what it did."""
         self.cfg, self.B, self.dev = cfg, batch, torch.device(device)
         # mixture of experts: (experts, experts per token), or None for a dense model - which launches exactly what it always did
         self.moe = (int(cfg["experts"]), int(cfg["experts_per_token"])) if cfg.get("experts") else None
@@ -281,6 +285,9 @@ class DecodeEngine:
         assert not prefix_cache or (page_pool is not None and tp_world == 1), \
             "DecodeEngine: prefix_cache=True shares pages of a page pool - give page_pool=N; it runs on one GPU (the allocator is one " \
             "launch on one device; tensor parallelism under a pool is not built)"
+        assert not share_pages or (page_pool is not None and tp_world == 1), \
+            "DecodeEngine: share_pages=True shares pages of a page pool - give page_pool=N; it runs on one GPU (the allocator is one " \
+            "launch on one device; tensor parallelism under a pool is not built)"
         nblocks = batch * self.mb if page_pool is None else int(page_pool) + 1       # (+ 1: the sink)
         perm = torch.randperm(batch * self.mb, generator=torch.Generator().manual_seed(seed)).reshape(batch, self.mb)
         self.pools, self.tables = [], []
@@ -299,7 +306,7 @@ class DecodeEngine:
         self.pager = self._all_rows = self.prefix = None
         self._row_cached = {}
         if page_pool is not None:
-            self.pager = pagingmod.PagePool(self.tables, self.pools, self.page_bytes, refcounts=bool(prefix_cache))
+            self.pager = pagingmod.PagePool(self.tables, self.pools, self.page_bytes, refcounts=bool(prefix_cache or share_pages))
             self.prefix = prefixmod.PrefixCache() if prefix_cache else None
             self._all_rows = torch.ones((batch,), dtype=torch.int32, device=self.dev)
         # ---- activation buffers (ActivationBuffer, input_metadata.py:71-109)
@@ -433,6 +440,53 @@ class DecodeEngine:
             for r in rows:
                 self.prefix.row_released(self._row_cached.pop(r, ()))
         self.pager.release(mask, drop_ids)
+
+    def _forkable(self, what):
+        self._single_gpu(what)
+        assert self.pager is not None and self.pager.refs is not None, \
+            f"{what}: rows share pages of a counted page pool - DecodeEngine(page_pool=N, share_pages=True) (or prefix_cache=True)"
+        assert self.history is not None, f"{what}: enable_drafting first (enable_drafting(None) for an empty batch): it writes `history`"
+
+    def _row_tensors(self):
+        """Every persistent per-row tensor that a text carries with it (those that exist)."""
+        return [t for t in (self.tokens, self.lengths, self.history, self.prompt_lens, self.limit_lens, self.finished, self.fsm_state,
+                            self.lora_ids, self.logprob_log, self.rank_log, self.top_ids_log, self.top_lp_log, self.hidden, self.final)
+                if t is not None]
+
+    def _fork_pages(self, pairs, lengths):
+        """The fork launch for `pairs` (dst, src) over the texts' `lengths` (int32 [B]), and the host's record of the cached pages the
+        new rows hold: all of the source's - they are whole prompt pages, below slot lengths - 1."""
+        src_rows = torch.full((self.B,), -1, dtype=torch.int32)
+        for d, s in pairs:
+            src_rows[d] = s
+            if self.prefix is not None:
+                self._row_cached[d] = self.prefix.row_held(self._row_cached.get(s, ()))
+        self.pager.fork(src_rows.to(self.dev), lengths, finished=self.finished if self.stopping is not None else None)
+
+    def fork(self, src, rows):
+        """Branch the running text of row `src` into the rows `rows` (distinct, without `src`), eagerly: they are released, every
+        per-row state of `src` - tokens, lengths, history, prompt_lens, limit_lens, finished, fsm_state, lora_ids, the log-probability
+        logs, hidden / final - is copied into them in place (no capture is invalidated), and ONE fork launch pair
+        (`paging.PagePool.fork`) maps the source's whole pages below slot lengths - 1 into them and gives each a copy of the partly
+        filled page, with `finished` while the stop rule is on: a row that cannot get its page ends with NO_PAGES (check() raises
+        while the rule is off).  No copy-on-write: every writer of either text writes slots >= lengths - 1, which lie in the copied
+        page or behind it.  The branches share the current token and draw their next ones under their own rows' sampler keys: they
+        diverge under sampling and stay identical under greedy decoding.  Needs a counted pool (share_pages=True or prefix_cache=True)
+        and enable_drafting; single GPU, with the lm_head."""
+        self._forkable("fork")
+        B = self.B
+        src, rows = int(src), [int(r) for r in rows]
+        assert 0 <= src < B and rows and len(set(rows)) == len(rows) and all(0 <= r < B for r in rows) and src not in rows, \
+            f"fork: row {src} into rows {rows} - distinct row indices in 0 .. {B - 1}, the source not among them"
+        self.release_rows(rows)
+        rows_t = torch.tensor(rows, dtype=torch.int64, device=self.dev)
+        src_t = torch.full((len(rows),), src, dtype=torch.int64, device=self.dev)
+        for t in self._row_tensors():
+            t.index_copy_(0, rows_t, torch.index_select(t, 0, src_t))
+        if self._text_starts is not None:
+            for r in rows:
+                self._text_starts[r] = self._text_starts[src]
+        self._fork_pages([(r, src) for r in rows], self.lengths)
 
     def evict_prefixes(self, pages, keep=()):
         """Evict up to `pages` cached pages that no row holds, least recently used leaves first (`prefix.PrefixCache.evict`; `keep`: ids
@@ -1468,7 +1522,7 @@ class DecodeEngine:
         """Where every row's generated text begins, on the host: `prompt_lens`, per row once admit() has been used."""
         return self._text_starts or [self._prompt_len] * self.B
 
-    def admit(self, rows, prompts, max_new_tokens=None, start_states=None, text_start=None, chunk=None):
+    def admit(self, rows, prompts, max_new_tokens=None, start_states=None, text_start=None, chunk=None, copy_rows=None):
         """Put new texts into the rows `rows` (distinct indices) of the fixed batch, eagerly, leaving every other row's `tokens`,
         `lengths`, `hidden`, `history`, logs, states and pages untouched byte for byte.  `prompts`: one 1-D token sequence per row,
         ragged, 1 <= P_r and P_r + 1 <= max_len.  After enable_drafting (enable_drafting(None) for an empty batch).  A static engine's
@@ -1491,7 +1545,14 @@ class DecodeEngine:
         mapped into the row by one hold launch between the release and the reserve, the passes run tokens[c_r:] at past c_r + c0 only,
         and - behind one read-back of the rows' page ids - the floor(P_r / 64) whole pages the prompt filled are entered into the cache,
         which takes its holds in one more launch.  Requests of ONE admit do not share what none of them found cached.  admit never
-        evicts (`evict_prefixes`).  Refused while set_lora is on."""
+        evicts (`evict_prefixes`).  Refused while set_lora is on.
+
+        `copy_rows` (None, or per prompt a list of further rows; needs a counted pool): the FOLLOWERS start as further samples of the
+        same prompt.  The rows named in `rows`, the leaders, run exactly what they run without it; then ONE fork launch pair maps the
+        prompt's whole pages into the followers and copies the partly filled one (lengths P_r + 1: slot P_r is the first one a
+        follower writes), and the head runs ONCE over leaders and followers, on the leaders' last hidden rows: every row draws its
+        own first token under key (its row, P_r).  Texts, limits, states, adapters, cleared logs and the root check cover all of them.
+        All rows, leaders and followers, must be distinct."""
         self._single_gpu("admit")
         assert self.prefix is None or not self._lora, \
             "admit: the engine has a prefix cache and LoRA is on (set_lora) - K / V under an adapter differ from the base model's, and a " \
@@ -1501,6 +1562,15 @@ class DecodeEngine:
         rows = [int(r) for r in rows]
         R = len(rows)
         assert R >= 1 and len(set(rows)) == R and all(0 <= r < B for r in rows), f"admit: rows {rows} - distinct row indices in 0 .. {B - 1}"
+        lead = list(range(R))                                               # per row of `rows`: the index of the prompt it runs
+        if copy_rows is not None:
+            self._forkable("admit(copy_rows=)")
+            copies = [[int(r) for r in c] for c in copy_rows]
+            assert len(copies) == R, f"admit: copy_rows is one list of further rows per prompt ({R})"
+            lead = lead + [i for i, c in enumerate(copies) for _ in c]
+            rows = rows + [r for c in copies for r in c]
+            assert len(set(rows)) == len(rows) and all(0 <= r < B for r in rows), \
+                f"admit: rows and copy_rows {rows} - distinct row indices in 0 .. {B - 1} overall"
         pl = [torch.as_tensor(p).to("cpu", torch.int64) for p in prompts]
         assert len(pl) == R and all(p.dim() == 1 for p in pl), f"admit: one 1-D token sequence per row ({R})"
         Ps = [p.numel() for p in pl]
@@ -1525,24 +1595,31 @@ class DecodeEngine:
         assert chunk is None or int(chunk) >= 1, f"admit: chunk={chunk} (None, or at least one token per sequence and pass)"
         chunk = maxP if chunk is None else min(int(chunk), maxP)
         i32 = dict(dtype=torch.int32, device=dev)
+        all_rows, rows = rows, rows[:R]                                     # leaders, then followers
         rows_t = torch.tensor(rows, dtype=torch.int64, device=dev)
+        all_t, lead_t = rows_t, None
+        if len(lead) > R:
+            all_t, lead_t = torch.tensor(all_rows, dtype=torch.int64, device=dev), torch.tensor(lead, dtype=torch.int64, device=dev)
+        every = lambda v: [v[i] for i in lead]                              # noqa: E731
         P_t = torch.tensor(Ps, **i32)
         # ---- the rows' state that the pass does not compute: text, where it begins, its limit; live again
         text = torch.zeros((R, cap), dtype=torch.int32)
         for i, p in enumerate(pl):
             text[i, :Ps[i]] = p.to(torch.int32)
         text_d = text.to(dev)                                               # the one upload of the prompts
-        self.history[rows_t] = text_d
-        self.prompt_lens[rows_t] = torch.tensor(starts, **i32)
+        self.history[all_t] = text_d if lead_t is None else torch.index_select(text_d, 0, lead_t)
+        self.prompt_lens[all_t] = torch.tensor(every(starts), **i32)
         self._text_starts = self._row_starts()
-        for r, s in zip(rows, starts):
+        for r, s in zip(all_rows, every(starts)):
             self._text_starts[r] = s
         if limits is not None:
-            self.limit_lens[rows_t] = torch.tensor(limits, **i32)
+            self.limit_lens[all_t] = torch.tensor(every(limits), **i32)
         if self.finished is not None:
-            self.finished[rows_t] = 0
+            self.finished[all_t] = 0
         if st is not None:
-            self.fsm_state[rows_t] = torch.tensor(st, **i32)
+            self.fsm_state[all_t] = torch.tensor(every(st), **i32)
+        if self._lora and lead_t is not None:                                    # a follower's prompt pages are its leader's: so is its adapter
+            self.lora_ids[all_t] = torch.index_select(self.lora_ids, 0, rows_t)[lead_t]
         # ---- pages: the rows give back what they own and take their prompts' (two launches).  Under a prefix cache the whole pages of
         # a prompt's beginning that are cached - at most those below its last token, which is always recomputed: the head needs its
         # hidden row - are mapped into the row by a hold between the two, and the reserve grows the row behind them.  What a request
@@ -1553,7 +1630,7 @@ class DecodeEngine:
             extra[rows_t] = P_t
             if self.prefix is not None:
                 cached = [self.prefix.match(p.tolist(), limit=P - 1) for p, P in zip(pl, Ps)]
-            self.release_rows(rows)
+            self.release_rows(all_rows)
             if any(cached):
                 self.pager.hold({r: ids for r, ids in zip(rows, cached) if ids})
             self.pager.reserve(self._all_rows, 0, extra_rows=extra, finished=self.finished if self.stopping is not None else None)
@@ -1580,9 +1657,15 @@ class DecodeEngine:
                 new += fresh
             if new:
                 self.pager.hold({}, hold_ids=new)
+        # ---- the followers: the prompt's whole pages shared, the partly filled one copied - one launch pair over texts of P_r + 1
+        if lead_t is not None:
+            told = torch.ones((B,), dtype=torch.int32)
+            told[rows] = torch.tensor(Ps, dtype=torch.int32) + 1
+            self._fork_pages([(r, rows[i]) for r, i in zip(all_rows[R:], lead[R:])], told.to(dev))
+            last, P_t = torch.index_select(last, 0, lead_t), P_t[lead_t]
         # ---- the head and the tail over the admitted rows, then what they leave to the text
-        self._prompt_head(last, P_t, rows_t)
-        self.history[rows_t, P_t.to(torch.int64)] = torch.index_select(self.tokens, 0, rows_t).to(torch.int32)
+        self._prompt_head(last, P_t, all_t)
+        self.history[all_t, P_t.to(torch.int64)] = torch.index_select(self.tokens, 0, all_t).to(torch.int32)
         self._len_bound = max(self._len_bound, maxP + 1)
         if self.stopping is not None:                                       # the root check of set_stopping: a first token that is a
             self._stop_k.zero_()                                            # stop, or a row at its limit; every other row's current
@@ -1590,7 +1673,10 @@ class DecodeEngine:
 
     def serve(self, requests, stop=(), parents=None, sampled=False, poll_every=8, chunk=None):
         """Serve a stream of requests through the fixed batch: `requests` is a list of (prompt_tokens, max_new_tokens), first come first
-        served.  Starts from the empty batch (enable_drafting(None), set_stopping(stop, 0): every row frozen), then loops:
+        served - or (prompt_tokens, max_new_tokens, n) for n samples of one prompt (needs a counted pool: share_pages=True or
+        prefix_cache=True): the group is admitted in one admit(copy_rows=) once n rows are free, the samples share the prompt's whole
+        pages, each is from then on a request of its own, and the result gains samples = [dict(tokens, reason, preempted_at)] * n
+        (the top-level entries are sample 0's), stats gains forked.  Starts from the empty batch (enable_drafting(None), set_stopping(stop, 0): every row frozen), then loops:
           1. the rows that finished hand their texts over (a device copy of their history rows; the texts are read once, at the end),
           2. their pages are released,
           3. waiting requests are admitted into free rows, in order, while the pool's free count covers ceil((P + 1) / 64) pages each,
@@ -1615,6 +1701,9 @@ class DecodeEngine:
         adv = 1 if parents is None else len(self._tree_arg(parents, "serve", drafting=False))
         sched = servingmod.Scheduler(requests, B, self.max_len, stoppingmod.NO_PAGES, pool_pages=None if self.pager is None else self.pager.N,
                                      advance=adv, static_pages=B * self.mb, prefix=self.prefix)
+        assert len(sched.reqs) == len(sched.groups) or self.pager.refs is not None, \
+            "serve: the samples of a request with n > 1 share pages of a counted page pool - DecodeEngine(page_pool=N, share_pages=True) " \
+            "(or prefix_cache=True)"
         self.set_stopping(None)
         self.enable_drafting(None, *(self._draft_params or ()))
         self.set_stopping(stop, 0)
@@ -1663,7 +1752,8 @@ class DecodeEngine:
             if rows:
                 before = len(self.prefix) if self.prefix is not None else 0
                 self.admit(rows, [q["prompt"] for q in batch], max_new_tokens=[q["max_new"] for q in batch],
-                           text_start=[q["start"] for q in batch], chunk=chunk)
+                           text_start=[q["start"] for q in batch], chunk=chunk,
+                           copy_rows=[sched.copy_rows.get(b, []) for b in rows] if sched.copy_rows else None)
                 if self.prefix is not None:
                     sched.stats["inserted_pages"] += len(self.prefix) - before
             if sched.idle():

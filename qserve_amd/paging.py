@@ -10,10 +10,11 @@ rows' pages to new texts, without the host reading a length.
                   release      push the masked rows' pages back and point their table entries at the sink (counted: give up their
                                holds, and the cache's `drop_ids`; a page is pushed when its last holder lets go);
                   hold         (counted) map pages that have a holder into further rows, and take the cache's holds;
+                  fork         (counted) branch rows off running texts: share the whole pages, copy the partly filled one;
                   free_pages, snapshot, check.
     SINK          page N of every pool tensor: what a table entry names that names no owned page.
 
-include/qserve_amd.h (`qs_pages_reserve`, `qs_pages_release`; `qs_pages_reserve_refs`, `qs_pages_hold`, `qs_pages_unhold`) has the rules, in exact integers.  Backed by qserve_amd/csrc/page_pool.hip.
+include/qserve_amd.h (`qs_pages_reserve`, `qs_pages_release`; `qs_pages_reserve_refs`, `qs_pages_hold`, `qs_pages_unhold`, `qs_pages_fork`) has the rules, in exact integers.  Backed by qserve_amd/csrc/page_pool.hip.
 DecodeEngine(page_pool=N) puts a pool under the engine."""
 import torch
 
@@ -157,6 +158,36 @@ class PagePool:
             check(lib.qs_pages_hold(*self._state(), ptr(self.refs), ptr(self._scratch), ptr(take), ptr(src), ptr(held), n, self.B, self.mb,
                                     self.L, self.N, self.page_bytes, stream()), what)
 
+    def fork(self, src_rows, lengths, finished=None):
+        """Branch rows off running texts: `src_rows` is int32 [B] on the device - src_rows[d] >= 0 makes row d a destination of that row,
+        negative leaves it alone - or a host dict dst -> src, uploaded once; `lengths` (int32 [B]) are the texts' lengths.  A destination
+        (which must own nothing, and whose source must be no destination) shares the source's whole pages below slot lengths - 1, where
+        every writer of either text writes from now on, and gets a fresh page with a copy of the partly filled one; it is refused -
+        `starved`, and `finished` = stopping.NO_PAGES where it was live - when that page cannot be had or the source itself was refused
+        pages.  One call of qs_pages_fork (two launches), nothing read back."""
+        what = "paging.PagePool.fork"
+        if self.refs is None:
+            raise RuntimeError(f"{what}: the pool keeps no reference counts - PagePool(..., refcounts=True)")
+        dev = self.free.device
+        if isinstance(src_rows, dict):
+            rows = torch.full((self.B,), -1, dtype=torch.int32)
+            for d, s in src_rows.items():
+                d, s = int(d), int(s)
+                if not 0 <= d < self.B or not 0 <= s < self.B or d == s:
+                    raise RuntimeError(f"{what}: row {d} <- row {s} - rows are 0 .. {self.B - 1}, and no row is its own source")
+                rows[d] = s
+            src_rows = rows.to(dev)
+        _rows(src_rows, torch.int32, (self.B,), "src_rows", dev, what)
+        _rows(lengths, torch.int32, (self.B,), "lengths", dev, what)
+        if finished is not None:
+            _rows(finished, torch.int32, (self.B,), "finished", dev, what)
+        for t, name in ((src_rows, "src_rows"), (lengths, "lengths"), (finished, "finished")):
+            if t is not None:
+                expect(t, torch.int32, name)
+        with guard(self.free):
+            check(lib.qs_pages_fork(*self._state(), ptr(self.refs), ptr(src_rows), ptr(lengths), ptr(finished), self.B, self.mb, self.L,
+                                    self.N, self.page_bytes, stream()), what)
+
     def rows_mask(self, rows):
         """int32 [B] on the device with ones at the row indices `rows` - what `release` takes."""
         rows = [int(r) for r in rows]
@@ -187,7 +218,9 @@ class PagePool:
                                "max_blocks, a page id outside 0 .. N - 1, or more pages released than the pool has) and changed nothing" +
                                ("" if self.refs is None else
                                 "; or, with reference counts: a popped page that has holders, a hold of a free page, into a row that owns "
-                                "pages or of more than max_blocks pages, an id twice in hold_ids, more holds given up than a page has"))
+                                "pages or of more than max_blocks pages, an id twice in hold_ids, more holds given up than a page has; a fork off a "
+                                "row outside the batch, off itself or off a destination of the same launch, into a row that owns pages, or "
+                                "off a row that names a free page"))
         if starved and bool(state[1:].any()):
             rows = torch.nonzero(state[1:]).view(-1).tolist()
             raise RuntimeError(f"paging.PagePool: rows {rows} were refused pages (the pool of {self.N} pages is exhausted): what they wrote "

@@ -87,6 +87,17 @@ class PrefixCache:
                 assert n.rows >= 1, f"prefix.PrefixCache.row_released: page {n.page} has no row holder"
                 n.rows -= 1
 
+    def row_held(self, ids):
+        """One row holder more for each of these pages that the cache knows (the others are skipped) - the inverse of `row_released`:
+        what a row is told that maps another row's pages without a `match` (a fork).  -> the ids it counted."""
+        held = []
+        for i in ids:
+            n = self.by_page.get(int(i))
+            if n is not None:
+                n.rows += 1
+                held.append(n.page)
+        return held
+
     def _blocked(self, keep):
         """The nodes that leaf-first eviction cannot reach: held by a row or named in `keep`, and every ancestor of such a node."""
         blocked = set()
