@@ -252,4 +252,7 @@ def named_cases():
         # the scan crosses a wave, the workgroup's stride
         "wave": (70, 4, 2, 150, [_reserve(wide(70), 1), _release(_i32(np.arange(70) % 3 == 0)), _reserve(wide(70) + 60, 12)]),
         "stride": (300, 4, 2, 700, [_reserve(wide(300), 1), _release(_i32(np.arange(300) % 3 == 1)), _reserve(wide(300) + 60, 12)]),
+        # a chunk of the row loop exactly full; the largest batch the entries take: four chunks, the carry crosses three boundaries
+        "chunk": (256, 4, 2, 600, [_reserve(wide(256), 1), _release(_i32(np.arange(256) % 3 == 1)), _reserve(wide(256) + 60, 12)]),
+        "full": (1024, 4, 2, 2400, [_reserve(wide(1024), 1), _release(_i32(np.arange(1024) % 3 == 1)), _reserve(wide(1024) + 60, 12)]),
     }

@@ -279,6 +279,9 @@ def named_cases():
         # the scans cross a wave, the workgroup's stride
         "wave": _wide(70),
         "stride": _wide(300),
+        # a chunk of the row loop exactly full; the largest batch the entry takes: four chunks, the carry crosses three boundaries
+        "chunk": _wide(256),
+        "full": _wide(1024),
         # ---- broken invariants: the last op fails
         "source_out_of_range": (*B0, [_TWO, _fork(5, {2: 5}, {0: 70})]),
         "self_fork": (*B0, [_TWO, _fork(5, {2: 2}, {2: 1})]),

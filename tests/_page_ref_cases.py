@@ -320,6 +320,9 @@ def named_cases():
         # the scans cross a wave, the workgroup's stride; N = 700: more freed pages than the workgroup has threads
         "wave": (70, 4, 2, 150, _wide_ops(70, 150)),
         "stride": (300, 4, 2, 700, _wide_ops(300, 700)),
+        # a chunk of the row loop exactly full; the largest batch the entries take: four chunks, the carry crosses three boundaries
+        "chunk": (256, 4, 2, 600, _wide_ops(256, 600)),
+        "full": (1024, 4, 2, 2400, _wide_ops(1024, 2400)),
         "many_freed": (300, 4, 2, 700, [_reserve(_i32([129] * 300), 1), _hold(300, 4, {}, range(698, -1, -7)),
                                         _unhold(_i32(np.ones(300)), range(5, 699, 7))]),
         # ---- broken invariants: the last op fails

@@ -91,7 +91,7 @@ def test_a_starved_source_refuses_its_destinations_without_an_error():
 
 
 def test_the_wide_cases_cross_a_wave_and_the_stride_and_run_out_of_pages():
-    for name, B in (("wave", 70), ("stride", 300)):
+    for name, B in (("wave", 70), ("stride", 300), ("chunk", 256), ("full", 1024)):
         states, ops = _last(name)
         st = states[2]
         dests = np.nonzero(ops[1]["src_rows"] >= 0)[0]

@@ -75,7 +75,7 @@ def test_a_reserve_grows_behind_a_hold():
 
 
 def test_the_wide_cases_end_with_every_page_free():
-    for name in ("wave", "stride", "many_freed"):
+    for name in ("wave", "stride", "chunk", "full", "many_freed"):
         st = _run(*R.named_cases()[name])[-1]
         assert st["count"] == st["N"] and not st["refs"].any(), name
     # many_freed: 233 rows of 3 pages; the rows' pages come back in row order, a cached one too (its drop comes later in H)
