@@ -1093,6 +1093,55 @@ int qs_pages_fork(int32_t* free_list, int32_t* count, int32_t* page_ids, int32_t
                   const int32_t* lengths, int32_t* finished, int batch, int max_blocks, int num_layers, int num_pages, int64_t page_bytes,
                   qs_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Beam search (no reference counterpart): the W best continuations of every group of W rows of a fixed batch, and the in-place move of
+ * the rows whose text changes - on the device: capturable, nothing allocated, nothing read back, no scratch.
+ *
+ * qs_beam_select.  logits fp16 [batch, n_vocab] with row stride row_stride (elements), as the head left them (penalised, masked); cum
+ * float [batch], the score of every row's text; finished int32 [batch]; tokens int64 [batch], every row's current token; width W,
+ * 1 .. 32, batch % W == 0: rows g * W .. g * W + W - 1 form group g.  Outputs: parent int32 [batch] (absolute row indices), next_token
+ * int64 [batch], cum_out float [batch] (must not alias cum), moved int32 [batch] or null (1 where parent[d] != d), src_rows int32 [batch]
+ * or null (parent[d] where moved, else -1: what qs_pages_fork takes), and the candidate workspace cand_ids int32 [batch, W], cand_lp
+ * float [batch, W], an output too.  TWO launches on the stream.
+ *
+ * A row b is DEAD iff cum[b] == -inf, FROZEN iff it is not dead and finished[b] != 0, LIVE otherwise.
+ *
+ * Launch 1, one workgroup of 1024 threads per row: a live row writes into cand_ids[b, :] / cand_lp[b, :] the top list qs_logprob_rows
+ * defines for top = W at T = 1 - (key descending, index ascending), only logits other than -inf, the tail id -1 / lp -inf - with the
+ * same operations in the same order: ids and lp are BIT-IDENTICAL to what qs_logprob_rows writes for that row.  A dead or frozen row
+ * reads no logit and writes ids -1 / lp -inf.
+ *
+ * Launch 2, one wave per group, integer operations and single fp32 operations rounded on their own; no atomics.  The CANDIDATES of a
+ * group: for a live row b every (b, r) with cand_ids[b, r] >= 0, score = cum[b] + cand_lp[b, r] (one fp32 add), token = cand_ids[b, r];
+ * for a frozen row b the one candidate (b, 0) with score = cum[b], token = tokens[b].  A candidate whose score is -inf (or NaN) is
+ * dropped.  Order: score descending as fp32 values (-0 equals +0), then row ascending, then r ascending.  The first min(W, count)
+ * candidates are CHOSEN.  Slots: for every row p with a chosen candidate, p's first chosen candidate takes slot p; the remaining chosen
+ * candidates, in order, take the slots of the rows without one, in ascending row order.  Slot d with a candidate (p, token, score):
+ * parent[d] = p, next_token[d] = token, cum_out[d] = score; a slot left over: parent[d] = d, next_token[d] = tokens[d], cum_out[d] =
+ * -inf.  So every source of a move is a row that stays: parent[parent[d]] == parent[d] - moved / src_rows meet what qs_pages_unhold
+ * followed by qs_pages_fork ask of a mask and its sources, and where every row keeps one child nothing moves.
+ * Rows with NaN, +inf or no finite logit are the caller's error; the call still ends.  The result is a function of the inputs alone:
+ * bit-identical run to run and eager against graph replay.
+ *
+ * QS_EINVAL before any device call: logits, cum, finished, tokens, parent, next_token, cum_out, cand_ids or cand_lp null; width outside
+ * 1 .. 32; batch < 0 or > 65 535 or not a multiple of width; n_vocab < 8 or > 2^22, row_stride < n_vocab or not a multiple of 8; cum_out
+ * == cum; logits not 16-byte, an int64 array not 8-byte, an int32 / float array not 4-byte aligned.  batch == 0: QS_OK, no launch.
+ *
+ * qs_rows_move.  parent int32 [batch]; bases / row_bytes: HOST arrays of `num` (0 .. 16) device base addresses and row sizes in bytes
+ * (1 .. 2^31) - tensor i is [batch] rows of row_bytes[i] bytes at bases[i]; they travel by value in the kernel argument; error int32
+ * [1].  ONE launch, a grid over (tensor, row): for every tensor and every row d with p = parent[d] != d, the bytes of row d become the
+ * bytes of row p - 16-byte vectors where the base and the row size are multiples of 16, bytes otherwise.  A p outside 0 .. batch - 1,
+ * or with parent[p] != p (a source that is itself a destination), sets error[0] = 1 and row d is skipped in every tensor: no address
+ * is formed from an unchecked index, and since every source stays the move needs no staging.  Vector stores only; no scratch.
+ * QS_EINVAL before any device call: parent or error null or not 4-byte aligned; batch < 0 or > 65 535; num outside 0 .. 16; bases or
+ * row_bytes null with num > 0; a null base; a row size outside 1 .. 2^31.  batch == 0 or num == 0: QS_OK, no launch.
+ * ---------------------------------------------------------------------------------------------------------- */
+int qs_beam_select(const void* logits, int64_t row_stride, int n_vocab, const float* cum, const int32_t* finished, const int64_t* tokens,
+                   int batch, int width, int32_t* parent, int64_t* next_token, float* cum_out, int32_t* moved, int32_t* src_rows,
+                   int32_t* cand_ids, float* cand_lp, qs_stream_t stream);
+int qs_rows_move(const int32_t* parent, int batch, const void* const* bases, const int64_t* row_bytes, int num, int32_t* error,
+                 qs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,7 @@ import qserve_backend.layernorm_ops as layernorm_ops
 import qserve_backend.qgemm_w4a8_per_chn as gemm_chn
 import qserve_backend.qgemm_w4a8_per_group as gemm_grp
 
+from . import beams as beamsmod
 from . import constraints as constraintsmod
 from . import drafting as draftingmod
 from . import fused as fusedmod
@@ -406,6 +407,10 @@ class DecodeEngine:
         # place; set_lora: True while lora_rows runs behind the four linears of every layer; the step's workspace
         self.lora_table = self.lora_ids = self._lora_step_ws = None
         self._lora = False
+        # set_beams: the group width while the step regroups (None: off), the final ranking's length penalty, and the round's persistent
+        # tensors (`_beam`: a namespace; `beam_score` float32 [B]: the sum of every row's text)
+        self.beams = self._beam = self.beam_score = self.beam_parent = None
+        self._beam_penalty = 1.0
 
     def _single_gpu(self, what):
         """What every entry behind the un-cut fp16 lm_head asks for (sampling, penalties, shared prefixes, tree verification, drafting):
@@ -474,6 +479,7 @@ class DecodeEngine:
         diverge under sampling and stay identical under greedy decoding.  Needs a counted pool (share_pages=True or prefix_cache=True)
         and enable_drafting; single GPU, with the lm_head."""
         self._forkable("fork")
+        self._no_beams("fork", "the round itself decides which rows continue which texts")
         B = self.B
         src, rows = int(src), [int(r) for r in rows]
         assert 0 <= src < B and rows and len(set(rows)) == len(rows) and all(0 <= r < B for r in rows) and src not in rows, \
@@ -497,6 +503,93 @@ class DecodeEngine:
             self.pager.release(torch.zeros((self.B,), dtype=torch.int32, device=self.dev), ids)
         return ids
 
+    # ---- beam search (qserve_amd.beams, csrc/beam_select.hip) ------------------------------------------------------------------------
+    def _no_beams(self, what, why):
+        """What the entries refuse that cannot run while set_beams is on."""
+        assert self.beams is None, f"{what}: beam search is on (set_beams) - {why}; set_beams(None) first"
+
+    def set_beams(self, width, length_penalty=1.0):
+        """Make step() / capture() / run() / generate() one round of beam search over groups of `width` rows: rows g * width ..
+        g * width + width - 1 are the hypotheses of one text.  Behind the unchanged head (logits, penalties, the constraint's mask; no
+        arg-max) `beams.select` picks per group the `width` best (row, token) continuations by `beam_score` + log-probability,
+        `beams.move_rows` moves the per-row text state (lengths, history, prompt_lens, limit_lens, finished, fsm_state, lora_ids) of the
+        rows that got another parent, in place, and the existing pool entries regroup the cache: `paging.PagePool.release(moved)`, then
+        `paging.PagePool.fork(src_rows, lengths + 1)` - the whole pages shared, the tail page copied.  A row with a surviving child
+        keeps its best child in place, so every source of a move stays, and where every beam keeps one child nothing moves.  A
+        destination that is refused its tail page ends with finished = NO_PAGES and score -inf: the hypothesis is dropped.  A finished
+        row stays in its group as a frozen row and competes with its raw sum; `length_penalty` ranks only at the end (`beam_search`).
+        Everything lives in persistent device tensors: the round is captured like any other step, and `beams=width` is part of what a
+        capture freezes.  `beam_score` float32 [B] is cleared to 0 by this call: every row starts as a hypothesis of its own text;
+        admit() under beams starts whole groups from one prompt.
+
+        Needs: single GPU with the lm_head; a counted pool without a prefix cache (share_pages=True) - the prefix cache's host record of
+        held pages cannot follow a device-side regroup -; enable_drafting; set_stopping on; B % width == 0; sampling and set_logprobs
+        off.  While on, set_sampling, set_logprobs, fork, serve, the prefill entries and the tree entries (verify_tree, speculate, their
+        captures) refuse.  set_beams(None) switches it off: every path launches exactly what it launches without this call."""
+        if width is None:
+            self.beams = None
+            return
+        self._forkable("set_beams")
+        width = int(width)
+        assert self.prefix is None, \
+            "set_beams: the engine has a prefix cache, whose host record of the pages every row holds cannot follow a regroup on the " \
+            "device - DecodeEngine(page_pool=N, share_pages=True) without prefix_cache"
+        assert self.stopping is not None, "set_beams: set_stopping first (finished rows stay in their group as frozen rows, and nothing else ends the search)"
+        assert 1 <= width <= beamsmod.MAX_WIDTH and self.B % width == 0, \
+            f"set_beams: width={width} (1 .. {beamsmod.MAX_WIDTH}) must divide the batch of {self.B} rows: rows g * width .. form group g"
+        assert self.sampling is None, "set_beams: sampling is on - beams are chosen by score, not drawn; set_sampling(None) first"
+        assert self._logprobs is None, "set_beams: set_logprobs is on - the logs do not follow a regroup; set_logprobs(None) first"
+        assert self.cfg["vocab"] >= 8 and self.cfg["vocab"] % 8 == 0, "set_beams: the logit rows need a vocabulary that is a multiple of 8"
+        B, dev = self.B, self.dev
+        if self._beam is None or self._beam.cand_ids.size(1) != width:
+            i32, f32 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float32, device=dev)
+            self._beam = SimpleNamespace(
+                score_out=torch.zeros((B,), **f32), parent=torch.zeros((B,), **i32), next_token=torch.zeros((B,), dtype=torch.int64, device=dev),
+                moved=torch.zeros((B,), **i32), src_rows=torch.full((B,), -1, **i32), cand_ids=torch.full((B, width), -1, **i32),
+                cand_lp=torch.zeros((B, width), **f32), lens=torch.zeros((B,), **i32))
+        if self.beam_score is None:
+            self.beam_score = torch.zeros((B,), dtype=torch.float32, device=dev)
+        self.beam_score.zero_()
+        self.beam_parent = self._beam.parent                                # (the last round's parents, for callers that follow the regroup)
+        self.beams, self._beam_penalty = width, float(length_penalty)
+
+    def _beam_moved_tensors(self):
+        """The per-row text state that the launches behind the regroup read (those that exist); `tokens` is written from the
+        selection, `hidden` / `final` are derived from it by the next step."""
+        return [t for t in (self.lengths, self.history, self.prompt_lens, self.limit_lens, self.finished, self.fsm_state, self.lora_ids)
+                if t is not None]
+
+    def _beam_round(self, logits):
+        """The regroup of one beam round, between the head and the tail of step(): select, move, unhold, fork, and the new tokens and
+        scores - nothing read back.  Slot lengths - 1 was written by this step and belongs to the child: the fork is
+        told lengths + 1, so its rule w = (len - 1) / 64, t = (len - 1) % 64 carries that slot."""
+        bm = self._beam
+        torch.add(self.lengths, 1, out=bm.lens)
+        beamsmod.select(logits, self.beam_score, self.finished, self.tokens, self.beams,
+                        out=(bm.parent, bm.next_token, bm.score_out, bm.moved, bm.src_rows, bm.cand_ids, bm.cand_lp))
+        beamsmod.move_rows(bm.parent, self._beam_moved_tensors(), self.pager.error)
+        self.pager.release(bm.moved)
+        self.pager.fork(bm.src_rows, bm.lens, finished=self.finished)
+        # a destination that was refused its tail page holds nothing (finished = NO_PAGES by the fork): its hypothesis is dropped
+        bm.score_out.masked_fill_((bm.moved != 0) & (self.pager.starved != 0), float("-inf"))
+        self.beam_score.copy_(bm.score_out)
+        self.tokens.copy_(bm.next_token)
+
+    def beam_search(self, max_rounds, poll_every=8):
+        """generate() under set_beams, and the final ranking: per group the hypotheses that are alive (score above -inf), best first by
+        `beams.rank` - score / max(generated tokens, 1) ** length_penalty in float64, ties by row.
+        -> (groups: per group a list of (tokens, cum_score, final_score, reason) - the generated tokens as generate() returns them, the
+        raw sum, the ranked score, `finished` -; rounds; read_backs)."""
+        assert self.beams is not None, "beam_search: set_beams first"
+        texts, reasons, rounds, reads = self.generate(max_rounds, poll_every=poll_every)
+        cum = self.beam_score.cpu().tolist()
+        W, groups = self.beams, []
+        for g in range(self.B // W):
+            rows = list(range(g * W, g * W + W))
+            order, scores = beamsmod.rank([cum[b] for b in rows], [len(texts[b]) for b in rows], self._beam_penalty)
+            groups.append([(texts[rows[i]], cum[rows[i]], scores[i], reasons[rows[i]]) for i in order if cum[rows[i]] != float("-inf")])
+        return groups, rounds, reads
+
     # ---- the sampling head (qserve_amd.sampling, csrc/sample_rows.hip) --------------------------------------------------------
     def set_sampling(self, temperature, top_k=0, top_p=1.0, seed=0):
         """Make the head of step() / capture() / run(), of the prefill entries and of verify_tree(sampled=True) draw from the
@@ -510,6 +603,7 @@ class DecodeEngine:
         if temperature is None:
             self.sampling = None
             return
+        self._no_beams("set_sampling", "beams are chosen by score, not drawn (sampled beams are out of scope)")
         self._single_gpu("set_sampling")
         from .append import MAX_TREE
         if self._samp_t is None:
@@ -533,7 +627,7 @@ class DecodeEngine:
         """The keys of the tokens the head is about to draw: (b, lengths[b]) - the position the new token will hold."""
         return samplingmod.position_keys(self._samp_ids, self.lengths)
 
-    def _head(self, final, out, keys=None, draft=(), penalise=True):
+    def _head(self, final, out, keys=None, draft=(), penalise=True, choose=True):
         """The head of every path but the vocabulary-parallel one: the un-quantised fp16 lm_head on the normed rows `final`
         (llama_w4a8_unpad.py:392,476), the penalty launch while set_penalties is on (`draft`: the drafted tokens and the tree of a
         verification; a step's context is the text alone; the prefill entries and the host-walk verify_tree refuse to run while penalties
@@ -541,12 +635,15 @@ class DecodeEngine:
         token before the new text's history is complete), then out[r] = the arg-max of row r or, with `keys`, the token drawn under the
         Philox keys keys() - computed behind the logits, from the lengths as they stand then.  While set_constraint is on the mask
         launch runs behind the penalties: every row under the automaton state of its own node - `fsm_state` for a step and for the
-        prompt head, the states along the draft's paths for a verification.  -> the logits (penalised and masked, while on)."""
+        prompt head, the states along the draft's paths for a verification.  `choose=False`: no token is chosen, `out` is not written.
+        -> the logits (penalised and masked, while on)."""
         logits = torch.matmul(final, self.lm_head.t())
         if penalise and self.penalties is not None:
             self._penalize(logits, *draft)
         if self._fsm is not None:
             self._constrain(logits, *draft)
+        if not choose:                                               # (set_beams: the round chooses over groups of rows, behind the head)
+            return logits
         if keys is not None:
             self._sample(logits, out, keys())
         else:
@@ -717,6 +814,7 @@ class DecodeEngine:
     def _prefill_entry(self, what):
         """What every prefill entry refuses BEFORE it touches the cache: penalties on - the head of a prefill draws its token before
         the new prompt's history exists, so it could not penalise."""
+        self._no_beams(what, "a beam's first tokens are chosen by admit() over whole groups")
         assert self.penalties is None, \
             f"{what}: the prefill head does not penalise (the history of the new prompt does not exist yet) - set_penalties(None), " \
             "prefill, enable_drafting, then set_penalties again"
@@ -746,7 +844,14 @@ class DecodeEngine:
             self._head_finish(self.head_cand)
         else:
             keys = (lambda: samplingmod.position_keys(self._samp_ids, pos)) if self.sampling is not None else None
-            logits = self._head(final, out, keys, penalise=False)
+            beam = self.beams is not None and rows is not None       # (admit under set_beams; the prefill entries refuse)
+            logits = self._head(final, out, keys, penalise=False, choose=not beam)
+            if beam:                                                 # a group's first tokens: the leader's W best, slot i the i-th
+                cum = torch.full((self.B,), float("-inf"), dtype=torch.float32, device=self.dev)
+                cum[rows[rows % self.beams == 0]] = 0.0              # the followers are copies of the leader: only it has candidates
+                res = beamsmod.select(logits, cum, torch.zeros_like(pos), out, self.beams)
+                out.copy_(res[1])
+                self.beam_score[rows] = torch.index_select(res[2], 0, rows)
             if self._logprobs is not None:                           # a new text: the first token's entry lands at column prompt_len
                 self._clear_logprob_logs(rows)
             self._emit(logits, out, lengths=pos, k=k)                # (a prefill entry: stopping is off, by _prefill_entry)
@@ -1258,6 +1363,7 @@ class DecodeEngine:
         if top is None:
             self._logprobs = None
             return
+        self._no_beams("set_logprobs", "the logs are indexed by row and text position and do not follow a regroup (`beam_score` is the sum)")
         self._single_gpu("set_logprobs")
         top = int(top)
         assert 0 <= top <= logprobsmod.MAX_TOP, f"set_logprobs: top={top} (0 .. {logprobsmod.MAX_TOP})"
@@ -1440,10 +1546,10 @@ class DecodeEngine:
     def _capture_state(self):
         """What a capture freezes besides its own arguments, and generate() compares: whether the stop launch exists, the state of
         set_logprobs, the automaton whose tables are on - set_constraint uploads them once per TokenDFA object, so the object stands for
-        the tables and compares by identity -, whether the LoRA launches exist.  (Frozen too, and not in it: whether the head samples or
+        the tables and compares by identity -, whether the LoRA launches exist, the beam width (None: the step takes the arg-max).  (Frozen too, and not in it: whether the head samples or
         penalises.)"""
         return dict(stops=self.stopping is not None, logprobs=self._logprobs, automaton=None if self._fsm is None else self._fsm_src,
-                    lora=self._lora)
+                    lora=self._lora, beams=self.beams)
 
     def _kept_tensors(self):
         """Every persistent tensor a captured graph may touch and a later call may replace, by feature (None while the feature is off)."""
@@ -1452,7 +1558,8 @@ class DecodeEngine:
                     logprobs=None if self._logprobs is None else (self.logprob_log, self.rank_log, self.top_ids_log, self.top_lp_log,
                                                                   self._samp_t),
                     constraint=None if self._fsm is None else (self._fsm, self.fsm_state, self._fsm_node_state),
-                    lora=(self.lora_table, self.lora_ids, self._lora_step_ws) if self._lora else None)
+                    lora=(self.lora_table, self.lora_ids, self._lora_step_ws) if self._lora else None,
+                    beams=None if self.beams is None else (self.beam_score, *vars(self._beam).values()))
 
     def _captured(self, captured, n, *buffers, **own):
         """The record of the graph `_capture` just returned as `captured`: `graph`; `result`: what the captured call returned, tensors
@@ -1552,7 +1659,12 @@ class DecodeEngine:
         prompt's whole pages into the followers and copies the partly filled one (lengths P_r + 1: slot P_r is the first one a
         follower writes), and the head runs ONCE over leaders and followers, on the leaders' last hidden rows: every row draws its
         own first token under key (its row, P_r).  Texts, limits, states, adapters, cleared logs and the root check cover all of them.
-        All rows, leaders and followers, must be distinct."""
+        All rows, leaders and followers, must be distinct.
+
+        Under set_beams every prompt starts one whole group: its leader is row g * W, its copy_rows the group's other rows in order.
+        In place of the draw, `beams.select` runs over the head's rows with score 0 at the leaders and -inf at every other row: slot i of
+        the group gets the leader's i-th best first token and its log-probability as `beam_score`.  All parents are the leader, whose
+        copies the followers already are: nothing moves."""
         self._single_gpu("admit")
         assert self.prefix is None or not self._lora, \
             "admit: the engine has a prefix cache and LoRA is on (set_lora) - K / V under an adapter differ from the base model's, and a " \
@@ -1571,6 +1683,12 @@ class DecodeEngine:
             rows = rows + [r for c in copies for r in c]
             assert len(set(rows)) == len(rows) and all(0 <= r < B for r in rows), \
                 f"admit: rows and copy_rows {rows} - distinct row indices in 0 .. {B - 1} overall"
+        if self.beams is not None:                                           # a prompt starts one whole group: its first tokens are the W best
+            W = self.beams
+            groups = [[r] + (copies[i] if copy_rows is not None else []) for i, r in enumerate(rows[:R])]
+            assert all(g == list(range(g[0], g[0] + W)) and g[0] % W == 0 for g in groups), \
+                f"admit: beam search is on (set_beams({W})) - every prompt starts one whole group: its row g * {W} in `rows`, the group's " \
+                f"other rows, in order, as its copy_rows; got {groups}"
         pl = [torch.as_tensor(p).to("cpu", torch.int64) for p in prompts]
         assert len(pl) == R and all(p.dim() == 1 for p in pl), f"admit: one 1-D token sequence per row ({R})"
         Ps = [p.numel() for p in pl]
@@ -1665,6 +1783,9 @@ class DecodeEngine:
             last, P_t = torch.index_select(last, 0, lead_t), P_t[lead_t]
         # ---- the head and the tail over the admitted rows, then what they leave to the text
         self._prompt_head(last, P_t, all_t)
+        if self.beams is not None and self.pager is not None:               # a row that was refused pages holds no text: no hypothesis
+            self.beam_score.masked_fill_(torch.zeros((B,), dtype=torch.bool, device=dev).index_fill_(0, all_t, True) &
+                                         (self.pager.starved != 0), float("-inf"))
         self.history[all_t, P_t.to(torch.int64)] = torch.index_select(self.tokens, 0, all_t).to(torch.int32)
         self._len_bound = max(self._len_bound, maxP + 1)
         if self.stopping is not None:                                       # the root check of set_stopping: a first token that is a
@@ -1696,6 +1817,7 @@ class DecodeEngine:
         tokens it held at each preemption), stats dict(rounds, read_backs, admitted, preempted, peak_pages: the most pages in use at a
         read-back - the static batch * mb without a pool))."""
         self._single_gpu("serve")
+        self._no_beams("serve", "its scheduler admits and releases single rows, a beam group lives and ends as a whole")
         assert poll_every >= 1
         B, dev = self.B, self.dev
         adv = 1 if parents is None else len(self._tree_arg(parents, "serve", drafting=False))
@@ -1780,6 +1902,7 @@ class DecodeEngine:
         from . import append as appendmod
         par = [int(p) for p in (parents.tolist() if hasattr(parents, "tolist") else parents)]
         self._single_gpu(what)
+        self._no_beams(what, "beams under speculation are out of scope: a verification keeps one path per row")
         assert 1 <= len(par) <= appendmod.MAX_TREE and par[0] == -1 and all(0 <= p < i for i, p in enumerate(par) if i), \
             f"{what}: parents[0] = -1 (the root), every other node hangs off an earlier one; at most 64 nodes"
         assert not drafting or self.history is not None, f"{what}: enable_drafting first"
@@ -1850,7 +1973,9 @@ class DecodeEngine:
             yield self._head_local()                                 # candidates of the ranks meet in the sum all-reduce
             self._head_finish(self.head_cand_res)
         elif self.with_lm_head:                                      # (penalty context: history[b, :lengths[b]], the text so far)
-            logits = self._head(self.final, self.tokens, self._step_keys if self.sampling is not None else None)
+            logits = self._head(self.final, self.tokens, self._step_keys if self.sampling is not None else None, choose=self.beams is None)
+            if self.beams is not None:
+                self._beam_round(logits)
         k = self._emit(logits, self.tokens)                          # set_stopping: k = 0 (a stop before the new token, or a frozen row) / 1
         self.lengths.add_(1 if k is None else k)
         if self.history is not None:                                 # enable_drafting: the new token joins the text (k = 0: it does not)
