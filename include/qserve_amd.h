@@ -909,6 +909,19 @@ int qs_lora_rows(void* out, int64_t out_stride, const int8_t* x, int64_t x_strid
  * qs_moe_gemm_plan: plan4 = {mt, waves per workgroup, row blocks launched, 64-channel units} - a pure function of (P, E, N, K)
  * (csrc/moe_plan.h); every plan computes the same bits.
  *
+ * Two kernels compute a grouped GEMM, to the same bits: the weight-streaming one above (decode: few rows per expert) and a
+ * compute-bound tile (csrc/gemm_w4a8_moe_tiled.hip; prompts: many rows per expert) - a workgroup owns (expert, 128 sorted rows, 256
+ * channels) and stages both operands through LDS in stages of 64 k, gathering the rows through row_src in its DMA addresses; its grid is
+ * the bound ceil(P / 128) + E - 1 row blocks x N / 256 channel tiles.  The two entries above take the form qs_moe_gemm_form names -
+ * tiled needs N % 256 == 0, K >= 256, 32-bit offsets (x_rows * x_stride and one expert's N * K / 2 below 2^32) and ceil(P / E) at
+ * least the measured threshold of csrc/moe_plan.h - and fall back to streaming where the strides given do not fit.
+ * qs_w4a8_per_chn_moe_gemm_tiled / qs_w4a8_per_group_moe_gemm_tiled: the same argument lists and rules, always the tile, for any
+ * P >= 1; QS_EINVAL in addition where N is not a multiple of 256, K < 256 or an offset does not fit.  P == 0: QS_OK, no launch.
+ * qs_moe_gemm_tiled_plan: plan4 = {sorted rows per tile, channel tiles, row blocks launched, stages of 64 k}; QS_EINVAL where (N, K) is
+ * not the tile's.  qs_moe_gemm_form: *form = 0 (streaming) or 1 (tiled).  Both are pure functions of (P, E, N, K).
+ * qs_set_moe_gemm_form (process-wide test / measurement hook, see qs_set_gemm_variant): -1 [default] = the planner's choice, 0 = the
+ * two plain entries always stream, 1 = they take the tile wherever it serves.  Results never change.  qs_get_moe_gemm_form reads it.
+ *
  * qs_moe_combine (csrc/moe_route.hip): out[t, :] = half(sum_j weights[t, j] * float(y[pair_pos[t, j], :])) for t < T: float32, j
  * ascending, the first product alone and each further one added to it, multiply and add rounded separately (no contraction), one
  * rounding to fp16.  y fp16 [T k, N] / out fp16 [T, N] with row strides; pair_pos values are clamped into [0, T k - 1].
@@ -926,6 +939,17 @@ int qs_w4a8_per_chn_moe_gemm(const int8_t* x, int64_t x_stride, int x_rows, cons
 int qs_w4a8_per_group_moe_gemm(const int8_t* x, int64_t x_stride, int x_rows, const int32_t* row_src, const int32_t* expert_offsets,
                                const int8_t* qweight, const int8_t* zeros, const int8_t* scales_i8, const void* wscales,
                                const void* ascales, void* out, int64_t out_stride, int P, int E, int N, int K, qs_stream_t stream);
+int qs_moe_gemm_tiled_plan(int P, int E, int N, int K, int* plan4);
+int qs_moe_gemm_form(int P, int E, int N, int K, int* form);
+int qs_set_moe_gemm_form(int form);
+int qs_get_moe_gemm_form(void);
+int qs_w4a8_per_chn_moe_gemm_tiled(const int8_t* x, int64_t x_stride, int x_rows, const int32_t* row_src, const int32_t* expert_offsets,
+                                   const int8_t* qweight, const void* wscales, const void* ascales, const void* w_szs,
+                                   const void* a_ssums, void* out, int64_t out_stride, int P, int E, int N, int K, qs_stream_t stream);
+int qs_w4a8_per_group_moe_gemm_tiled(const int8_t* x, int64_t x_stride, int x_rows, const int32_t* row_src,
+                                     const int32_t* expert_offsets, const int8_t* qweight, const int8_t* zeros, const int8_t* scales_i8,
+                                     const void* wscales, const void* ascales, void* out, int64_t out_stride, int P, int E, int N, int K,
+                                     qs_stream_t stream);
 int qs_moe_combine(void* out, int64_t out_stride, const void* y, int64_t y_stride, const float* weights, const int32_t* pair_pos, int T,
                    int k, int N, qs_stream_t stream);
 

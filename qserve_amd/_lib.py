@@ -104,6 +104,12 @@ SIGNATURES = {
     "qs_moe_gemm_plan": (_i, [_i, _i, _i, _i, _vp]),
     "qs_w4a8_per_chn_moe_gemm": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
     "qs_w4a8_per_group_moe_gemm": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
+    "qs_moe_gemm_tiled_plan": (_i, [_i, _i, _i, _i, _vp]),
+    "qs_moe_gemm_form": (_i, [_i, _i, _i, _i, _vp]),
+    "qs_set_moe_gemm_form": (_i, [_i]),
+    "qs_get_moe_gemm_form": (_i, []),
+    "qs_w4a8_per_chn_moe_gemm_tiled": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
+    "qs_w4a8_per_group_moe_gemm_tiled": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
     "qs_moe_combine": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _i, _i, _i, _vp]),
     "qs_pages_reserve": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i, _vp]),
     "qs_pages_release": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _vp]),

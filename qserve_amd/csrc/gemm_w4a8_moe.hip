@@ -18,7 +18,7 @@
 // expert shapes, and without it there is no slab, counter or wait.  Activation rows are gathered through the per-lane row pointers.
 // Index hygiene: offsets are clamped into [0, P] and a range that runs backwards is empty; row_src values are clamped into
 // [0, x_rows - 1]: no device input moves an access outside the stated extents.
-#include "common.h"
+#include "gemm_w4a8_moe.h"
 #include "moe_plan.h"
 #include "gemm_plan.h"
 
@@ -215,19 +215,6 @@ __global__ __launch_bounds__(MT <= 2 ? 512 : 256, 2) void w4a8_moe_gemm(
     }
 }
 
-struct MoeArgs {
-    const int8_t* x;
-    int64_t x_stride;
-    int x_rows;
-    const int32_t *row_src, *offsets;
-    const int8_t *qweight, *zeros, *scales8;
-    const void *wscales, *ascales, *wszs, *assums;
-    void* out;
-    int64_t out_stride;
-    int P, E, N, K;
-    hipStream_t stream;
-};
-
 template <int MT, int MODE>
 int launch_moe(const MoeArgs& a, const moe_plan::MoePlan& pl) {
     auto kern = w4a8_moe_gemm<MT, MODE, 2>;
@@ -263,8 +250,11 @@ int require_moe_shape(int P, int E, int N, int K) {
     return QS_OK;
 }
 
+qs_flag g_moe_form = -1;   // qs_set_moe_gemm_form
+
+// form: < 0 = the planner's (moe_plan::moe_form, and the tile only where it serves the strides given), MOE_TILED = the tile or QS_EINVAL
 template <int MODE>
-int moe_gemm(const MoeArgs& a) {
+int moe_gemm(const MoeArgs& a, int form = -1) {
     if (int rc = require_moe_shape(a.P, a.E, a.N, a.K)) return rc;
     QS_REQUIRE(a.x && a.offsets && a.qweight && a.wscales && a.ascales && a.out, "w4a8 moe gemm: null pointer");
     if (MODE == 0) QS_REQUIRE(a.wszs && a.assums, "w4a8 per-channel moe gemm: null w_szs / a_ssums");
@@ -279,7 +269,15 @@ int moe_gemm(const MoeArgs& a) {
                    aligned(a.assums, 2),
                "w4a8 moe gemm: x, qweight and out must be 16-byte, the weight scales 8-byte, the level-2 scales / zeros, the offsets and "
                "row_src 4-byte, the activation scales 2-byte aligned");
+    const bool serves = moe_plan::tiled_serves(a.x_rows, a.x_stride, a.N, a.K);
+    if (form == moe_plan::MOE_TILED)
+        QS_REQUIRE(serves, "w4a8 moe gemm (tiled): N=%d must be a multiple of 256, K=%d at least 256, x_rows * x_stride = %lld and one expert's "
+                           "N * K / 2 = %lld below 2^32 (32-bit offsets)", a.N, a.K, (long long)a.x_rows * (long long)a.x_stride,
+                   (long long)a.N * a.K / 2);
     if (a.P == 0) return QS_OK;
+    const int hook = g_moe_form;   // qs_set_moe_gemm_form: the planner's choice, or one form wherever it serves
+    if (form == moe_plan::MOE_TILED || (serves && (hook < 0 ? moe_plan::moe_form(a.P, a.E, a.N, a.K) : hook) == moe_plan::MOE_TILED))
+        return qs_launch_moe_tiled(MODE, a);
     const moe_plan::MoePlan pl = moe_plan::plan_moe(a.P, a.E, a.N, a.K);
     switch (pl.mt) {
     case 1: return launch_moe<1, MODE>(a, pl);
@@ -314,4 +312,48 @@ extern "C" int qs_w4a8_per_group_moe_gemm(const int8_t* x, int64_t x_stride, int
     MoeArgs a = {x, x_stride, x_rows, row_src, expert_offsets, qweight, zeros, scales_i8, wscales, ascales, nullptr, nullptr, out, out_stride,
                  P, E, N, K, reinterpret_cast<hipStream_t>(stream)};
     return moe_gemm<1>(a);
+}
+
+// ---- the compute-bound tile (gemm_w4a8_moe_tiled.hip) behind the same checks ------------------------------------------------------------
+extern "C" int qs_moe_gemm_tiled_plan(int P, int E, int N, int K, int* plan4) {
+    QS_REQUIRE(plan4, "moe gemm tiled plan: null output");
+    for (int i = 0; i < 4; ++i) plan4[i] = 0;
+    if (int rc = require_moe_shape(P, E, N, K)) return rc;
+    QS_REQUIRE(N % moe_plan::TILED_CHANNELS == 0 && K >= 256, "moe gemm tiled plan: N=%d must be a multiple of 256, K=%d at least 256", N, K);
+    const moe_plan::MoeTiledPlan pl = moe_plan::plan_moe_tiled(P, E, N, K);
+    plan4[0] = pl.rows, plan4[1] = pl.ntiles, plan4[2] = pl.rblocks, plan4[3] = pl.stages;
+    return QS_OK;
+}
+
+extern "C" int qs_moe_gemm_form(int P, int E, int N, int K, int* form) {
+    QS_REQUIRE(form, "moe gemm form: null output");
+    *form = moe_plan::MOE_STREAMING;
+    if (int rc = require_moe_shape(P, E, N, K)) return rc;
+    *form = moe_plan::moe_form(P, E, N, K);
+    return QS_OK;
+}
+
+extern "C" int qs_set_moe_gemm_form(int form) {
+    QS_REQUIRE(form >= -1 && form <= moe_plan::MOE_TILED, "qs_set_moe_gemm_form: form %d not in {-1, 0, 1}", form);
+    g_moe_form = form;
+    return QS_OK;
+}
+extern "C" int qs_get_moe_gemm_form(void) { return g_moe_form; }
+
+extern "C" int qs_w4a8_per_chn_moe_gemm_tiled(const int8_t* x, int64_t x_stride, int x_rows, const int32_t* row_src,
+                                              const int32_t* expert_offsets, const int8_t* qweight, const void* wscales, const void* ascales,
+                                              const void* w_szs, const void* a_ssums, void* out, int64_t out_stride, int P, int E, int N, int K,
+                                              qs_stream_t stream) {
+    MoeArgs a = {x, x_stride, x_rows, row_src, expert_offsets, qweight, nullptr, nullptr, wscales, ascales, w_szs, a_ssums, out, out_stride,
+                 P, E, N, K, reinterpret_cast<hipStream_t>(stream)};
+    return moe_gemm<0>(a, moe_plan::MOE_TILED);
+}
+
+extern "C" int qs_w4a8_per_group_moe_gemm_tiled(const int8_t* x, int64_t x_stride, int x_rows, const int32_t* row_src,
+                                                const int32_t* expert_offsets, const int8_t* qweight, const int8_t* zeros,
+                                                const int8_t* scales_i8, const void* wscales, const void* ascales, void* out,
+                                                int64_t out_stride, int P, int E, int N, int K, qs_stream_t stream) {
+    MoeArgs a = {x, x_stride, x_rows, row_src, expert_offsets, qweight, zeros, scales_i8, wscales, ascales, nullptr, nullptr, out, out_stride,
+                 P, E, N, K, reinterpret_cast<hipStream_t>(stream)};
+    return moe_gemm<1>(a, moe_plan::MOE_TILED);
 }

@@ -9,7 +9,7 @@ block, qserve/modeling/models/mixtral_w4a8_unpad.py, spells the pipeline out and
     MoELinear    the stacked expert weights: qweight [E, N, K/2], s1_scales [E, N], s1_szeros [E, N] | s2_scales / s2_zeros [E, K/128, N]
 
 include/qserve_amd.h (`qs_moe_route`, `qs_w4a8_per_*_moe_gemm`, `qs_moe_combine`) has the rules; a numpy restatement is tests/_moe_cases.py.
-Backed by qserve_amd/csrc/moe_route.hip and gemm_w4a8_moe.hip.  DecodeEngine runs `moe_mlp` in place of the dense MLP for a config with
+Backed by qserve_amd/csrc/moe_route.hip, gemm_w4a8_moe.hip and gemm_w4a8_moe_tiled.hip.  DecodeEngine runs `moe_mlp` in place of the dense MLP for a config with
 `experts` / `experts_per_token`; it looks the function up per call, so a test can wrap it."""
 import ctypes
 
@@ -89,6 +89,24 @@ def gemm_plan(P, E, N, K):
     return tuple(plan)
 
 
+def gemm_tiled_plan(P, E, N, K):
+    """(sorted rows per tile, channel tiles, row blocks launched, stages of 64 k) of the compute-bound grouped tile
+    (qs_moe_gemm_tiled_plan): a pure function of the sizes; raises where the tile does not serve (N, K)."""
+    plan = (ctypes.c_int * 4)()
+    check(lib.qs_moe_gemm_tiled_plan(int(P), int(E), int(N), int(K), plan), "moe.gemm_tiled_plan")
+    return tuple(plan)
+
+
+FORMS = ("streaming", "tiled")
+
+
+def gemm_form(P, E, N, K):
+    """"streaming" or "tiled": the kernel `grouped_gemm` takes for these sizes when no form is forced (qs_moe_gemm_form): pure."""
+    form = ctypes.c_int()
+    check(lib.qs_moe_gemm_form(int(P), int(E), int(N), int(K), ctypes.byref(form)), "moe.gemm_form")
+    return FORMS[form.value]
+
+
 class MoELinear:
     """The E expert weights of one projection, each in the reference's packed W4A8 layout, stacked: qweight int8 [E, n, k/2], s1_scales
     fp16 [E, n], and s1_szeros fp16 [E, n] (per-channel, group_size -1) or s2_scales / s2_zeros int8 [E, k/128, n] (group_size 128).
@@ -132,12 +150,16 @@ class MoELinear:
         return {n: t[e] for n, t in self.tensors().items()}
 
 
-def grouped_gemm(x, x_scale, x_sum, expert_offsets, lin, out, row_src=None):
+def grouped_gemm(x, x_scale, x_sum, expert_offsets, lin, out, row_src=None, form=None):
     """out[p, :] = lin's expert e(p) applied to x[row_src[p], :] for every sorted position p < P = out's rows, e(p) the expert whose range
     of `expert_offsets` int32 [E + 1] holds p; row_src int32 [P] (None: x row p).  x int8 [rows, K] and out fp16 [P, N] may have padded
     rows (strides multiples of 16 and 8); x_scale (and, for per-channel weights, x_sum) fp16 [rows] belong to the SOURCE row.  Bit-identical
-    to the dense GEMM op on expert e's tensors and that row.  -> out."""
+    to the dense GEMM op on expert e's tensors and that row, whichever kernel computes it: form None follows the planner (`gemm_form`),
+    "streaming" / "tiled" force the weight-streaming kernel / the compute-bound tile ("tiled" raises, with the reason, on a shape the tile
+    does not serve).  -> out."""
     what = "moe.grouped_gemm"
+    if form not in (None,) + FORMS:
+        raise RuntimeError(f"{what}: form={form!r} (None, 'streaming' or 'tiled')")
     expect(x, torch.int8, "x", contiguous=False)
     expect(out, torch.float16, "out", contiguous=False)
     expect(x_scale, torch.float16, "x_scale")
@@ -175,15 +197,22 @@ def grouped_gemm(x, x_scale, x_sum, expert_offsets, lin, out, row_src=None):
     _same_device(what, out, x, x_scale, x_sum, expert_offsets, row_src, *lin.tensors().values())
     if P == 0:
         return out
+    chn, grp = (lib.qs_w4a8_per_chn_moe_gemm_tiled, lib.qs_w4a8_per_group_moe_gemm_tiled) if form == "tiled" else \
+        (lib.qs_w4a8_per_chn_moe_gemm, lib.qs_w4a8_per_group_moe_gemm)
+    hook = lib.qs_get_moe_gemm_form()
     with guard(out):
-        if per_group:
-            check(lib.qs_w4a8_per_group_moe_gemm(ptr(x), x_stride, rows, ptr(row_src), ptr(expert_offsets), ptr(lin.qweight), ptr(lin.s2_zeros),
-                                                 ptr(lin.s2_scales), ptr(lin.s1_scales), ptr(x_scale), ptr(out), out_stride, P, E, N, K,
-                                                 stream()), what)
-        else:
-            check(lib.qs_w4a8_per_chn_moe_gemm(ptr(x), x_stride, rows, ptr(row_src), ptr(expert_offsets), ptr(lin.qweight), ptr(lin.s1_scales),
-                                               ptr(x_scale), ptr(lin.s1_szeros), ptr(x_sum), ptr(out), out_stride, P, E, N, K, stream()),
-                  what)
+        try:
+            if form == "streaming":
+                check(lib.qs_set_moe_gemm_form(0), what)
+            if per_group:
+                check(grp(ptr(x), x_stride, rows, ptr(row_src), ptr(expert_offsets), ptr(lin.qweight), ptr(lin.s2_zeros), ptr(lin.s2_scales),
+                          ptr(lin.s1_scales), ptr(x_scale), ptr(out), out_stride, P, E, N, K, stream()), what)
+            else:
+                check(chn(ptr(x), x_stride, rows, ptr(row_src), ptr(expert_offsets), ptr(lin.qweight), ptr(lin.s1_scales), ptr(x_scale),
+                          ptr(lin.s1_szeros), ptr(x_sum), ptr(out), out_stride, P, E, N, K, stream()), what)
+        finally:
+            if form == "streaming":
+                lib.qs_set_moe_gemm_form(hook)
     return out
 
 
