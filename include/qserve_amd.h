@@ -869,6 +869,22 @@ int64_t qs_lora_rows_workspace(int T, int K, int r, int nseg);
 int qs_lora_rows(void* out, int64_t out_stride, const int8_t* x, int64_t x_stride, const void* x_scale, const void* A, const void* B,
                  const float* scaling, const int32_t* seq_adapter, int slots, int T, int K, int N, int r, int rows_per_seq, int nseg,
                  int seg_end0, int seg_end1, int seg_end2, void* workspace, int64_t workspace_size, qs_stream_t stream);
+/* The GROUPED form of the same update (csrc/lora_grouped.hip): the arguments, the rule, the workspace and the BITS of qs_lora_rows -
+ * element for element, so the form is a choice of cost alone -, but a tile is 16 rows of one ADAPTER, wherever they sit in the batch:
+ * the rows of adapter a are the rows t with seq_adapter[t / rows_per_seq] == a in ascending t, tile i of a is rows 16 i .. 16 i + 15
+ * of that list.  Every workgroup finds its tile from seq_adapter on the device (nothing is read back; a captured call follows ids
+ * changed in place); the grid is qs_lora_rows_grouped_tiles(T, rows_per_seq, slots) = ceil(T / 16) + min(slots, T / rows_per_seq) - 1
+ * tiles, a bound for every assignment of ids.  Rows of an id outside 0 .. slots-1 belong to no tile.  Two launches.  QS_EINVAL before
+ * any device call: what qs_lora_rows refuses, and what the planner (csrc/lora_plan.h) does not serve in this form: rows_per_seq >= 16,
+ * slots > 64, T / rows_per_seq > 16 384 sequences.
+ * qs_lora_rows_form: the form the planner takes for a call, 0 = rows (qs_lora_rows), 1 = grouped; QS_EINVAL for T outside 0 .. 2^24,
+ * rows_per_seq < 1 or not a divisor of T, slots < 1 (the same for qs_lora_rows_grouped_tiles).  qs_lora_rows stays the rows form. */
+int qs_lora_rows_grouped(void* out, int64_t out_stride, const int8_t* x, int64_t x_stride, const void* x_scale, const void* A,
+                         const void* B, const float* scaling, const int32_t* seq_adapter, int slots, int T, int K, int N, int r,
+                         int rows_per_seq, int nseg, int seg_end0, int seg_end1, int seg_end2, void* workspace, int64_t workspace_size,
+                         qs_stream_t stream);
+int qs_lora_rows_form(int T, int rows_per_seq, int slots);
+int qs_lora_rows_grouped_tiles(int T, int rows_per_seq, int slots);
 
 /* ----------------------------------------------------------------------------------------------------------
  * Mixture-of-experts layers over the W4A8 linears (no reference counterpart: the reference's Mixtral block raises before routing -

@@ -99,6 +99,9 @@ SIGNATURES = {
     "qs_constrain_advance": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
     "qs_lora_rows_workspace": (_i64, [_i, _i, _i, _i]),
     "qs_lora_rows": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp]),
+    "qs_lora_rows_grouped": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp]),
+    "qs_lora_rows_form": (_i, [_i, _i, _i]),
+    "qs_lora_rows_grouped_tiles": (_i, [_i, _i, _i]),
     "qs_moe_route_workspace": (_i64, [_i, _i, _i]),
     "qs_moe_route": (_i, [_vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "qs_moe_gemm_plan": (_i, [_i, _i, _i, _i, _vp]),

@@ -23,31 +23,9 @@
 //              and finally out = fp16(float(out) + scaling[a] * acc) as one 4-byte read-modify-write per row.  LDS: 12 288 bytes.
 //
 // The LDS bound of the file: 17 408 bytes per workgroup.
-#include "common.h"
+#include "lora_common.h"
 
 namespace {
-
-constexpr int LR_THREADS = 256;
-constexpr int LR_WAVES = LR_THREADS / 64;
-constexpr int LR_TILE = 16;                          // rows of one sequence per workgroup (the N extent of the MFMA)
-constexpr int LR_KSLICE = 512;                       // k per shrink workgroup: 128 per wave, four k-steps of 32
-constexpr int LR_JGROUP = 64;                        // rank rows per shrink workgroup: four MFMA tiles of 16
-constexpr int LR_RED_LD = LR_JGROUP + 4;             // floats per row of the cross-wave exchange (padded against bank conflicts)
-constexpr int LR_NSLICE = 2 * LR_THREADS;            // output columns per expand workgroup
-constexpr int LR_MAX_SEG = 3;
-constexpr int LR_MAX_RANK = 64;
-constexpr int LR_MAX_R = LR_MAX_SEG * LR_MAX_RANK;   // rank rows of all segments
-constexpr int LR_MAX_ROWS = 1 << 24;
-constexpr int LR_MAX_K = 1 << 20;
-constexpr int LR_MAX_N = 1 << 22;
-
-// 8 int8 -> 8 fp16 (exact)
-__device__ __forceinline__ h8 s8_to_h8(v2u v) {
-    h8 r;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) r[e] = (_Float16)(short)(signed char)((v[e >> 2] >> (8 * (e & 3))) & 0xFFu);
-    return r;
-}
 
 // grid = (tiles, K slices, j groups), 256 threads.  tps: tiles per sequence; R = nseg * r.  The launcher checks everything.
 __global__ __launch_bounds__(LR_THREADS) void lora_shrink_kernel(const int8_t* __restrict__ x, long long x_stride,
@@ -189,14 +167,6 @@ __global__ __launch_bounds__(LR_THREADS) void lora_expand_kernel(_Float16* __res
     }
 }
 
-inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-inline bool rank_ok(int r) { return r == 8 || r == 16 || r == 32 || r == 64; }
-
-inline int64_t workspace_bytes(int T, int K, int r, int nseg) {
-    return (int64_t)((K + LR_KSLICE - 1) / LR_KSLICE) * T * nseg * r * (int64_t)sizeof(float);
-}
-
 }  // namespace
 
 extern "C" int64_t qs_lora_rows_workspace(int T, int K, int r, int nseg) {
@@ -210,33 +180,17 @@ extern "C" int qs_lora_rows(void* out, int64_t out_stride, const int8_t* x, int6
                             const void* B, const float* scaling, const int32_t* seq_adapter, int slots, int T, int K, int N, int r,
                             int rows_per_seq, int nseg, int seg_end0, int seg_end1, int seg_end2, void* workspace, int64_t workspace_size,
                             qs_stream_t stream) {
-    QS_REQUIRE(out && x && x_scale && A && B && scaling && seq_adapter && workspace, "lora_rows: null pointer");
-    QS_REQUIRE(rank_ok(r), "lora_rows: r=%d (8, 16, 32 or 64)", r);
-    QS_REQUIRE(K >= 128 && K <= LR_MAX_K && K % 128 == 0, "lora_rows: K=%d (a multiple of 128, 128 .. %d)", K, LR_MAX_K);
-    QS_REQUIRE(N >= 64 && N <= LR_MAX_N && N % 64 == 0, "lora_rows: N=%d (a multiple of 64, 64 .. %d)", N, LR_MAX_N);
-    QS_REQUIRE(nseg >= 1 && nseg <= LR_MAX_SEG, "lora_rows: nseg=%d (1 .. %d)", nseg, LR_MAX_SEG);
     const int ends[LR_MAX_SEG] = {seg_end0, seg_end1, seg_end2};
-    for (int g = 0, prev = 0; g < nseg; prev = ends[g++])
-        QS_REQUIRE(ends[g] > prev && ends[g] % 64 == 0, "lora_rows: segment end %d = %d (ascending multiples of 64)", g, ends[g]);
-    QS_REQUIRE(ends[nseg - 1] == N, "lora_rows: the last segment ends at %d, N=%d", ends[nseg - 1], N);
-    QS_REQUIRE(slots >= 1, "lora_rows: slots=%d (>= 1)", slots);
-    QS_REQUIRE(T >= 0 && T <= LR_MAX_ROWS && rows_per_seq >= 1 && T % rows_per_seq == 0,
-               "lora_rows: T=%d (0 .. %d) must be a multiple of rows_per_seq=%d (>= 1)", T, LR_MAX_ROWS, rows_per_seq);
-    QS_REQUIRE(x_stride >= K && x_stride % 16 == 0 && out_stride >= N && out_stride % 8 == 0,
-               "lora_rows: x stride %lld (>= K=%d, a multiple of 16), out stride %lld (>= N=%d, a multiple of 8)", (long long)x_stride, K,
-               (long long)out_stride, N);
-    QS_REQUIRE(aligned(out, 16) && aligned(x, 16) && aligned(A, 16) && aligned(B, 16) && aligned(workspace, 16) && aligned(x_scale, 2) &&
-                   aligned(scaling, 4) && aligned(seq_adapter, 4),
-               "lora_rows: out, x, A, B and the workspace must be 16-byte, scaling and seq_adapter 4-byte, x_scale 2-byte aligned");
-    QS_REQUIRE(workspace_size >= workspace_bytes(T, K, r, nseg), "lora_rows: the workspace holds %lld bytes, %lld are needed",
-               (long long)workspace_size, (long long)workspace_bytes(T, K, r, nseg));
+    int rc = lora_check_args("lora_rows", out, out_stride, x, x_stride, x_scale, A, B, scaling, seq_adapter, slots, T, K, N, r, rows_per_seq,
+                             nseg, ends, workspace, workspace_size);
+    if (rc != QS_OK) return rc;
     if (T == 0) return QS_OK;
     const int R = nseg * r, tps = (rows_per_seq + LR_TILE - 1) / LR_TILE, tiles = T / rows_per_seq * tps;
     const int kslices = (K + LR_KSLICE - 1) / LR_KSLICE;
     const int e0 = nseg >= 2 ? ends[0] : INT32_MAX, e1 = nseg >= 3 ? ends[1] : INT32_MAX;
     hipLaunchKernelGGL(lora_shrink_kernel, dim3(tiles, kslices, (R + LR_JGROUP - 1) / LR_JGROUP), dim3(LR_THREADS), 0, (hipStream_t)stream, x,
                        (long long)x_stride, (const _Float16*)A, seq_adapter, slots, K, R, rows_per_seq, tps, T, (float*)workspace);
-    int rc = qs_launch_status("lora_rows (shrink)");
+    rc = qs_launch_status("lora_rows (shrink)");
     if (rc != QS_OK) return rc;
     hipLaunchKernelGGL(lora_expand_kernel, dim3(tiles, (N + LR_NSLICE - 1) / LR_NSLICE), dim3(LR_THREADS), 0, (hipStream_t)stream,
                        (_Float16*)out, (long long)out_stride, (const _Float16*)x_scale, (const _Float16*)B, scaling, seq_adapter, slots, N, r,

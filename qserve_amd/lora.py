@@ -7,8 +7,11 @@ GEMM, per row, on the quantised activations that GEMM read - capturable in a hip
     LoraTable   the A / B tensors of every layer and linear for `slots` adapters of rank <= `rank`, filled from PEFT-named tensors
                 (`load`) in the row order qserve_amd.loader fuses the base weights in, zeroed again by `unload`.
 
+    rows_form   the kernel form `lora_rows` takes for a call: "rows" (a tile is up to 16 rows of one sequence; csrc/lora_rows.hip) or
+                "grouped" (a tile is 16 rows of one adapter, wherever they sit in the batch; csrc/lora_grouped.hip).  The same bits.
+
 include/qserve_amd.h (`qs_lora_rows`) has the rule; a float64 numpy restatement is tests/_lora_cases.py.  Backed by
-qserve_amd/csrc/lora_rows.hip.  DecodeEngine.enable_lora / load_lora / set_lora put it behind the four linears of every layer."""
+qserve_amd/csrc/lora_rows.hip and lora_grouped.hip; the choice between them is csrc/lora_plan.h.  DecodeEngine.enable_lora / load_lora / set_lora put it behind the four linears of every layer."""
 import re
 
 import torch
@@ -31,15 +34,29 @@ def workspace_bytes(T, K, r, nseg):
     return int(n)
 
 
-def lora_rows(out, x, x_scale, A, B, scaling, seq_adapter, rows_per_seq, seg_ends, workspace=None):
+FORMS = ("rows", "grouped")
+
+
+def rows_form(T, rows_per_seq, slots):
+    """The form the planner (csrc/lora_plan.h through qs_lora_rows_form) takes for a `lora_rows` call of T rows, rows_per_seq rows per
+    sequence, `slots` adapters: "rows" or "grouped"."""
+    f = lib.qs_lora_rows_form(int(T), int(rows_per_seq), int(slots))
+    check(0 if f >= 0 else int(f), "lora.rows_form")
+    return FORMS[f]
+
+
+def lora_rows(out, x, x_scale, A, B, scaling, seq_adapter, rows_per_seq, seg_ends, workspace=None, form=None):
     """out[t, n] = fp16(out[t, n] + scaling[a] * sum_j B[a, n, j] * t_j) in place, t_j = x_scale[t] * sum_k A[a, g r + j, k] * x[t, k] in
     float32, for every row t whose sequence's adapter a = seq_adapter[t // rows_per_seq] lies in 0 .. slots-1; g: the segment of column
     n.  out fp16 [T, N]; x int8 [T, K] and x_scale fp16 [T]: the quantised activations the base GEMM read; A fp16 [slots, nseg * r, K];
     B fp16 [slots, N, r]; scaling float32 [slots]; seq_adapter int32 [T / rows_per_seq]; seg_ends: the nseg (1 .. 3) ascending segment
     ends, multiples of 64, the last one N.  r in 8, 16, 32, 64; K a multiple of 128, N of 64; out and x may have padded rows (strides
     multiples of 8 and 16).  `workspace`: a contiguous device tensor of at least workspace_bytes(T, K, r, nseg) bytes (None: a fresh
-    one).  -> out."""
+    one).  `form`: "rows" or "grouped" (the same bits; None: rows_form's choice); a named form the planner does not serve for these sizes
+    is refused with its reason.  -> out."""
     what = "lora.lora_rows"
+    if form is not None and form not in FORMS:
+        raise RuntimeError(f"{what}: form={form!r} (None or one of {FORMS})")
     _typed(out, torch.float16, "out")
     _typed(x, torch.int8, "x")
     _typed(x_scale, torch.float16, "x_scale")
@@ -89,10 +106,10 @@ def lora_rows(out, x, x_scale, A, B, scaling, seq_adapter, rows_per_seq, seg_end
     if T == 0:
         return out
     e = seg_ends + [0] * (MAX_SEGMENTS - nseg)
+    entry = lib.qs_lora_rows_grouped if (form or rows_form(T, rows_per_seq, slots)) == "grouped" else lib.qs_lora_rows
     with guard(out):
-        check(lib.qs_lora_rows(ptr(out), out_stride, ptr(x), x_stride, ptr(x_scale), ptr(A), ptr(B), ptr(scaling), ptr(seq_adapter), slots, T,
-                               K, N, r, rows_per_seq, nseg, e[0], e[1], e[2], ptr(workspace), workspace.numel() * workspace.element_size(),
-                               stream()), what)
+        check(entry(ptr(out), out_stride, ptr(x), x_stride, ptr(x_scale), ptr(A), ptr(B), ptr(scaling), ptr(seq_adapter), slots, T, K, N, r,
+                    rows_per_seq, nseg, e[0], e[1], e[2], ptr(workspace), workspace.numel() * workspace.element_size(), stream()), what)
     return out
 
 
