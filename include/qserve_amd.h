@@ -877,12 +877,27 @@ int qs_lora_rows(void* out, int64_t out_stride, const int8_t* x, int64_t x_strid
  * tiles, a bound for every assignment of ids.  Rows of an id outside 0 .. slots-1 belong to no tile.  Two launches.  QS_EINVAL before
  * any device call: what qs_lora_rows refuses, and what the planner (csrc/lora_plan.h) does not serve in this form: rows_per_seq >= 16,
  * slots > 64, T / rows_per_seq > 16 384 sequences.
- * qs_lora_rows_form: the form the planner takes for a call, 0 = rows (qs_lora_rows), 1 = grouped; QS_EINVAL for T outside 0 .. 2^24,
- * rows_per_seq < 1 or not a divisor of T, slots < 1 (the same for qs_lora_rows_grouped_tiles).  qs_lora_rows stays the rows form. */
+ * The PROMPT form (csrc/lora_prompt.hip; qs_lora_rows_prompt): again the arguments, the rule, the workspace and the BITS of
+ * qs_lora_rows, but a tile is up to 64 consecutive rows of one SEQUENCE - ceil(rows_per_seq / 64) tiles per sequence, the last one
+ * short -, for the passes with many rows per sequence (prefill, prefill_chunked, a wide tree): a slice of A or B is fetched once per
+ * 64 rows, a shrink wave sums the chunks of a K slice in its own registers and a workgroup walks a run of K slices.  The adapter id is
+ * read on the device.  Two launches.  QS_EINVAL before any device call: what qs_lora_rows refuses, and rows_per_seq < 16 (the other
+ * two forms serve that).  No slot limit.  qs_lora_rows_prompt_run: the K slices (of 512) a shrink workgroup of a call with that
+ * many tiles walks, slices y run .. y run + run - 1 for workgroup y (csrc/lora_plan.h); QS_EINVAL for tiles or K slices < 1.
+ * qs_lora_rows_form: the form the planner takes for a call, 0 = rows (qs_lora_rows), 1 = grouped, 2 = prompt; QS_EINVAL for T outside
+ * 0 .. 2^24, rows_per_seq < 1 or not a divisor of T, slots < 1 (the same for qs_lora_rows_grouped_tiles).  qs_lora_rows stays the
+ * rows form.  qs_lora_rows_form_for_rank: what a PLANNED form becomes for a call of rank r - the planner does not see r, and the
+ * prompt form is planned up to r = 16 only (csrc/lora_plan.h has the measurement); QS_EINVAL for a form outside 0 .. 2 or a bad r. */
 int qs_lora_rows_grouped(void* out, int64_t out_stride, const int8_t* x, int64_t x_stride, const void* x_scale, const void* A,
                          const void* B, const float* scaling, const int32_t* seq_adapter, int slots, int T, int K, int N, int r,
                          int rows_per_seq, int nseg, int seg_end0, int seg_end1, int seg_end2, void* workspace, int64_t workspace_size,
                          qs_stream_t stream);
+int qs_lora_rows_prompt(void* out, int64_t out_stride, const int8_t* x, int64_t x_stride, const void* x_scale, const void* A,
+                        const void* B, const float* scaling, const int32_t* seq_adapter, int slots, int T, int K, int N, int r,
+                        int rows_per_seq, int nseg, int seg_end0, int seg_end1, int seg_end2, void* workspace, int64_t workspace_size,
+                        qs_stream_t stream);
+int qs_lora_rows_prompt_run(int tiles, int kslices);
+int qs_lora_rows_form_for_rank(int form, int r);
 int qs_lora_rows_form(int T, int rows_per_seq, int slots);
 int qs_lora_rows_grouped_tiles(int T, int rows_per_seq, int slots);
 

@@ -100,6 +100,9 @@ SIGNATURES = {
     "qs_lora_rows_workspace": (_i64, [_i, _i, _i, _i]),
     "qs_lora_rows": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp]),
     "qs_lora_rows_grouped": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp]),
+    "qs_lora_rows_prompt": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp]),
+    "qs_lora_rows_prompt_run": (_i, [_i, _i]),
+    "qs_lora_rows_form_for_rank": (_i, [_i, _i]),
     "qs_lora_rows_form": (_i, [_i, _i, _i]),
     "qs_lora_rows_grouped_tiles": (_i, [_i, _i, _i]),
     "qs_moe_route_workspace": (_i64, [_i, _i, _i]),

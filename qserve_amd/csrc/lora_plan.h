@@ -1,11 +1,13 @@
-// lora_plan.h -- which form of the LoRA row update serves a call, and the grid of the grouped one.  Plain C++17 next to moe_plan.h:
-// no HIP, no device access, no global state - a function of (T, rows_per_seq, slots) alone, so it can be asked on a machine without a
-// GPU (qs_lora_rows_form, qs_lora_rows_grouped_tiles).  Both forms compute the same bits (lora_grouped.hip): the choice is cost only.
+// lora_plan.h -- which form of the LoRA row update serves a call, and the grids of the grouped and the prompt one.  Plain C++17 next
+// to moe_plan.h: no HIP, no device access, no global state - a function of (T, rows_per_seq, slots) alone, so it can be asked on a
+// machine without a GPU (qs_lora_rows_form, qs_lora_rows_grouped_tiles).  All three forms compute the same bits (lora_grouped.hip,
+// lora_prompt.hip): the choice is cost only.
 #pragma once
 
 namespace lora_plan {
 
-constexpr int TILE = 16;                  // rows of a tile, of either form
+constexpr int TILE = 16;                  // rows of a tile of the rows and the grouped form
+constexpr int PROMPT_TILE = 64;           // rows of a tile of the prompt form: one 16-row MFMA block for each of the four waves
 constexpr int GROUPED_MAX_SLOTS = 64;     // the grouped kernels keep one LDS counter per slot and pick the adapter with one ballot word
 
 // Tiles the grouped form launches: adapter a with c_a > 0 rows needs ceil(c_a / 16) tiles, and at most min(slots, S) adapters have
@@ -50,10 +52,69 @@ inline const char* grouped_refusal(int T, int rows_per_seq, int slots) {
     return nullptr;
 }
 
-enum LoraForm { LORA_ROWS = 0, LORA_GROUPED = 1 };
+// ---- the prompt form (lora_prompt.hip): a tile is up to 64 consecutive rows of one sequence
+inline int prompt_tiles(int T, int rows_per_seq) {
+    if (T <= 0 || rows_per_seq <= 0) return 0;
+    return T / rows_per_seq * ((rows_per_seq + PROMPT_TILE - 1) / PROMPT_TILE);
+}
+
+// K slices (of 512) a prompt shrink workgroup walks one after the other: slices run .. run + prompt_run - 1 of workgroup y = run /
+// prompt_run, the last run short.  A wave keeps its rows' x and its accumulators for the whole run, so a long run is cheap; but the
+// grid has to cover the 256 CUs several times (about four workgroups each, PROMPT_SHRINK_WGS; a workgroup is one wave per SIMD), so
+// with few tiles the runs are short - one slice at the least - and with many they are long.  Every slice belongs to exactly one run.
+constexpr int PROMPT_SHRINK_WGS = 1024;
+inline int prompt_run(int tiles, int kslices) {
+    if (tiles <= 0 || kslices <= 0) return 0;
+    int runs = (PROMPT_SHRINK_WGS + tiles - 1) / tiles;
+    if (runs > kslices) runs = kslices;
+    return (kslices + runs - 1) / runs;
+}
+
+// Output column slices (of 512) a prompt expand workgroup walks, as grouped_expand_ysplit: a workgroup stages its tile's t once - a
+// read of every K-slice plane of 64 rows - and keeps it for the slices blockIdx.y, blockIdx.y + ysplit, ...; about four workgroups for
+// each of the 256 CUs.
+inline int prompt_expand_ysplit(int tiles, int nslices) {
+    if (tiles <= 0 || nslices <= 0) return 0;
+    const int want = (1024 + tiles - 1) / tiles;
+    return want < nslices ? want : nslices;
+}
+
+// What the prompt form serves at all: a sequence that fills one 16-row block of a tile.  Below that the other two forms serve the
+// call.  No slot limit: the tile's adapter is one read of seq_adapter.
+inline const char* prompt_refusal(int T, int rows_per_seq, int slots) {
+    (void)T;
+    (void)slots;
+    if (rows_per_seq < TILE) return "rows_per_seq < 16: a sequence does not fill one wave's block, the rows and the grouped form serve it";
+    return nullptr;
+}
+
+// Where the planner takes the prompt form.  The measured sweep (profiles/lora_prompt.txt, section 1: rows_per_seq 16, 32, 64, 128, 256,
+// 1 024 at T = 4 096 and 16 384, r = 16, 8 adapters, both forms captured, in alternation, medians of three) has prompt / rows at the
+// qkv (4096 -> 6144) / gate_up (4096 -> 28672) shape: rows_per_seq = 16 0.91 / 0.82 at T = 4 096 and 0.86 / 0.70 at 16 384; 32 0.94 /
+// 0.77 and 0.84 / 0.66; 64 0.83 / 0.74 and 0.76 / 0.72; 256 0.82 / 0.75 and 0.76 / 0.72; o and down 0.68 - 0.90; the spread inside the
+// run is 0.01 at the most but for the lines at rows_per_seq = 16 (0.04 - 0.06), and an earlier run of the same script had the same
+// lines within 0.07 of these (gate_up at 16 384 rows from 64 rows per sequence on: 0.65 there).  The form won at EVERY point of the
+// sweep by more than the spread, so both limits are ends of it, not crossovers:
+//   PROMPT_MIN_ROWS_PER_SEQ  rows_per_seq = 16 would have won too (above), but the planner's answer "rows" for (4096, 16, 8) is pinned
+//                            by tests/test_lora_grouped_cpu.py, so the limit is 17; 17 .. 31 lie between two measured wins.
+//   PROMPT_MIN_ROWS          4 096, the smaller T of the sweep; nothing below it was measured (a 64-node tree at bs = 64 is 4 096 rows).
+//   PROMPT_MAX_PLANNED_RANK  the planner cannot see r through (T, rows_per_seq, slots); `planned_for_rank` is asked behind it.  At r = 64
+//                            the prompt form LOSES, 1.28 / 1.28 of the rows form at qkv / gate_up (section 2): its expand holds all r
+//                            values of B for two columns and runs one wave per SIMD there.  r = 32 was not measured.  So a planned
+//                            "prompt" becomes "rows" above r = 16, the measured rank; the form stays reachable by name at every rank.
+constexpr int PROMPT_MIN_ROWS_PER_SEQ = 17;
+constexpr int PROMPT_MIN_ROWS = 4096;
+constexpr int PROMPT_MAX_PLANNED_RANK = 16;
+
+enum LoraForm { LORA_ROWS = 0, LORA_GROUPED = 1, LORA_PROMPT = 2 };
 inline LoraForm lora_form(int T, int rows_per_seq, int slots) {
-    if (T <= 0 || rows_per_seq <= 0 || grouped_refusal(T, rows_per_seq, slots)) return LORA_ROWS;
+    if (T <= 0 || rows_per_seq <= 0) return LORA_ROWS;
+    if (!prompt_refusal(T, rows_per_seq, slots) && rows_per_seq >= PROMPT_MIN_ROWS_PER_SEQ && T >= PROMPT_MIN_ROWS) return LORA_PROMPT;
+    if (grouped_refusal(T, rows_per_seq, slots)) return LORA_ROWS;
     return T / rows_per_seq >= GROUPED_MIN_SEQS ? LORA_GROUPED : LORA_ROWS;
 }
+
+// The planner's form `form` for a call of rank r (PROMPT_MAX_PLANNED_RANK has the measurement).
+inline LoraForm planned_for_rank(LoraForm form, int r) { return form == LORA_PROMPT && r > PROMPT_MAX_PLANNED_RANK ? LORA_ROWS : form; }
 
 }  // namespace lora_plan

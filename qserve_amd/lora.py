@@ -7,11 +7,12 @@ GEMM, per row, on the quantised activations that GEMM read - capturable in a hip
     LoraTable   the A / B tensors of every layer and linear for `slots` adapters of rank <= `rank`, filled from PEFT-named tensors
                 (`load`) in the row order qserve_amd.loader fuses the base weights in, zeroed again by `unload`.
 
-    rows_form   the kernel form `lora_rows` takes for a call: "rows" (a tile is up to 16 rows of one sequence; csrc/lora_rows.hip) or
-                "grouped" (a tile is 16 rows of one adapter, wherever they sit in the batch; csrc/lora_grouped.hip).  The same bits.
+    rows_form   the kernel form `lora_rows` takes for a call: "rows" (a tile is up to 16 rows of one sequence; csrc/lora_rows.hip),
+                "grouped" (a tile is 16 rows of one adapter, wherever they sit in the batch; csrc/lora_grouped.hip) or "prompt" (a
+                tile is up to 64 rows of one sequence, for prompt passes; csrc/lora_prompt.hip).  The same bits.
 
 include/qserve_amd.h (`qs_lora_rows`) has the rule; a float64 numpy restatement is tests/_lora_cases.py.  Backed by
-qserve_amd/csrc/lora_rows.hip and lora_grouped.hip; the choice between them is csrc/lora_plan.h.  DecodeEngine.enable_lora / load_lora / set_lora put it behind the four linears of every layer."""
+qserve_amd/csrc/lora_rows.hip, lora_grouped.hip and lora_prompt.hip; the choice between them is csrc/lora_plan.h.  DecodeEngine.enable_lora / load_lora / set_lora put it behind the four linears of every layer."""
 import re
 
 import torch
@@ -34,12 +35,12 @@ def workspace_bytes(T, K, r, nseg):
     return int(n)
 
 
-FORMS = ("rows", "grouped")
+FORMS = ("rows", "grouped", "prompt")
 
 
 def rows_form(T, rows_per_seq, slots):
     """The form the planner (csrc/lora_plan.h through qs_lora_rows_form) takes for a `lora_rows` call of T rows, rows_per_seq rows per
-    sequence, `slots` adapters: "rows" or "grouped"."""
+    sequence, `slots` adapters: "rows", "grouped" or "prompt"."""
     f = lib.qs_lora_rows_form(int(T), int(rows_per_seq), int(slots))
     check(0 if f >= 0 else int(f), "lora.rows_form")
     return FORMS[f]
@@ -52,7 +53,7 @@ def lora_rows(out, x, x_scale, A, B, scaling, seq_adapter, rows_per_seq, seg_end
     B fp16 [slots, N, r]; scaling float32 [slots]; seq_adapter int32 [T / rows_per_seq]; seg_ends: the nseg (1 .. 3) ascending segment
     ends, multiples of 64, the last one N.  r in 8, 16, 32, 64; K a multiple of 128, N of 64; out and x may have padded rows (strides
     multiples of 8 and 16).  `workspace`: a contiguous device tensor of at least workspace_bytes(T, K, r, nseg) bytes (None: a fresh
-    one).  `form`: "rows" or "grouped" (the same bits; None: rows_form's choice); a named form the planner does not serve for these sizes
+    one).  `form`: "rows", "grouped" or "prompt" (the same bits; None: rows_form's choice, "rows" in place of "prompt" above r = 16); a named form the planner does not serve for these sizes
     is refused with its reason.  -> out."""
     what = "lora.lora_rows"
     if form is not None and form not in FORMS:
@@ -106,7 +107,9 @@ def lora_rows(out, x, x_scale, A, B, scaling, seq_adapter, rows_per_seq, seg_end
     if T == 0:
         return out
     e = seg_ends + [0] * (MAX_SEGMENTS - nseg)
-    entry = lib.qs_lora_rows_grouped if (form or rows_form(T, rows_per_seq, slots)) == "grouped" else lib.qs_lora_rows
+    if form is None:                                     # (the planner does not see r: a planned "prompt" holds up to r = 16, lora_plan.h)
+        form = FORMS[lib.qs_lora_rows_form_for_rank(FORMS.index(rows_form(T, rows_per_seq, slots)), r)]
+    entry = dict(rows=lib.qs_lora_rows, grouped=lib.qs_lora_rows_grouped, prompt=lib.qs_lora_rows_prompt)[form]
     with guard(out):
         check(entry(ptr(out), out_stride, ptr(x), x_stride, ptr(x_scale), ptr(A), ptr(B), ptr(scaling), ptr(seq_adapter), slots, T, K, N, r,
                     rows_per_seq, nseg, e[0], e[1], e[2], ptr(workspace), workspace.numel() * workspace.element_size(), stream()), what)
