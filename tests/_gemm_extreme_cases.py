@@ -216,10 +216,12 @@ def fp32_spacing(v):
 # ---- the table ----------------------------------------------------------------------------------------------------------------------------
 # family: own = the planner's choice; splitk / pair / tiled / wide / ring = forced by `code` (include/qserve_amd.h qs_gemm_variant_code);
 # every row of these six also runs the raw-accumulator entry (gemm_forward_acc).  planes = the K-slice planes entries finished by
-# add_residual_rms_norm_general_planes; gate_up = GEMM + silu * mul in one call; moe = the grouped GEMM; w8a8.
+# add_residual_rms_norm_general_planes; gate_up = GEMM + silu * mul in one call; moe = the grouped GEMM, moe_tiled = its compute-bound tile,
+# forced; w8a8.
 # plan: what the planner must report for the row - qs_w4a8_gemm_plan's (family, p0 .. p3), None = not pinned; planes:
-# qs_w4a8_gemm_planes_plan's (k_slices, m_tiles, units, token blocks); moe: qs_moe_gemm_plan's (mt, waves, row blocks, units).
-# extra: moe = rows per expert (M = their sum, over 14 source rows).
+# qs_w4a8_gemm_planes_plan's (k_slices, m_tiles, units, token blocks); moe: qs_moe_gemm_plan's (mt, waves, row blocks, units); moe_tiled:
+# qs_moe_gemm_tiled_plan's (rows per tile, channel tiles, row blocks, stages).
+# extra: moe, moe_tiled = rows per expert (M = their sum, over 14 source rows).
 Row = collections.namedtuple("Row", "family code mode M N K wkind scales plan note extra")
 F_SPLITK, F_PAIR, F_RING, F_TILED, F_WIDE = 1, 2, 3, 4, 5
 PC, PG, ANY = MODES
@@ -369,6 +371,19 @@ MOE = [
     _row("moe", -1, PG, 110, 64, 2176, "bm128", plan=(4, 4, 3, 1), extra=(70, 40)),
 ]
 
+# the compute-bound grouped tile (csrc/gemm_w4a8_moe_tiled.hip, form="tiled"): its own nibble unpack, level-2 dequant in registers and
+# epilogue.  The same two experts and 14 source rows; P = 150 = a full 128-row block plus two rows of expert 0, then a short block.
+# plan: qs_moe_gemm_tiled_plan's (rows per tile, channel tiles, row blocks, stages of 64 k) - 18 to 224 stages through the 6-deep ring.
+MOE_TILED = [
+    _row("moe_tiled", -1, PC, 150, 256, 14336, "q15", plan=(128, 1, 3, 224), extra=(130, 20)),
+    _row("moe_tiled", -1, PC, 150, 256, 14336, "q15_half", "overflow", plan=(128, 1, 3, 224), extra=(130, 20)),
+    _row("moe_tiled", -1, PC, 150, 512, 8832, "q15", plan=(128, 2, 3, 138), extra=(130, 20)),
+    _row("moe_tiled", -1, PG, 150, 256, 2176, "mixed", plan=(128, 1, 3, 34), extra=(130, 20)),
+    _row("moe_tiled", -1, PG, 150, 512, 1152, "b127", plan=(128, 2, 3, 18), extra=(130, 20)),
+    _row("moe_tiled", -1, PG, 150, 256, 2176, "bm128", plan=(128, 1, 3, 34), extra=(130, 20)),
+    _row("moe_tiled", -1, ANY, 150, 256, 1152, "mixed", plan=(128, 1, 3, 18), extra=(130, 20)),
+]
+
 W8A8 = [
     _row("w8a8", -1, "w8a8", 1, 64, 1152, "b127"),
     _row("w8a8", -1, "w8a8", 17, 192, 2176, "mixed"),
@@ -388,9 +403,9 @@ def _tie_rows(rows):
     return out
 
 
-TABLE = OWN + SPLITK + PAIR + TILED + RING + PLANES + GATE_UP + MOE + W8A8
+TABLE = OWN + SPLITK + PAIR + TILED + RING + PLANES + GATE_UP + MOE + W8A8 + MOE_TILED
 TABLE = TABLE + _tie_rows(TABLE)
-FAMILIES = ("own", "splitk", "pair", "tiled", "wide", "ring", "planes", "gate_up", "moe", "w8a8")
+FAMILIES = ("own", "splitk", "pair", "tiled", "wide", "ring", "planes", "gate_up", "moe", "w8a8", "moe_tiled")
 
 
 def row_id(row):
@@ -399,7 +414,7 @@ def row_id(row):
 
 def source_rows(row):
     """Activation rows of the row's problem: M, or the 14 source rows a grouped GEMM gathers from."""
-    return MOE_X_ROWS if row.family == "moe" else row.M
+    return MOE_X_ROWS if row.family in ("moe", "moe_tiled") else row.M
 
 
 def row_problem_key(row):

@@ -1,7 +1,7 @@
 """The table of tests/_gemm_extreme_cases.py, checked without a GPU: on every row's operands the oracle's accumulators equal the int64
 matmul; the rows are what they claim - accumulators of at least 2^24 that fp32 cannot hold, slices that are large and cancel, the
 inf / NaN layout of the overflow scales from the oracle alone; every row gets the plan it names from qs_w4a8_gemm_plan /
-qs_w4a8_gemm_planes_plan / qs_moe_gemm_plan (a row that silently ran another geometry would test nothing); and every family keeps the
+qs_w4a8_gemm_planes_plan / qs_moe_gemm_plan / qs_moe_gemm_tiled_plan (a row that silently ran another geometry would test nothing); and every family keeps the
 rows tests/test_gemm_extremes_gpu.py is there for, so a later edit cannot drop one silently."""
 import ctypes as C
 
@@ -176,9 +176,10 @@ def lib(built_lib):
 def _planned(lib, row):
     from qserve_amd._lib import check
     per_group = int(row.mode != "per_channel")
-    if row.family == "moe":
+    if row.family in ("moe", "moe_tiled"):
         buf = (C.c_int * 4)()
-        check(lib.qs_moe_gemm_plan(row.M, len(row.extra), row.N, row.K, buf), "moe gemm plan")
+        fn = lib.qs_moe_gemm_plan if row.family == "moe" else lib.qs_moe_gemm_tiled_plan
+        check(fn(row.M, len(row.extra), row.N, row.K, buf), "moe gemm plan")
         return tuple(buf)
     buf = (C.c_int * (4 if row.family == "planes" else 5))()
     lib.qs_set_gemm_variant(row.code)
@@ -206,12 +207,15 @@ def test_every_row_plans_as_it_claims(lib):
             assert got[0] in (1, 2, 4) and (row.code < 0 or got[0] == cases.ring_geometry(row.code)[2])
         if row.family == "moe":
             assert sum(row.extra) == row.M and got[3] == row.N // 64
+        if row.family == "moe_tiled":                                   # a full row block and a short one of expert 0, a short one of expert 1
+            assert sum(row.extra) == row.M and got[1] * 256 == row.N and got[3] * 64 == row.K and None not in row.plan
+            assert got[0] < row.extra[0] < 2 * got[0] and 0 < row.extra[1] < got[0] and got[2] == 3
 
 
 def test_sizes_stay_inside_the_limits_and_say_where_k_was_substituted():
     assert len({cases.row_id(r) for r in cases.TABLE}) == len(cases.TABLE)
     for row in cases.TABLE:
-        assert 1 <= row.M <= 130 and row.N <= 512 and row.K <= 14336 and row.K % 128 == 0, cases.row_id(row)
+        assert 1 <= row.M <= (150 if row.family == "moe_tiled" else 130) and row.N <= 512 and row.K <= 14336 and row.K % 128 == 0, cases.row_id(row)
         listed = cases.PC_K if row.mode == "per_channel" else cases.BYTE_K
         assert (row.K in listed) == (not row.note.startswith("K ")), cases.row_id(row)
         assert row.K >= listed[0], "every K reaches 2^24"
@@ -245,5 +249,9 @@ def test_every_family_keeps_its_rows():
     assert any(r.plan[4] == 2 and r.N // (64 * r.plan[2]) % 4 == 0 for r in cases.RING), "a two-slice seam that takes the XCD mapping"
     assert {cases.ring_geometry(r.code)[2] for r in cases.RING} == {1, 2, 4} == {r.plan[0] for r in cases.PLANES}
     assert {r.extra for r in cases.MOE} == {(20, 13), (7, 3), (70, 40)} and {r.plan[0] for r in cases.MOE} == {1, 2, 4}
+    assert {r.extra for r in cases.MOE_TILED} == {(130, 20)} and {r.mode for r in cases.MOE_TILED} == set(cases.MODES)
+    assert {r.N for r in cases.MOE_TILED} == {256, 512} and max(r.K for r in cases.MOE_TILED) == 14336
+    offsets, row_src = cases.moe_routing(cases.MOE_TILED[0])
+    assert offsets.tolist() == [0, 130, 150] and set(row_src.tolist()) == set(range(cases.MOE_X_ROWS)) and (np.diff(row_src) < 0).any()
     offsets, row_src = cases.moe_routing(cases.MOE[0])
     assert offsets.tolist() == [0, 20, 33] and len(set(row_src.tolist())) < len(row_src) and (np.diff(row_src) < 0).any()

@@ -240,13 +240,25 @@ def test_grouped_gemm(gpu, row):
     """Two experts - the row's weights and all-zero nibbles - over 14 source rows, every pattern twice, row_src with repeats, padded x and out:
     bit-equal to the oracle of every pair's (expert, source row), to the dense entry per expert on the gathered rows, rows >= P and the
     guard columns untouched, the second launch equal to the first."""
+    _grouped_gemm(gpu, row, None)
+
+
+@_rows("moe_tiled")
+def test_grouped_gemm_tiled(gpu, row):
+    """test_grouped_gemm through the compute-bound tile (form="tiled": csrc/gemm_w4a8_moe_tiled.hip), under the plan the row names: its
+    nibble unpack and level-2 dequant on -128 and on bytes no (z, s2) pair gives, its epilogue on accumulators beyond 2^24, inf / NaN
+    and the tie scales, over 18 to 224 stages of its ring."""
+    _grouped_gemm(gpu, row, "tiled")
+
+
+def _grouped_gemm(gpu, row, form):
     from qserve_amd import _lib, moe
     lib = _lib.lib
     pr = cases.row_problem(row)
     experts = [pr, cases.moe_zero_expert(pr)]
     offsets, row_src = cases.moe_routing(row)
     P, N, K, per_chn = row.M, row.N, row.K, row.mode == "per_channel"
-    assert moe.gemm_plan(P, 2, N, K) == row.plan
+    assert (moe.gemm_tiled_plan if form == "tiled" else moe.gemm_plan)(P, 2, N, K) == row.plan
     names = ("qweight", "wscales", "w_szs") if per_chn else ("qweight", "wscales", "s2_scales", "s2_zeros")
     stacked = {n: dev(np.stack([e[n] for e in experts])) for n in names}
     if per_chn:
@@ -270,11 +282,11 @@ def test_grouped_gemm(gpu, row):
                 want[offsets[e]:offsets[e + 1]] = cases.oracle_out(sub, cases.oracle_acc(sub), fma=bool(conv))
             out_store = torch.full((P + 3, N + 8), FILL, dtype=torch.float16, device=gpu)
             out = out_store[:P, :N]
-            moe.grouped_gemm(x, scale, ssum, dev(offsets), lin, out, row_src=dev(row_src))
+            moe.grouped_gemm(x, scale, ssum, dev(offsets), lin, out, row_src=dev(row_src), form=form)
             first = out_store.cpu().numpy().copy()
             _same_f16(first[:P, :N], want, f"epilogue {conv}: against the oracle")
             assert (first[P:] == FILL).all() and (first[:, N:] == FILL).all(), "a row >= P or a guard column was written"
-            moe.grouped_gemm(x, scale, ssum, dev(offsets), lin, out, row_src=dev(row_src))
+            moe.grouped_gemm(x, scale, ssum, dev(offsets), lin, out, row_src=dev(row_src), form=form)
             assert np.array_equal(out_store.cpu().numpy().view(np.uint16), first.view(np.uint16)), "the second launch differs"
             for e in range(2):
                 lo, hi = int(offsets[e]), int(offsets[e + 1])

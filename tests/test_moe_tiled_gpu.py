@@ -1,6 +1,8 @@
 """The compute-bound grouped W4A8 tile (csrc/gemm_w4a8_moe_tiled.hip) on the GPU, through the forced entries (`form="tiled"`): bit-equal
 to the dense entries per expert, 0 ulp against oracle.w4a8 at one routing per mode, and to the streaming form where the planner takes the
-tile by itself.  The ring is 6 stages of 64 k deep: K = 256 fills less than it, 384 exactly it, 1024 wraps it."""
+tile by itself.  The ring is 6 stages of 64 k deep: K = 256 fills less than it, 384 exactly it, 1024 wraps it; test_tiled_stage_counts runs every even
+stage count between.  Grids wider than two channel tiles, far source rows and hostile row_src: tests/test_moe_tiled_grid_gpu.py; extreme
+operands: the moe_tiled family of tests/test_gemm_extremes_gpu.py."""
 import functools
 
 import numpy as np
@@ -76,6 +78,19 @@ def _check_against_dense(mode, lin, x, scale, ssum, src, bounds, out, what):
 def test_tiled_against_dense(moe, gpu, mode, epi, Kk, N, routing):
     """The forced tile, rows gathered through a row_src with repeats in no order from padded x rows into padded out rows: bit-equal to the
     dense entry per expert; rows >= P and the guard columns keep their fill; "edges" also 0 ulp against the oracle pair by pair."""
+    _tiled_against_dense(moe, gpu, mode, epi, Kk, N, routing)
+
+
+@pytest.mark.parametrize("Kk", [512, 640, 768, 896])
+@pytest.mark.parametrize("mode,epi", MODES, ids=MODE_IDS)
+def test_tiled_stage_counts(moe, gpu, mode, epi, Kk):
+    """With K = 256 and 384 above, every even stage count nh = K / 64 from 4 to 14 around the ring's depth of 6: the steady loop runs 1, 2,
+    3 and 4 times before the drain, and the run-time wait counts of fill and drain take each of their values.  The assertions of
+    test_tiled_against_dense on "edges", the 0-ulp oracle included."""
+    _tiled_against_dense(moe, gpu, mode, epi, Kk, 256, "edges")
+
+
+def _tiled_against_dense(moe, gpu, mode, epi, Kk, N, routing):
     from qserve_amd._lib import check, lib
     counts = ROUTINGS[routing]
     E, P = len(counts), sum(counts)
