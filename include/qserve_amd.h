@@ -869,7 +869,7 @@ int64_t qs_lora_rows_workspace(int T, int K, int r, int nseg);
 int qs_lora_rows(void* out, int64_t out_stride, const int8_t* x, int64_t x_stride, const void* x_scale, const void* A, const void* B,
                  const float* scaling, const int32_t* seq_adapter, int slots, int T, int K, int N, int r, int rows_per_seq, int nseg,
                  int seg_end0, int seg_end1, int seg_end2, void* workspace, int64_t workspace_size, qs_stream_t stream);
-/* The GROUPED form of the same update (csrc/lora_grouped.hip): the arguments, the rule, the workspace and the BITS of qs_lora_rows -
+/* The GROUPED form of the same update (csrc/lora_rows.hip too): the arguments, the rule, the workspace and the BITS of qs_lora_rows -
  * element for element, so the form is a choice of cost alone -, but a tile is 16 rows of one ADAPTER, wherever they sit in the batch:
  * the rows of adapter a are the rows t with seq_adapter[t / rows_per_seq] == a in ascending t, tile i of a is rows 16 i .. 16 i + 15
  * of that list.  Every workgroup finds its tile from seq_adapter on the device (nothing is read back; a captured call follows ids

@@ -1,6 +1,6 @@
 // lora_plan.h -- which form of the LoRA row update serves a call, and the grids of the grouped and the prompt one.  Plain C++17 next
 // to moe_plan.h: no HIP, no device access, no global state - a function of (T, rows_per_seq, slots) alone, so it can be asked on a
-// machine without a GPU (qs_lora_rows_form, qs_lora_rows_grouped_tiles).  All three forms compute the same bits (lora_grouped.hip,
+// machine without a GPU (qs_lora_rows_form, qs_lora_rows_grouped_tiles).  All three forms compute the same bits (lora_rows.hip,
 // lora_prompt.hip): the choice is cost only.
 #pragma once
 

@@ -7,14 +7,10 @@
 // device, so a captured call follows ids changed in place.  The workspace is exactly the rows form's (qs_lora_rows_workspace: float32
 // K-slice planes [K slices, T, nseg * r]).
 //
-// Same bits as lora_rows.hip, element for element: per row and rank row chains of four MFMA k-steps over each 128-chunk of K from
-// +0.0; the four chunk sums of a 512-slice added in chunk order (an absent chunk of a partial last slice is +0.0, as the idle wave's
-// accumulator is there); the slices added in slice order; one multiply by float(x_scale); acc = fmaf(float(B[n, j]), t_j, acc) over j
-// ascending; fp16(fmaf(scaling, acc, float(old))).  An MFMA column depends on its own operand column only and an MFMA row on its own
-// operand row only, so which rows share a tile - and what stands in the columns and rows nobody stores - does not change a value.
-// Every float32 step is an explicit operation, and the last fmaf is held as a float32 value (as_f32) so that it is not folded into
-// the fp16 rounding (lora_grouped.hip has the finding).  No atomics, no cross-workgroup wait inside a launch, no scratch.  This file
-// holds TWO kernels:
+// Every sum runs in the order lora_rows.hip states in front of its kernels, the staging and the landing step are lora_common.h's, shared
+// with the 16-row forms.  An MFMA column depends on its own operand column only and an MFMA row on its own operand row only, so which
+// rows share a tile - and what stands in the columns and rows nobody stores - does not change a value.  No atomics, no cross-workgroup
+// wait inside a launch, no scratch.  This file holds TWO kernels:
 //
 //   lora_prompt_shrink_kernel<NJT>   grid = (tiles, runs of K slices, rank groups of 16 NJT <= 64 rank rows), 256 threads, NO LDS and NO
 //              barrier.  Wave w owns rows 16 w .. 16 w + 15 of the tile - a wave whose block is empty leaves - and whole 512-slices:
@@ -45,12 +41,7 @@ namespace {
 constexpr int LP_TILE = lora_plan::PROMPT_TILE;      // rows per workgroup: one MFMA block of LR_TILE rows per wave
 static_assert(LP_TILE == LR_WAVES * LR_TILE, "a wave owns one 16-row block of the tile");
 
-// A float32 value the compiler has to produce as such (lora_grouped.hip: left alone, the rule's last fmaf and the fp16 rounding are
-// folded into v_fma_mixlo_f16 - one rounding where lora_rows.hip has two).
-__device__ __forceinline__ float as_f32(float v) {
-    asm volatile("" : "+v"(v));
-    return v;
-}
+using PromptTile = SeqTile<LP_TILE>;
 
 // the operands of one 128-chunk of K in a lane: 8 int8 of x and 8 fp16 of A per rank tile, for each of the four k-steps
 template <int NJT>
@@ -76,14 +67,13 @@ __global__ __launch_bounds__(LR_THREADS) void lora_prompt_shrink_kernel(const in
                                                                         const _Float16* __restrict__ A, const int* __restrict__ seq_adapter,
                                                                         int slots, int K, int R, int rps, int tps, int T, int run,
                                                                         float* __restrict__ ws) {
-    const int s = blockIdx.x / tps, ti = blockIdx.x - s * tps;
-    const int a = seq_adapter[s];
-    if (a < 0 || a >= slots) return;                     // the base model (workgroup-uniform)
-    const int rows = rps - ti * LP_TILE < LP_TILE ? rps - ti * LP_TILE : LP_TILE;
+    const PromptTile tl(seq_adapter, slots, rps, tps);
+    if (tl.rows == 0) return;                            // the base model (workgroup-uniform)
+    const int a = tl.a, rows = tl.rows;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
     if (wave * LR_TILE >= rows) return;                  // the wave's block is empty (no barrier in this kernel)
     const bool live = wave * LR_TILE + c < rows;
-    const size_t row = (size_t)s * rps + ti * LP_TILE + (live ? wave * LR_TILE + c : 0);
+    const size_t row = tl.row(live ? wave * LR_TILE + c : 0);
     const int j0 = blockIdx.z * (16 * NJT);
     const int8_t* xp = x + row * x_stride + 8 * g;
     const _Float16* ap[NJT];
@@ -139,12 +129,10 @@ __global__ __launch_bounds__(LR_THREADS) void lora_prompt_expand_kernel(_Float16
                                                                         int slots, int N, int R, int rps, int tps, int T, int kslices, int e0,
                                                                         int e1, const float* __restrict__ ws) {
     extern __shared__ __attribute__((aligned(16))) float s_t[];   // [LP_TILE][R]
-    const int s = blockIdx.x / tps, ti = blockIdx.x - s * tps;
-    const int a = seq_adapter[s];
-    if (a < 0 || a >= slots) return;                     // the base model (workgroup-uniform)
-    const size_t row0 = (size_t)s * rps + ti * LP_TILE;
-    const int rows = rps - ti * LP_TILE < LP_TILE ? rps - ti * LP_TILE : LP_TILE;
-    const int tid = threadIdx.x;
+    const PromptTile tl(seq_adapter, slots, rps, tps);
+    if (tl.rows == 0) return;                            // the base model (workgroup-uniform)
+    const int a = tl.a, rows = tl.rows, tid = threadIdx.x;
+    const size_t row0 = tl.row0;
     const int nslices = (N + LR_NSLICE - 1) / LR_NSLICE;
 
     // the thread's columns of the current column slice, and block `blk` of the tile's rows of out for them.  Loads take no branch: a
@@ -174,16 +162,7 @@ __global__ __launch_bounds__(LR_THREADS) void lora_prompt_expand_kernel(_Float16
     request_b();
 
     // ---- 1. t[row, j] = x_scale[row] * (the K-slice planes summed in slice order), all segments, the tile's rows
-    const int q = R >> 2;
-    for (int i = tid; i < rows * q; i += LR_THREADS) {
-        const int t = i / q, j4 = (i - t * q) * 4;
-        const float* p = ws + (row0 + t) * R + j4;
-        v4f sum = *reinterpret_cast<const v4f*>(p);
-#pragma unroll 8
-        for (int sl = 1; sl < kslices; ++sl) sum += *reinterpret_cast<const v4f*>(p + (size_t)sl * T * R);
-        const float sx = (float)x_scale[row0 + t];
-        *reinterpret_cast<v4f*>(&s_t[t * R + j4]) = sum * sx;
-    }
+    lora_stage(s_t, R, tl, R, T, kslices, ws, x_scale);
     __syncthreads();
 
     // ---- 2. two columns per thread, the tile's 16-row blocks, one column slice after the other (no barrier from here on)
@@ -234,9 +213,8 @@ __global__ __launch_bounds__(LR_THREADS) void lora_prompt_expand_kernel(_Float16
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
                         const int t = 4 * tq + k;
-                        const h2 old = __builtin_bit_cast(h2, o[t]);
-                        const float y0 = as_f32(__builtin_fmaf(sc, acc0[k], (float)old[0])), y1 = as_f32(__builtin_fmaf(sc, acc1[k], (float)old[1]));
-                        if (mine && blk * LR_TILE + t < rows) *reinterpret_cast<u32*>(ob + (blk * LR_TILE + t) * out_stride) = pack_h2(y0, y1);
+                        const u32 y = lora_land(o[t], sc, acc0[k], acc1[k]);
+                        if (mine && blk * LR_TILE + t < rows) *reinterpret_cast<u32*>(ob + (blk * LR_TILE + t) * out_stride) = y;
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -269,38 +247,26 @@ void launch_expand(dim3 grid, size_t lds, hipStream_t stream, _Float16* out, lon
 
 }  // namespace
 
-extern "C" int qs_lora_rows_prompt_run(int tiles, int kslices) {
-    QS_REQUIRE(tiles >= 1 && kslices >= 1, "lora_rows_prompt_run: tiles=%d, K slices=%d (>= 1)", tiles, kslices);
-    return lora_plan::prompt_run(tiles, kslices);
-}
-
-extern "C" int qs_lora_rows_form_for_rank(int form, int r) {
-    QS_REQUIRE(form >= 0 && form <= (int)lora_plan::LORA_PROMPT && rank_ok(r), "lora_rows_form_for_rank: form=%d (0 .. 2), r=%d (8, 16, 32 or 64)", form, r);
-    return (int)lora_plan::planned_for_rank((lora_plan::LoraForm)form, r);
-}
-
+// (the planner's entry points of this form, qs_lora_rows_prompt_run and qs_lora_rows_form_for_rank, stand with the others in lora_rows.hip)
 extern "C" int qs_lora_rows_prompt(void* out, int64_t out_stride, const int8_t* x, int64_t x_stride, const void* x_scale, const void* A,
                                    const void* B, const float* scaling, const int32_t* seq_adapter, int slots, int T, int K, int N, int r,
                                    int rows_per_seq, int nseg, int seg_end0, int seg_end1, int seg_end2, void* workspace,
                                    int64_t workspace_size, qs_stream_t stream) {
-    const int ends[LR_MAX_SEG] = {seg_end0, seg_end1, seg_end2};
-    int rc = lora_check_args("lora_rows_prompt", out, out_stride, x, x_stride, x_scale, A, B, scaling, seq_adapter, slots, T, K, N, r,
-                             rows_per_seq, nseg, ends, workspace, workspace_size);
+    LoraCall c;
+    int rc = lora_prologue("lora_rows_prompt", c, out, out_stride, x, x_stride, x_scale, A, B, scaling, seq_adapter, slots, T, K, N, r,
+                           rows_per_seq, nseg, seg_end0, seg_end1, seg_end2, workspace, workspace_size);
     if (rc != QS_OK) return rc;
     const char* why = lora_plan::prompt_refusal(T, rows_per_seq, slots);
     QS_REQUIRE(!why, "lora_rows_prompt: T=%d, rows_per_seq=%d, slots=%d: %s", T, rows_per_seq, slots, why);
     if (T == 0) return QS_OK;
-    const int R = nseg * r, tps = (rows_per_seq + LP_TILE - 1) / LP_TILE, tiles = lora_plan::prompt_tiles(T, rows_per_seq);
-    const int kslices = (K + LR_KSLICE - 1) / LR_KSLICE, nslices = (N + LR_NSLICE - 1) / LR_NSLICE;
-    const int run = lora_plan::prompt_run(tiles, kslices);
-    const int e0 = nseg >= 2 ? ends[0] : INT32_MAX, e1 = nseg >= 3 ? ends[1] : INT32_MAX;
+    const int R = c.R, tps = (rows_per_seq + LP_TILE - 1) / LP_TILE, tiles = lora_plan::prompt_tiles(T, rows_per_seq);
+    const int run = lora_plan::prompt_run(tiles, c.kslices);
     // rank groups: the R / 16 (rounded up) rank tiles split evenly over as few groups of at most four (LR_JGROUP rows) as hold them
     const int jtiles = (R + 15) / 16, jgroups = (jtiles + 3) / 4, njt = (jtiles + jgroups - 1) / jgroups;
-    const dim3 sgrid(tiles, (kslices + run - 1) / run, jgroups);
+    const dim3 sgrid(tiles, (c.kslices + run - 1) / run, jgroups);
     const hipStream_t st = (hipStream_t)stream;
 #define QS_SHRINK(NJT)                                                                                                                    \
-    launch_shrink<NJT>(sgrid, st, x, (long long)x_stride, (const _Float16*)A, seq_adapter, slots, K, R, rows_per_seq, tps, T, run, \
-                       (float*)workspace)
+    launch_shrink<NJT>(sgrid, st, x, (long long)x_stride, c.A, seq_adapter, slots, K, R, rows_per_seq, tps, T, run, c.ws)
     switch (njt) {
         case 1: QS_SHRINK(1); break;
         case 2: QS_SHRINK(2); break;
@@ -310,11 +276,11 @@ extern "C" int qs_lora_rows_prompt(void* out, int64_t out_stride, const int8_t* 
 #undef QS_SHRINK
     rc = qs_launch_status("lora_rows_prompt (shrink)");
     if (rc != QS_OK) return rc;
-    const dim3 egrid(tiles, lora_plan::prompt_expand_ysplit(tiles, nslices));
+    const dim3 egrid(tiles, lora_plan::prompt_expand_ysplit(tiles, c.nslices));
     const size_t lds = (size_t)LP_TILE * R * sizeof(float);
 #define QS_EXPAND(RK)                                                                                                                       \
-    launch_expand<RK>(egrid, lds, st, (_Float16*)out, (long long)out_stride, (const _Float16*)x_scale, (const _Float16*)B, scaling, seq_adapter, \
-                      slots, N, R, rows_per_seq, tps, T, kslices, e0, e1, (const float*)workspace)
+    launch_expand<RK>(egrid, lds, st, c.out, (long long)out_stride, c.x_scale, c.B, scaling, seq_adapter, slots, N, R, rows_per_seq, tps, T, \
+                      c.kslices, c.e0, c.e1, c.ws)
     switch (r) {
         case 8: QS_EXPAND(8); break;
         case 16: QS_EXPAND(16); break;

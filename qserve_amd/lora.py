@@ -8,11 +8,12 @@ GEMM, per row, on the quantised activations that GEMM read - capturable in a hip
                 (`load`) in the row order qserve_amd.loader fuses the base weights in, zeroed again by `unload`.
 
     rows_form   the kernel form `lora_rows` takes for a call: "rows" (a tile is up to 16 rows of one sequence; csrc/lora_rows.hip),
-                "grouped" (a tile is 16 rows of one adapter, wherever they sit in the batch; csrc/lora_grouped.hip) or "prompt" (a
+                "grouped" (a tile is 16 rows of one adapter, wherever they sit in the batch; csrc/lora_rows.hip too) or "prompt" (a
                 tile is up to 64 rows of one sequence, for prompt passes; csrc/lora_prompt.hip).  The same bits.
 
 include/qserve_amd.h (`qs_lora_rows`) has the rule; a float64 numpy restatement is tests/_lora_cases.py.  Backed by
-qserve_amd/csrc/lora_rows.hip, lora_grouped.hip and lora_prompt.hip; the choice between them is csrc/lora_plan.h.  DecodeEngine.enable_lora / load_lora / set_lora put it behind the four linears of every layer."""
+qserve_amd/csrc/lora_rows.hip (the rows and the grouped form) and lora_prompt.hip; the choice between them is
+csrc/lora_plan.h, the bits of every form are pinned by tests/golden/lora_bits.json.  DecodeEngine.enable_lora / load_lora / set_lora put it behind the four linears of every layer."""
 import re
 
 import torch

@@ -1,4 +1,4 @@
-"""The grouped form of the LoRA row update (`lora.lora_rows(form="grouped")`, csrc/lora_grouped.hip) against the rows form, in ONE run
+"""The grouped form of the LoRA row update (`lora.lora_rows(form="grouped")`, csrc/lora_rows.hip) against the rows form, in ONE run
 (no pass / fail threshold; figures only - csrc/lora_plan.h takes its constants from the "S sweep" section):
 
   1. per call, rows form and grouped form in alternation, on the four linears of a Llama-3-8B layer (qkv 4096 -> 6144 in three
@@ -88,7 +88,7 @@ def main():
         ws = torch.empty((loramod.workspace_bytes(T, K, r, len(ends)),), dtype=torch.uint8, device=dev)
         ids = (torch.arange(S, device=dev, dtype=torch.int32) * 7 + 3) % distinct       # (interleaved: a group's rows are not adjacent)
         graphs = {}
-        for form in loramod.FORMS:
+        for form in ("rows", "grouped"):                       # (not loramod.FORMS: the prompt form refuses rows_per_seq < 16)
             for _ in range(2):
                 loramod.lora_rows(out, x, x_scale, A, B, scaling, ids, rps, ends, workspace=ws, form=form)
             torch.cuda.synchronize()

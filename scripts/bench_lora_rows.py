@@ -1,4 +1,4 @@
-"""What per-sequence LoRA adapters cost (`qs_lora_rows`, DecodeEngine.set_lora), in ONE run (no pass / fail threshold; figures only):
+"""What per-sequence LoRA adapters cost (`qs_lora_rows`, csrc/lora_rows.hip; DecodeEngine.set_lora), in ONE run (no pass / fail threshold; figures only):
 
   1. the lora_rows call (two launches: shrink + expand) on the four linears of a Llama-3-8B layer - qkv 4096 -> 6144 in three segments,
      o 4096 -> 4096, gate_up 4096 -> 28672 in two segments, down 14336 -> 4096 - at T = 64 rows (a decode step at B = 64, one row per

@@ -8,6 +8,10 @@ column n in segment g:
 The oracle evaluates it in float64 and returns, next to y, the magnitude M = scaling * sum_j |B| * x_scale * sum_k |A| |x| of the
 tolerance  |got - y| <= 2^-11 |y| + 2^-24 + 2 (K + r + 4) 2^-24 M:  the first two terms are the final fp16 rounding (half an ulp of a
 normal, half a subnormal step), the last a float32 summation of exact fp16 x int8 products in any order, with the two scalings."""
+import hashlib
+import json
+import os
+
 import numpy as np
 
 SENTINEL_H = np.float16(-1234.0)
@@ -87,6 +91,41 @@ def views(c):
 def case_oracle(c):
     out, x = views(c)
     return oracle(out, x, c["x_scale"], c["A"], c["B"], c["scaling"], c["seq_adapter"], c["rows_per_seq"], c["seg_ends"])
+
+
+# ---- the recorded bits -------------------------------------------------------------------------------------------------------------
+# tests/golden/lora_bits.json: form -> case name -> {"inputs": SHA-256 of the case's inputs, "out_store": SHA-256 of the whole out_store
+# after the call}, recorded by scripts/record_lora_bits.py with the library of the commit its docstring names.  The GPU tests of the
+# three forms compare what they computed anyway against it: a kernel edit or a compiler update that moves one bit of any form fails.
+BITS_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "lora_bits.json")
+
+
+def _sha256(arrays):
+    h = hashlib.sha256()
+    for a in arrays:
+        a = np.ascontiguousarray(a)
+        h.update(f"{a.dtype.str}{a.shape}".encode())
+        h.update(a.tobytes())
+    return h.hexdigest()
+
+
+def input_digest(c):
+    """SHA-256 of everything a case hands to the call: the tensors (stores included, with their sentinels) and the scalar arguments."""
+    scalars = np.asarray([c["T"], c["rows_per_seq"], c["K"], c["N"], c["r"], c["slots"], *c["seg_ends"]], dtype=np.int64)
+    return _sha256([scalars] + [c[k] for k in ("out_store", "x_store", "x_scale", "A", "B", "scaling", "seq_adapter")])
+
+
+def store_digest(store):
+    """SHA-256 of a whole out_store (numpy fp16, guard rows and padding included)."""
+    return _sha256([store])
+
+
+def assert_recorded_bits(form, name, c, got_store):
+    """`got_store`, the out_store of case `c` after the call under `form`, has the recorded bits."""
+    with open(BITS_FILE) as f:
+        rec = json.load(f)[form][name]
+    assert input_digest(c) == rec["inputs"], f"{form} / {name}: inputs drifted, re-record at the parent (scripts/record_lora_bits.py)"
+    assert store_digest(got_store) == rec["out_store"], f"{form} / {name}: out_store differs from the recorded bits"
 
 
 # ---- synthetic adapters under PEFT's names ------------------------------------------------------------------------------------------

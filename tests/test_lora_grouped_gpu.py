@@ -1,8 +1,9 @@
-"""`lora.lora_rows(..., form="grouped")` on the GPU: tiles of one adapter's rows, found on the device (csrc/lora_grouped.hip).  Every
+"""`lora.lora_rows(..., form="grouped")` on the GPU: tiles of one adapter's rows, found on the device (csrc/lora_rows.hip).  Every
 case against the float64 oracle of tests/_lora_cases.py under its derived tolerance
     |got - y| <= 2^-11 |y| + 2^-24 + 2 (K + r + 4) 2^-24 M,   M = scaling sum_j |B| x_scale sum_k |A| |x|
-and bit for bit against form="rows" on a fresh copy; x and out are views into sentinel-filled stores (a guard row on either side,
-padding behind every row) that must come back untouched, rows of an id out of range must keep their bits.  The cases are the smallest
+and bit for bit against form="rows" on a fresh copy and against the bits recorded in tests/golden/lora_bits.json; x and out are views
+into sentinel-filled stores (a guard row on either side, padding behind every row) that must come back untouched, rows of an id out
+of range must keep their bits.  The cases are the smallest
 shapes at which the form can go wrong; what each probes stands beside it.  A captured call must follow ids changed in place."""
 import numpy as np
 import pytest
@@ -79,6 +80,7 @@ def test_grouped_against_the_oracle_and_the_rows_form(gpu, lora, name):
     assert np.array_equal(after[:, N:], before[:, N:]), "the padding behind out's rows changed"
     assert np.array_equal(x_store.cpu().numpy(), c["x_store"]), "x changed"
     assert not active.any() or (after[1:T + 1, :N][active] != before[1:T + 1, :N][active]).mean() > 0.5, "the adapters hardly changed their rows"
+    K.assert_recorded_bits("grouped", name, c, got_store)
 
 
 def test_a_captured_call_follows_ids_changed_in_place(gpu, lora):

@@ -3,8 +3,8 @@
 on every case of _lora_cases.SHAPES: T in {1, 3, 64, 130} (and 36, for rows_per_seq = 12, which divides none of those), rows_per_seq
 in {1, 3, 5, 12, 65}, K in {128, 256, 4096, 14336}, N = 64 / 1024 in three segments / 28672 in two, every r, slots 1 and 4, adapters mixed
 with -1, `slots` and -7.  x and out are views into sentinel-filled stores (a guard row on either side, padding behind every row) that must
-come back untouched; rows of an adapter out of range must keep their bits.  Two runs and a graph replay must agree bit for bit; a zeroed
-slot must leave the values as they are."""
+come back untouched; rows of an adapter out of range must keep their bits.  Every case's out_store must have the bits recorded in
+tests/golden/lora_bits.json.  Two runs and a graph replay must agree bit for bit; a zeroed slot must leave the values as they are."""
 import numpy as np
 import pytest
 import torch
@@ -52,6 +52,7 @@ def test_rows_against_the_oracle(gpu, lora, name):
     if active.any():
         changed = (after[1:T + 1, :N][active] != before[1:T + 1, :N][active]).mean()
         assert changed > 0.5, "the adapters hardly changed their rows"
+    K.assert_recorded_bits("rows", name, c, got_store)
 
 
 @pytest.mark.parametrize("name", ["step_64", "two_long_seqs", "mlp_wide"])
