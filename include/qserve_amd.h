@@ -786,6 +786,51 @@ int qs_logprob_rows(const void* logits, int64_t row_stride, int n_vocab, const i
                     float* out_top_lp, int64_t out_stride, int out_cols, qs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Scoring given tokens (no reference counterpart): the log-probability of targets[r] under the un-quantised fp16 lm_head applied to row
+ * r of `hidden`, the greedy token and the log-sum-exp, WITHOUT a logit matrix - no [rows, n_vocab] array exists, not in global memory
+ * and not in the workspace.  What a prompt's perplexity, loglikelihood / is_greedy requests and prompt_logprobs need.  Capturable,
+ * nothing allocated, nothing read back.  (csrc/score_rows.hip; geometry csrc/score_plan.h; DESIGN.md "Scoring prompts".)
+ *
+ * hidden fp16 [rows, K] with row stride hidden_stride (elements); lm_head fp16 [n_vocab, K] with row stride lm_head_stride; targets
+ * int32 [rows]; out_lp float [rows]; out_greedy int32 [rows] or null; out_lse float [rows] or null.
+ *
+ * Per row r, with the logits x_i = hidden[r] . lm_head[i], i in [0, n_vocab), accumulated in fp32 on the fp16 matrix cores (k in
+ * ascending blocks of 16) and never rounded to fp16:
+ *     m = max x;  S = sum exp(x_i - m) in fp32 (hardware exp2, partial sums per tile of 256 columns and per split, merged in a fixed order);
+ *     out_lse    = m + log S;
+ *     out_lp     = (x_t - m) - log S for t = targets[r]; t outside [0, n_vocab): NaN, and no address is formed from t (callers use t = -1
+ *                  for "do not score");
+ *     out_greedy = the lowest index among the maxima of x.
+ * Two columns whose lm_head rows are bit-equal have bit-equal logits, wherever they lie.  Rows and columns beyond the edge of a tile are
+ * masked by the kernel: the caller pads nothing; bytes between K and a row stride are never read.  Rows with a NaN or an infinite logit
+ * are the caller's error; the call still ends.  Every merge has a fixed order and there are no atomics: bit-identical run to run and eager
+ * against graph replay.  Against the exact values: |x_i - exact| <= 2 (K + 4) 2^-24 sum_k |h_k w_ik| (fp16 products are exact in fp32;
+ * one rounding per accumulation step), and on top of the logits' error |lp - exact| <= 1e-5 + 2^-21 |lp| for the softmax stage.
+ *
+ * Two launches: the walk - a workgroup of 512 threads per (128 rows, split of the vocabulary), one 16-byte record per (row, split) into
+ * `workspace` - and a merge of a row's records in ascending split order.  qs_score_rows_workspace_bytes(rows, n_vocab, K, splits) is
+ * the size `workspace` needs (splits = 0: the planner's count, what qs_score_rows uses); the workspace carries nothing between calls.
+ * qs_score_rows_split is the same call with the split count given (0: planned; otherwise cut to 1 .. min(vocabulary tiles, 64) and
+ * normalised so that no split is empty) - the results' roundings depend on the count, everything else does not.
+ * qs_score_rows_plan: plan8 = {tile rows, tile columns, ring depth, row tiles, vocabulary tiles, splits, tiles per split, workspace
+ * bytes} - a pure function of its arguments, runs without a GPU.  qs_score_rows_grid_position: the (row tile, split) workgroup `id`
+ * of the walk takes, 1; or 0 for a surplus workgroup (-1, -1) - pure as well.
+ *
+ * QS_EINVAL before any device call: hidden, lm_head, targets, out_lp or workspace null; K not a positive multiple of 64; n_vocab < 8 or
+ * > 2^22; rows < 0 or > 2^24; a row stride < K, not a multiple of 8 (16 bytes) or > 2^22; hidden, lm_head or workspace not 16-byte, an
+ * int32 / float array not 4-byte aligned; workspace_bytes below the plan's.  rows == 0: QS_OK, no launch.
+ * ---------------------------------------------------------------------------------------------------------- */
+int qs_score_rows(const void* hidden, int64_t hidden_stride, const void* lm_head, int64_t lm_head_stride, const int32_t* targets, int rows,
+                  int n_vocab, int K, float* out_lp, int32_t* out_greedy, float* out_lse, void* workspace, int64_t workspace_bytes,
+                  qs_stream_t stream);
+int qs_score_rows_split(const void* hidden, int64_t hidden_stride, const void* lm_head, int64_t lm_head_stride, const int32_t* targets,
+                        int rows, int n_vocab, int K, int splits, float* out_lp, int32_t* out_greedy, float* out_lse, void* workspace,
+                        int64_t workspace_bytes, qs_stream_t stream);
+int64_t qs_score_rows_workspace_bytes(int rows, int n_vocab, int K, int splits);
+int qs_score_rows_plan(int rows, int n_vocab, int K, int splits, long long* plan8);
+int qs_score_rows_grid_position(int rows, int n_vocab, int K, int splits, int id, int* row_tile, int* split);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Constrained decoding (no reference counterpart): a TOKEN AUTOMATON restricts what every sequence may emit - a regular expression, a
  * choice list, a JSON shape of bounded depth, compiled on the host into two device tables - and the three entries below apply it inside
  * the decode round, on the device: capturable, nothing allocated, nothing read back, no scratch.  Integer rules only: bit-identical run

@@ -94,6 +94,11 @@ SIGNATURES = {
     "qs_ngram_draft_lds_tokens": (_i, []),
     "qs_stop_update": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "qs_logprob_rows": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _i, _vp, _vp, _vp, _vp, _i64, _i, _vp]),
+    "qs_score_rows": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "qs_score_rows_split": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "qs_score_rows_workspace_bytes": (_i64, [_i, _i, _i, _i]),
+    "qs_score_rows_plan": (_i, [_i, _i, _i, _i, _vp]),
+    "qs_score_rows_grid_position": (_i, [_i, _i, _i, _i, _i, _vp, _vp]),
     "qs_constrain_node_states": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i64, _i, _i, _i, _i, _vp, _vp]),
     "qs_constrain_rows": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _i64, _i, _i, _i, _vp]),
     "qs_constrain_advance": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i64, _i, _i, _i, _i, _i, _vp]),

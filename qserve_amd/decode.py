@@ -924,7 +924,53 @@ class DecodeEngine:
                                     self.rope_base, self.int4, max_seqlen_q=n, max_past=past0 + c0)
         return attend
 
-    def _prompt_pass(self, tokens, lens, chunk, bufs, base, attend, lora_ids=None):
+    def score(self, tokens, lens=None, chunk=None):
+        """How likely is this text under the model: `prefill_chunked` over `tokens` [B, P] (chunks of `chunk` columns; None: whole) that
+        also scores every prompt token, and ends in the state that entry ends in - cache filled, first token drawn, lengths = P + 1 -, so
+        generation can go on behind a scored prompt.  -> (lp float32 [B, P], greedy bool [B, P]): lp[b, p] = the log-probability of
+        tokens[b, p] given tokens[b, :p] under the raw logits of the fp16 lm_head (no temperature, penalty or constraint enters),
+        greedy[b, p] = whether tokens[b, p] is what the greedy head would have chosen there.  Column 0 has no context: NaN / False.
+        `lens` (B ints): right-padded texts - attention is causal, so a position never sees the padding behind it; positions >= lens[b]
+        report NaN / False (they still run and fill the cache, as `prefill_chunked` would with the same tokens).
+        Every pass's rows go through the final norm and `logprobs.score_rows` (qs_score_rows: no logit matrix) with the NEXT tokens as
+        targets; a row that is the last of its chunk finds its target in the next chunk's first column.  Works under LoRA and MoE, as
+        the prompt pass does.  Single GPU, with the lm_head, no beams; refuses what every prefill entry refuses."""
+        self._prefill_entry("score")
+        assert self.tp_world == 1 and not self.vocab_parallel, "score: single GPU - under tensor parallelism the head is cut over the vocabulary"
+        assert self.with_lm_head, "score: the engine was built without the lm_head"
+        B, dev = self.B, self.dev
+        assert isinstance(tokens, torch.Tensor) and tokens.dim() == 2 and tokens.size(0) == B and tokens.size(1) >= 1 and \
+            not tokens.is_floating_point(), f"score: tokens must be an integer tensor [{B}, P]"
+        P = tokens.size(1)
+        assert P + 1 <= self.max_len, f"score: P={P} + 1 exceeds max_len={self.max_len}"
+        lens = [P] * B if lens is None else [int(n) for n in lens]
+        assert len(lens) == B and all(1 <= n <= P for n in lens), f"score: lens must be {B} values in 1 .. {P}"
+        chunk = P if chunk is None else min(int(chunk), P)
+        assert chunk >= 1
+        tokens = tokens.to(dev, torch.int64).contiguous()
+        # targets[b, p] = the token row (b, p) predicts: tokens[b, p + 1] while that is text, else -1
+        targets = torch.full((B, P), -1, dtype=torch.int32, device=dev)
+        targets[:, :P - 1] = tokens[:, 1:].to(torch.int32)
+        targets.masked_fill_(torch.arange(1, P + 1, device=dev).unsqueeze(0) >= torch.tensor(lens, device=dev).unsqueeze(1), -1)
+        lp = torch.full((B, P), float("nan"), dtype=torch.float32, device=dev)
+        greedy = torch.zeros((B, P), dtype=torch.bool, device=dev)
+
+        def score_pass(h, live, ns, c0):
+            n = ns[0]                                                    # (every sequence runs all P columns: one width per pass)
+            final = torch.empty_like(h)
+            layernorm_ops.rms_norm(final, h, self.norm_w, self.cfg["eps"])
+            tgt = targets[:, c0:c0 + n].reshape(-1)                      # sequence-major, as the pass's rows are
+            row_lp, row_greedy = logprobsmod.score_rows(final, self.lm_head, tgt)
+            m = min(n, P - 1 - c0)                                       # the row of column P - 1 predicts what follows the prompt
+            lp[:, c0 + 1:c0 + 1 + m] = row_lp.view(B, n)[:, :m]
+            greedy[:, c0 + 1:c0 + 1 + m] = ((row_greedy == tgt) & (tgt >= 0)).view(B, n)[:, :m]
+
+        self._prompt_pages(P)
+        last = self._prompt_pass(tokens, [P] * B, chunk, self._prompt_buffers(B * chunk), 0, self._append_over(self.tables), on_rows=score_pass)
+        self._prompt_head(last, P)
+        return lp, greedy
+
+    def _prompt_pass(self, tokens, lens, chunk, bufs, base, attend, lora_ids=None, on_rows=None):
         """THE chunked prompt pass: the layer stack over R sequences of possibly different lengths, `tokens` [R, >= max(lens)] on the
         device (padded; sequence r is tokens[r, :lens[r]]) and `lens` a host list, in passes of `chunk` columns: pass c0 runs
         tokens[r, c0 : c0 + chunk] of every sequence that has a token left - one with none is left out -, behind a past of base + c0
@@ -932,8 +978,10 @@ class DecodeEngine:
         with cu_seqlens from the pass's lengths.  attend(li, qkv, cu_seqlens, past_lens, n, c0, live) -> fp16 [T, H, 128]: the append
         attention of layer li over the pass's T rows; n: the longest sequence of the pass; `live`: the sequences in it, int64 indices
         on the device, or None when all are.  `bufs`: _prompt_buffers of at least R * chunk rows.  `lora_ids`: the adapter of every
-        SEQUENCE int32 [R], handed on per token (None: the engine's, which needs equal lengths).  -> every sequence's last hidden row,
-        gathered where the sequence ends, [R, hid]."""
+        SEQUENCE int32 [R], handed on per token (None: the engine's, which needs equal lengths).  `on_rows` (None: nothing is called or
+        launched): on_rows(h, live, ns, c0) after every pass's layer stack - h fp16 [T, hid] the pass's rows before the final norm,
+        sequence-major: ns[j] rows of sequence live[j], columns c0 .. c0 + ns[j] - 1; h is reused by the next pass.  -> every
+        sequence's last hidden row, gathered where the sequence ends, [R, hid]."""
         R, dev = len(lens), self.dev
         last = torch.empty((R, self.hid), dtype=torch.float16, device=dev)
         for c0 in range(0, max(lens), chunk):
@@ -949,6 +997,8 @@ class DecodeEngine:
             ids = None if lora_ids is None else torch.repeat_interleave(     # the adapter of every token of this pass
                 lora_ids if live_t is None else torch.index_select(lora_ids, 0, live_t), torch.tensor(ns, dtype=torch.int64, device=dev), output_size=T)
             self._prompt_layers(h, bufs, lambda li, qkv: attend(li, qkv, cu, past, n, c0, live_t).reshape(T, -1), ids)
+            if on_rows is not None:
+                on_rows(h, live, ns, c0)
             ended = [(r, cu_h[j + 1] - 1) for j, r in enumerate(live) if c0 + ns[j] == lens[r]]
             if ended:
                 last[torch.tensor([r for r, _ in ended], dtype=torch.int64, device=dev)] = \

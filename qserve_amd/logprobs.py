@@ -7,12 +7,16 @@ reproducible and capturable in a hipGraph.
                    count), each scored for the token that follows it - the next node on the path, or the bonus token -, written at the
                    token's text position
     new_logs       the four output tensors, filled with what a column nobody wrote holds (NaN, 0, -1, NaN)
+    score_rows     GIVEN tokens scored from hidden rows and the lm_head itself, with no logit matrix (qs_score_rows, csrc/score_rows.hip):
+                   what DecodeEngine.score runs behind a prompt pass; score_plan: its geometry
     MAX_TOP        entries of a top list
 
 include/qserve_amd.h (`qs_logprob_rows`) has the contract: the values describe softmax(logits / T) - top-k and top-p do not enter -, all
 sums are exact integer sums (bit-identical run to run and under graph replay), rank and ids are decided by integer keys alone, a tie
 class of any size is cut by index.  Backed by qserve_amd/csrc/logprob_rows.hip.  DecodeEngine.set_logprobs puts it behind the engine's
 heads."""
+import ctypes as C
+
 import torch
 
 from .backend._util import check, expect, guard, lib, ptr, stream
@@ -122,6 +126,57 @@ def logprob_rows(logits, ids, temperature=1.0, top=0, out=None):
                                       top, ptr(lp), ptr(rank), ptr(tids), ptr(tlp), stride, 1, stream()), what)
     sq = lambda t: None if t is None else t.squeeze(1)   # noqa: E731
     return sq(lp), sq(rank), sq(tids), sq(tlp)
+
+
+def score_plan(rows, n_vocab, K, splits=0):
+    """What `score_rows` launches for rows x n_vocab at depth K (csrc/score_plan.h through qs_score_rows_plan; pure, runs without a GPU):
+    dict(tile_rows, tile_vocab, depth, row_tiles, vocab_tiles, splits, tiles_per_split, workspace_bytes).  `splits` > 0 forces a count."""
+    buf = (C.c_longlong * 8)()
+    check(lib.qs_score_rows_plan(int(rows), int(n_vocab), int(K), int(splits), C.cast(buf, C.c_void_p)), "logprobs.score_plan")
+    return dict(zip(("tile_rows", "tile_vocab", "depth", "row_tiles", "vocab_tiles", "splits", "tiles_per_split", "workspace_bytes"), buf))
+
+
+_score_workspace = {}           # device -> uint8 tensor, re-created only when a call needs more
+
+
+def score_rows(hidden, lm_head, targets, greedy=True, lse=False, _splits=0):
+    """Row r of `hidden` (fp16 [rows, K], K a multiple of 64) scored for targets[r] (int32 [rows]; -1: do not score) under the fp16
+    `lm_head` [V, K], V in 8 .. 2^22, with no [rows, V] array anywhere (qs_score_rows).  Both matrices: a unit column stride and a row
+    stride that is a multiple of 8 and >= K - views of wider buffers are fine.  -> (lp float32 [rows], greedy int32 [rows] or None[, lse
+    float32 [rows]]): lp = the log-softmax of the fp32 logits at the target (NaN for a target outside [0, V)), greedy = the lowest index
+    among the row's maxima, lse = the log-sum-exp.  The workspace (a record per row and vocabulary split) is kept per device and grows
+    only; a captured call holds on to the one it was captured with, so capture after the largest call.  `_splits`: a forced split count
+    (tests)."""
+    what = "logprobs.score_rows"
+    for t, name in ((hidden, "hidden"), (lm_head, "lm_head")):
+        _typed(t, torch.float16, name)
+        if t.dim() != 2 or (t.size(1) > 1 and t.stride(1) != 1):
+            raise RuntimeError(f"{what}: {name} must be 2-d with a unit column stride, got {tuple(t.shape)}, strides {t.stride()}")
+    (rows, K), (V, K2) = hidden.shape, lm_head.shape
+    if K != K2 or K < 64 or K % 64 != 0:
+        raise RuntimeError(f"{what}: hidden is [{rows}, {K}], lm_head [{V}, {K2}]: one K, a multiple of 64")
+    if not 8 <= V <= 1 << 22:
+        raise RuntimeError(f"{what}: V={V} (8 .. {1 << 22})")
+    hs, ws = (hidden.stride(0) if rows > 1 else K), (lm_head.stride(0) if V > 1 else K)
+    if hs < K or ws < K or hs % 8 != 0 or ws % 8 != 0:
+        raise RuntimeError(f"{what}: row strides {hs} / {ws} must be multiples of 8 that are >= K={K}")
+    dev = hidden.device
+    _rows(targets, torch.int32, (rows,), "targets", dev, what)
+    _on_device(((hidden, "hidden", False), (lm_head, "lm_head", False), (targets, "targets", True)))
+    if lm_head.device != dev:
+        raise RuntimeError(f"{what}: lm_head is on {lm_head.device}, hidden on {dev}")
+    lp = torch.empty((rows,), dtype=torch.float32, device=dev)
+    gr = torch.empty((rows,), dtype=torch.int32, device=dev) if greedy else None
+    ls = torch.empty((rows,), dtype=torch.float32, device=dev) if lse else None
+    if rows > 0:
+        need = int(lib.qs_score_rows_workspace_bytes(rows, V, K, int(_splits)))
+        work = _score_workspace.get(dev)
+        if work is None or work.numel() < need:
+            work = _score_workspace[dev] = torch.empty((need,), dtype=torch.uint8, device=dev)
+        with guard(hidden):
+            check(lib.qs_score_rows_split(ptr(hidden), hs, ptr(lm_head), ws, ptr(targets), rows, V, K, int(_splits), ptr(lp), ptr(gr), ptr(ls),
+                                          ptr(work), work.numel(), stream()), what)
+    return (lp, gr, ls) if lse else (lp, gr)
 
 
 def logprob_path(logits, node_tokens, accept_idx, accept_lens, next_token, lengths=None, temperature=1.0, top=0, out=None, cols=None):
