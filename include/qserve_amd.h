@@ -284,6 +284,31 @@ void qs_set_attention_variant(int variant);
 int qs_attention_plan(int batch, int num_heads, int num_kv_heads, int max_blocks, int timestep, int int4_kv_cache,
                       int* plan3);
 
+/* Decode attention for page tables of any length (no reference counterpart): the contract, arguments, layouts and side effect of
+ * qs_single_query_attention - the new token's K / V slot receives the same bits -, served by a split-KV matrix-core kernel whose
+ * page ranges are cut ON THE DEVICE from length_per_sample (csrc/attention_long.hip).  qs_single_query_attention sends tables of
+ * more than 192 entries (12 288 tokens) to its VALU kernel, one workgroup per sequence and KV head; this entry is for those, and
+ * for short texts under such tables: a sequence's cached pages go evenly to at most `splits` workgroups per KV head, at least
+ * `min_pages` pages each, and the workgroups left over write empty records.  num_splits = 0: the planner's count for
+ * (batch, heads, max_blocks) - never the lengths, so a captured launch stays valid while they grow; >= 1: that count, cut to 64.
+ * Either is cut to what the split-KV workspace holds; with one range, and where the workspace cannot be had (its first use inside
+ * a stream capture: allocate it before, qs_stream_scratch_bind does), `out` is written directly, without workspace or merge.
+ * Results are bit-identical run to run and under graph replay (the merge adds the records in range order).
+ * Supported: Dh = 128, tokens_per_block = 64, kv_cache_with_zeros, KV4 and KV8, num_heads / num_kv_heads in 1 .. 8, any
+ * max_blocks > 0, batch and num_kv_heads <= 65535; QS_ENOSUP otherwise.  Uses the split-KV workspace (same stream rule as above). */
+int qs_single_query_attention_long(const void* q, const void* k, const void* v, const int64_t* kv_pointers,
+                                   const int32_t* length_per_sample, void* out, int batch, int num_heads, int num_kv_heads,
+                                   int head_dim, int64_t q_stride0, int64_t kv_stride0, int max_blocks, int memory_max_seqlen,
+                                   int tokens_per_block, int size_per_token, int timestep, int rotary_embedding_dim,
+                                   float rotary_base, int neox_rotary_style, int int4_kv_cache, int kv_cache_with_zeros,
+                                   int num_splits, qs_stream_t stream);
+
+/* Plan only (no device access): what qs_single_query_attention_long launches when it is asked to choose, plan3 = {splits, waves per
+ * workgroup, min_pages}: the grid is (num_kv_heads, batch, splits); range z of a sequence with n cached pages is pages
+ * [z n / r, (z + 1) n / r) with r = clamp(n / min_pages, 1, splits), and the new token belongs to range r - 1.  `splits` assumes
+ * the split-KV workspace.  All zero for batch = 0. */
+int qs_single_query_attention_long_plan(int batch, int num_heads, int num_kv_heads, int max_blocks, int int4_kv_cache, int* plan3);
+
 /* Prefill KV writer.  Replaces qserve_backend.fused_attention.apply_bias_rope_update_kv_cache
  *   (kernels/csrc/fused_attention/update_kv_cache.h:11-27, update_kv_cache.cu:20-108).
  *   qkv half [num_tokens, (H+2Hkv)*Dh] modified in place (rotated q and k are written back);

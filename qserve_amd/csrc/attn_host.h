@@ -43,6 +43,16 @@ struct DecodeArgs {
 int qs_launch_decode_mfma(const DecodeArgs& a, const attn_plan::AttnPlan& plan);    // family 1, attention_mfma.hip
 int qs_launch_decode_mfma8(const DecodeArgs& a, const attn_plan::AttnPlan& plan);   // family 2, attention_mfma8.hip
 
+// ---- long-context decode attention (attention_long.hip): the decode record, the cache format and the wanted range count -----------
+struct DecodeLongArgs {
+    DecodeArgs d;                    // quant / fused unused: the entry has no fused quantiser
+    bool int4;
+    int batch;
+};
+// runs plan.splits ranges per (sequence, KV head) - fewer where the workspace holds fewer, one (no workspace, no merge) where it
+// cannot be had
+int qs_launch_decode_long(const DecodeLongArgs& a, const attn_plan::LongPlan& plan);
+
 // ---- append attention: the four entries' common arguments, checked ------------------------------------------------------------
 struct AppendArgs {
     const _Float16* qkv;

@@ -99,6 +99,41 @@ inline AttnPlan plan_attention(int batch, int H, int Hkv, int max_blocks, int ti
     return {2, nsplit, DECODE_WAVES_KV8, 0, 0};
 }
 
+// ---- long-context decode attention (qs_single_query_attention_long, attention_long.hip) ------------------------------------------
+// Workgroup = (KV head, sequence, range), grid (Hkv, batch, splits).  `splits` is chosen HERE, from the table's length alone (a
+// captured graph stays valid while the lengths grow); the kernel cuts a sequence's own pages evenly over at most `splits` ranges of
+// at least `min_pages` pages, so a short text under a long table runs a few short chains and the other workgroups leave empty records.
+// The split planner's "fill the CUs once" form: blocks = batch * Hkv, split until the chip is full, never below min_pages pages per
+// range at the table's length, at most MAX_SPLITS, and cut to what the workspace holds of decode_split_bytes records.
+// Fitted to scripts/bench_decode_long.py -> profiles/decode_long.txt (MI355X, H = 32, Hkv = 8; the lines named are that file's):
+//   LONG_FILL_KV4 = 512    two 78 KiB workgroups per CU x 256 CUs (the LDS budget in attention_long.hip); the append planner's FILL.
+//                          "kv4 B=8": 8 splits (512 / 64) are the best or within 0.4 % of it at 12 352, 32 768 and 131 072 tokens.
+//   LONG_FILL_KV8 = 256    one 142 KiB workgroup per CU.  "kv8 B=8": 4 splits (256 / 64) beat 8 at every context (50.1 against 59.0 us
+//                          at 12 352, 105.7 against 113.0 at 32 768); "kv8 B=1": 32 splits are the best or within 3.2 % from 12 352 on.
+//   LONG_SPLITS_CAP = 32   "kv4 B=1": the starting form's 64 splits lose to 32 at every context (131 072 tokens: 68.4 against 61.1 us,
+//                          32 768: 42.5 against 31.0, 1 024 under a 2 048-entry table: 34.8 against 21.9) - 64 records per head cost
+//                          the merge more than the shorter chains save.  A forced count may still reach MAX_SPLITS.
+//   LONG_MIN_PAGES = 2     a range of two pages still keeps two waves on one page each; its set-up is the rotation of q and its
+//                          record 520 B per head.  A STARTING value, not swept: profiles/decode_long.txt "not measured".
+// Regret left: a short text under a long table pays for the empty records of the ranges it does not use (1 024 tokens under 2 048
+// entries, B = 1: 32 splits 21.9 us KV4 / 22.3 us KV8 against 14.9 / 16.5 us un-split) - the count cannot follow the lengths.
+constexpr int LONG_WAVES = 4;
+constexpr int LONG_FILL_KV4 = 512, LONG_FILL_KV8 = 256;
+constexpr int LONG_SPLITS_CAP = 32;
+constexpr int LONG_MIN_PAGES = 2;
+struct LongPlan {
+    int splits, waves, min_pages;
+};
+inline LongPlan plan_decode_long(int batch, int Hkv, int G, int max_blocks, bool int4, size_t capacity) {
+    const long blocks = (long)batch * Hkv;
+    LongPlan p = {1, LONG_WAVES, LONG_MIN_PAGES};
+    if (blocks <= 0 || blocks >= 512) return p;
+    long s = (int4 ? LONG_FILL_KV4 : LONG_FILL_KV8) / blocks;
+    if (s > max_blocks / LONG_MIN_PAGES) s = max_blocks / LONG_MIN_PAGES;
+    p.splits = s > 1 ? fit_splits((int)s, decode_split_bytes((int)blocks, G), capacity, LONG_SPLITS_CAP) : 1;
+    return p;
+}
+
 // ---- append attention: geometry of a launch - the ONE statement of it (the plan entries and the launchers all ask here) --------
 struct AppendPlan {
     int tile_tokens, q_tiles, waves;

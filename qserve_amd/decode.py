@@ -34,6 +34,7 @@ from . import constraints as constraintsmod
 from . import drafting as draftingmod
 from . import fused as fusedmod
 from . import logprobs as logprobsmod
+from . import long_decode
 from . import lora as loramod
 from . import moe as moemod
 from . import paging as pagingmod
@@ -2036,7 +2037,13 @@ class DecodeEngine:
         cfg, B = self.cfg, self.B
         q, k, v = qkv.split([self.H * 128, self.Hkv * 128, self.Hkv * 128], dim=-1)
         q, k, v = q.reshape(B, self.H, 128), k.reshape(B, self.Hkv, 128), v.reshape(B, self.Hkv, 128)
-        if self.fuse_pairs:  # attention + invoke_quant(_fuse_sum) of its output in one call (bit-identical pair fusion)
+        if self.max_len > 12288:
+            # a table of more than 192 entries: fused_attention's dispatcher has only its VALU kernel for it - the split-KV matrix-core
+            # entry instead (long_decode.py; its ranges follow `lengths` on the device), then the quantiser as the un-fused pair
+            attn = long_decode.single_query_attention_long(q, k, v, self.tables[li], self.lengths, self.size_per_token, self.max_len,
+                                                           self.rope_base, self.int4)
+            self._quant(self.q_attn, attn.reshape(B, -1), self.q_sum, self.q_scale)
+        elif self.fuse_pairs:  # attention + invoke_quant(_fuse_sum) of its output in one call (bit-identical pair fusion)
             fusedmod.single_query_attention_quant(
                 q, k, v, self.tables[li], self.lengths, self.q_attn, self.q_scale, 8192, 64, self.size_per_token, self.max_len, 128,
                 self.rope_base, True, self.int4, True, quant_sum=self.q_sum if self.group_size == -1 else None)

@@ -32,6 +32,16 @@ def attention_plan(batch, num_heads, num_kv_heads, max_blocks, timestep, int4_kv
     return dict(family=ATTN_FAMILIES.get(buf[0], "none"), kv_splits=buf[1], waves=buf[2])
 
 
+def attention_long_plan(batch, num_heads, num_kv_heads, max_blocks, int4_kv_cache=True):
+    """-> dict(splits, waves, min_pages): what `qs_single_query_attention_long` launches when it is asked to choose
+    (`qs_single_query_attention_long_plan`): `splits` page ranges per sequence and KV head, of at least `min_pages` pages each
+    (`long_decode.page_ranges` has the cut); all zero for an empty launch."""
+    buf = (C.c_int * 3)()
+    check(lib.qs_single_query_attention_long_plan(batch, num_heads, num_kv_heads, max_blocks, int(bool(int4_kv_cache)),
+                                                  C.cast(buf, C.c_void_p)), "attention long plan")
+    return dict(splits=buf[0], waves=buf[1], min_pages=buf[2])
+
+
 def append_attention_plan(batch, max_seqlen_q, num_heads, num_kv_heads):
     """-> dict(tile_tokens, q_tiles, waves): the append attention launcher's geometry (`qs_append_attention_plan`).  One
     workgroup serves `tile_tokens` new tokens of one KV head with all its query heads; all zero for an empty launch."""
