@@ -309,6 +309,40 @@ int qs_single_query_attention_long(const void* q, const void* k, const void* v, 
  * the split-KV workspace.  All zero for batch = 0. */
 int qs_single_query_attention_long_plan(int batch, int num_heads, int num_kv_heads, int max_blocks, int int4_kv_cache, int* plan3);
 
+/* Sliding-window attention (no reference counterpart; Mistral-7B-v0.1: W = 4 096).  The rule, everywhere: with a window W >= 1 the key
+ * at position j is visible to the query at position p iff p - W < j <= p (transformers' kv_idx > q_idx - sliding_window; the token
+ * itself counts).  K / V are written for every token exactly as without a window - same bytes, same slots.
+ *   qs_single_query_attention_window  qs_single_query_attention_long (arguments, layouts, side effect, validation, workspace and
+ *                      merge rules, bit-identical results run to run and under graph replay) with `window` in front of num_splits:
+ *                      the new token of a sequence of len = length_per_sample[b] tokens attends to the cached tokens
+ *                      [max(0, len - W), len - 1) and to itself.  The page ranges are cut on the device from the WINDOW's pages
+ *                      [max(0, len - W) / 64, ceil((len - 1) / 64)), so a chain is at most W / 64 + 2 pages whatever the text's
+ *                      length; W = 1 reads no cached page.  window = 0: no window (qs_single_query_attention_long's result);
+ *                      window < 0: QS_EINVAL before any device call.  csrc/attention_window.hip.
+ *   qs_single_query_attention_window_plan  pure: plan3 = {splits, waves per workgroup, min_pages} as qs_single_query_attention_long_plan,
+ *                      from (batch, heads, max_blocks, window) alone: splits <= min(max_blocks, W / 64 + 2) / min_pages.
+ *   qs_append_attention_window  qs_append_attention (arguments, layout contract, validation) with `window` in front of the stream: row
+ *                      t of sequence b, at p = past + t, sees the cached keys [max(0, p - W + 1), past) and the new keys
+ *                      [max(past, p - W + 1), p].  One un-split launch of qs_append_attention_plan's grid; pages below the first row's
+ *                      window of a query tile are never requested.  window = 0: qs_append_attention's launch; window < 0: QS_EINVAL
+ *                      before any device call.  csrc/append_window.hip.
+ * Refused, never silently un-windowed: there is no windowed form of qs_append_attention_split, qs_append_tree_attention or
+ * qs_append_attention_shared (the Python entries raise on window > 0 with a split request, a tree mask or shared groups) and
+ * qs_flash_attn_varlen_fwd has no window (flash_attn_varlen_func(window_size=...) raises).  Not built: ring-buffer tables, releasing the
+ * pages that fell out of the window, attention sinks. */
+int qs_single_query_attention_window(const void* q, const void* k, const void* v, const int64_t* kv_pointers,
+                                     const int32_t* length_per_sample, void* out, int batch, int num_heads, int num_kv_heads,
+                                     int head_dim, int64_t q_stride0, int64_t kv_stride0, int max_blocks, int memory_max_seqlen,
+                                     int tokens_per_block, int size_per_token, int timestep, int rotary_embedding_dim,
+                                     float rotary_base, int neox_rotary_style, int int4_kv_cache, int kv_cache_with_zeros,
+                                     int window, int num_splits, qs_stream_t stream);
+int qs_single_query_attention_window_plan(int batch, int num_heads, int num_kv_heads, int max_blocks, int window, int int4_kv_cache,
+                                          int* plan3);
+int qs_append_attention_window(const void* qkv, void* out, const int32_t* cu_seqlens_q, const int32_t* past_lens,
+                               const int64_t* kv_pointers, int num_tokens, int batch, int max_seqlen_q, int max_blocks, int num_heads,
+                               int num_kv_heads, int head_dim, int64_t qkv_stride0, int64_t out_stride0, int tokens_per_block,
+                               int size_per_token, int int4_kv_cache, int kv_cache_with_zeros, int window, qs_stream_t stream);
+
 /* Prefill KV writer.  Replaces qserve_backend.fused_attention.apply_bias_rope_update_kv_cache
  *   (kernels/csrc/fused_attention/update_kv_cache.h:11-27, update_kv_cache.cu:20-108).
  *   qkv half [num_tokens, (H+2Hkv)*Dh] modified in place (rotated q and k are written back);
@@ -377,7 +411,8 @@ int qs_silu_and_mul_quant(int8_t* out, const void* input, void* input_sum, void*
  *   k,v half [total_k, Hkv, 128] token strides k_stride0 / v_stride0
  *   out half [total_q, H, 128]   token stride o_stride0
  *   cu_seqlens_q / cu_seqlens_k int32 [batch+1] (device).  causal: bottom-right aligned when lengths differ (v2.1+).
- * head_dim must be 128; dropout, ALiBi, sliding windows and returning probabilities are not provided.
+ * head_dim must be 128; dropout, ALiBi, sliding windows and returning probabilities are not provided (a sliding-window model's
+ * prompt runs through qs_append_attention_window with past = 0).
  * Layout contract (QS_EINVAL otherwise, checked before any device call): heads contiguous (element strides (stride0, 128, 1));
  *   q, k, v   16-byte aligned; q_stride0, k_stride0, v_stride0 multiples of 8 elements, >= the token's heads (H*128 resp.
  *             Hkv*128) and < 2^24.  q, k and v may live in three buffers with three strides.  Every such stride is served with the

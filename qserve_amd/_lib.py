@@ -42,6 +42,10 @@ SIGNATURES = {
     "qs_single_query_attention_long": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i64, _i, _i, _i, _i, _i,
                                             _i, _f, _i, _i, _i, _i, _vp]),
     "qs_single_query_attention_long_plan": (_i, [_i, _i, _i, _i, _i, _vp]),
+    "qs_single_query_attention_window": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i64, _i, _i, _i, _i, _i,
+                                              _i, _f, _i, _i, _i, _i, _i, _vp]),
+    "qs_single_query_attention_window_plan": (_i, [_i, _i, _i, _i, _i, _i, _vp]),
+    "qs_append_attention_window": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i64, _i64, _i, _i, _i, _i, _i, _vp]),
     "qs_apply_bias_rope_update_kv_cache": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i,
                                                 _i, _i, _vp]),
     "qs_compute_padding_offsets": (_i, [_vp, _vp, _i, _i, _vp]),

@@ -13,6 +13,10 @@ un-split `qs_append_attention`; otherwise `qs_append_attention_split` cuts every
 workgroups of their own and merges their partial results - `num_splits` ranges when given, else what the planner
 (`qserve_amd.plan.append_attention_split_plan`) picks for the upper-bound hint `max_past`.
 
+`window` (append_attention, append): W >= 1 = sliding-window attention (Mistral) - the row at position p sees key j iff
+p - W < j <= p - through `qs_append_attention_window` (csrc/append_window.hip): un-split, from the window's first page on.  The
+writer is unchanged.  A window together with forced splits, a tree mask or shared groups raises: none of those has a windowed kernel.
+
 Shared prefixes (prefix reuse): batch-adjacent sequences whose K / V tables name the SAME pages for a common leading context form a
 group; `shared_prefix_groups` builds the three device arrays that describe the groups:
 
@@ -76,13 +80,31 @@ def append_rope_update_kv_cache(qkv, cu_seqlens_q, past_lens, kv_pointers, num_h
                                                  128, float(rope_theta), int(bool(int4_kv)), 1, stream()), what)
 
 
+def _window(window, what, **unsupported):
+    """The `window` keyword of the append entries: 0 = none, W >= 1 = sliding-window attention (row at position p sees key j iff
+    p - W < j <= p).  `unsupported`: what the call also asks for and no windowed kernel serves - refused, never silently un-windowed."""
+    w = int(window)
+    if w < 0:
+        raise RuntimeError(f"{what}: window={window} (0 = none, >= 1 = a sliding window of that many keys)")
+    asked = [name for name, on in unsupported.items() if on]
+    if w > 0 and asked:
+        raise NotImplementedError(f"{what}: window={w} together with {' and '.join(asked)} - the windowed walk (csrc/append_window.hip) is "
+                                  "un-split and linear: the window bounds the chain, and no tree-masked, shared-prefix or split-KV form "
+                                  "of it is built")
+    return w
+
+
 def append_attention(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, size_per_token, int4_kv,
-                     max_seqlen_q=None, out=None, max_past=None, num_splits=None):
+                     max_seqlen_q=None, out=None, max_past=None, num_splits=None, window=0):
     """`qkv` ALREADY rotated (append_rope_update_kv_cache) -> out fp16 [T, H, 128].  `max_seqlen_q`: an upper bound of the new
     tokens per sequence (sizes the launch; default: all T rows - correct, without a device read-back, but a larger grid).
     `max_past`: an upper bound of `past_lens` known on the host - a hint the split-KV planner sizes the launch with, never
-    something the result depends on; `num_splits` >= 1 forces that many page ranges per sequence.  Both None: the un-split call."""
+    something the result depends on; `num_splits` >= 1 forces that many page ranges per sequence.  Both None: the un-split call.
+    `window`: W >= 1 = sliding-window attention through `qs_append_attention_window` - row i, at position past + i, sees the keys
+    past + i - W + 1 .. past + i; an un-split launch that starts at the window's first page (`max_past`, a hint, is ignored; a
+    forced `num_splits` > 1 raises)."""
     what = "append.append_attention"
+    window = _window(window, what, num_splits=num_splits is not None and int(num_splits) > 1)
     batch = _check_common(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, size_per_token, int4_kv, what)
     T, H = qkv.size(0), int(num_heads)
     if out is None:
@@ -99,7 +121,9 @@ def append_attention(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_k
     args = (ptr(qkv), ptr(out), ptr(cu_seqlens_q), ptr(past_lens), ptr(kv_pointers), T, batch, min(msq, T), kv_pointers.size(-1), H,
             int(num_kv_heads), 128, qkv.stride(0), out.stride(0), 64, int(size_per_token), int(bool(int4_kv)), 1)
     with guard(qkv):
-        if max_past is None and num_splits is None:
+        if window > 0:
+            check(lib.qs_append_attention_window(*args, window, stream()), what)
+        elif max_past is None and num_splits is None:
             check(lib.qs_append_attention(*args, stream()), what)
         else:
             hint = -1 if max_past is None else min(max(int(max_past), 0), 2 ** 31 - 1)
@@ -108,12 +132,15 @@ def append_attention(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_k
 
 
 def append(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, size_per_token, rope_theta, int4_kv,
-           max_seqlen_q=None, max_past=None, num_splits=None):
-    """Writer, then attention (the two touch disjoint page slots; the attention needs the writer's in-place rotation of qkv)."""
+           max_seqlen_q=None, max_past=None, num_splits=None, window=0):
+    """Writer, then attention (the two touch disjoint page slots; the attention needs the writer's in-place rotation of qkv).
+    `window`: as for append_attention (checked before the writer touches anything); the writer is the same - every token's K / V
+    go to their slots."""
+    window = _window(window, "append.append", num_splits=num_splits is not None and int(num_splits) > 1)
     append_rope_update_kv_cache(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, size_per_token, rope_theta,
                                 int4_kv)
     return append_attention(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, size_per_token, int4_kv,
-                            max_seqlen_q=max_seqlen_q, max_past=max_past, num_splits=num_splits)
+                            max_seqlen_q=max_seqlen_q, max_past=max_past, num_splits=num_splits, window=window)
 
 
 # ---- shared prefixes ------------------------------------------------------------------------------------------------------------
@@ -142,7 +169,7 @@ def shared_prefix_groups(group_sizes, prefix_lens, device=None, batch=None):
 
 def append_attention_shared(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, size_per_token, int4_kv, groups,
                             max_seqlen_q=None, out=None, max_group_tokens=None, max_prefix=None, max_suffix_past=None,
-                            num_prefix_splits=None, num_suffix_splits=None):
+                            num_prefix_splits=None, num_suffix_splits=None, window=0):
     """`append_attention` (qkv ALREADY rotated -> out fp16 [T, H, 128]) for a batch in groups with common leading pages.  `groups`: the
     triple of `shared_prefix_groups`; the caller keeps the members' table entries below prefix / 64 equal to the first member's and
     every member's past >= its group's prefix.  `max_group_tokens`: an upper bound of a group's new tokens (default: all T rows);
@@ -150,6 +177,7 @@ def append_attention_shared(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads
     something the result depends on.  `num_prefix_splits` / `num_suffix_splits`: None asks the planner, >= 1 forces the count,
     `num_prefix_splits=-1` forces "do not share" (the split-KV call over the whole past)."""
     what = "append.append_attention_shared"
+    _window(window, what, **{"shared groups": True})      # (`window` exists here to be refused: see _window)
     batch = _check_common(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, size_per_token, int4_kv, what)
     try:
         group_offsets, prefix_lens, seq_group = groups
@@ -191,9 +219,10 @@ def append_attention_shared(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads
 
 def append_shared(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, size_per_token, rope_theta, int4_kv, groups,
                   max_seqlen_q=None, max_group_tokens=None, max_prefix=None, max_suffix_past=None, num_prefix_splits=None,
-                  num_suffix_splits=None):
+                  num_suffix_splits=None, window=0):
     """Writer, then shared-prefix attention.  The writer is append_rope_update_kv_cache: new token i goes to slot past + i >= prefix, a
     page the sequence owns - the shared pages are only read."""
+    _window(window, "append.append_shared", **{"shared groups": True})      # (before the writer touches anything)
     append_rope_update_kv_cache(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, size_per_token, rope_theta,
                                 int4_kv)
     return append_attention_shared(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, size_per_token, int4_kv, groups,
@@ -249,10 +278,11 @@ def append_tree_rope_update_kv_cache(qkv, cu_seqlens_q, past_lens, kv_pointers, 
 
 
 def append_tree_attention(qkv, cu_seqlens_q, past_lens, kv_pointers, tree_mask, num_heads, num_kv_heads, size_per_token, int4_kv,
-                          max_seqlen_q=None, out=None, max_past=None, num_splits=None):
+                          max_seqlen_q=None, out=None, max_past=None, num_splits=None, window=0):
     """`qkv` ALREADY rotated (append_tree_rope_update_kv_cache) -> out fp16 [T, H, 128].  `max_seqlen_q` (<= 64; default: min(T, 64)),
     `max_past`, `num_splits` as for append_attention; with both None the launch is un-split."""
     what = "append.append_tree_attention"
+    _window(window, what, **{"a tree mask": True})        # (`window` exists here to be refused: see _window)
     batch = _check_common(qkv, cu_seqlens_q, past_lens, kv_pointers, num_heads, num_kv_heads, size_per_token, int4_kv, what)
     _check_tree(tree_mask, qkv, max_seqlen_q, what)
     T, H = qkv.size(0), int(num_heads)
@@ -277,8 +307,9 @@ def append_tree_attention(qkv, cu_seqlens_q, past_lens, kv_pointers, tree_mask, 
 
 
 def append_tree(qkv, cu_seqlens_q, past_lens, kv_pointers, tree_mask, num_heads, num_kv_heads, size_per_token, rope_theta, int4_kv,
-                max_seqlen_q=None, max_past=None, num_splits=None):
+                max_seqlen_q=None, max_past=None, num_splits=None, window=0):
     """Tree writer, then tree attention (the attention needs the writer's in-place rotation of qkv)."""
+    _window(window, "append.append_tree", **{"a tree mask": True})          # (before the writer touches anything)
     if max_seqlen_q is not None and int(max_seqlen_q) > MAX_TREE:      # (before the writer touches anything)
         raise RuntimeError(f"append.append_tree: max_seqlen_q={max_seqlen_q}: a tree has at most {MAX_TREE} nodes per sequence")
     append_tree_rope_update_kv_cache(qkv, cu_seqlens_q, past_lens, kv_pointers, tree_mask, num_heads, num_kv_heads, size_per_token,

@@ -39,21 +39,52 @@ struct CausalNewKeys {
     }
 };
 
+// The LOWER EDGE of the walk, its third policy.  NoWindow: there is none - every use below is an `if constexpr` that folds away, the
+// kernels without a window are built from the text they always were.  SlidingWindow (append_window.hip): the row of new token tok sees
+// the key at absolute position j iff j > below + tok, below = past - W.  The kernel starts the walk at the first page and the first
+// tile of new keys that some row of its query tile can see (key0, new_tile0); a tile whose first key lies at or below the lower edge
+// of the wave's LAST row gets the mask (wave-uniform), the others - the bulk of a long window - take the unmasked path untouched.
+// The tiles a workgroup walks first can be FULLY masked for its later rows (their window starts further up): such a row's running
+// maximum is still -inf when its first visible key arrives.  The form chosen for that is the GUARDED RESCALE softmax_tile_masked
+// already has for the tree masks (flash_tile.h: m_use = 0 while the maximum is -inf, so alpha = exp2(-inf - 0) = 0 and every
+// probability is exp2(-inf) = 0 - no NaN, l and O stay exactly 0 until the row's first key), not a finite initial maximum.
+struct NoWindow {
+    static constexpr bool ON = false;
+};
+struct SlidingWindow {
+    static constexpr bool ON = true;
+    int below;         // past - W: new token tok sees absolute keys > below + tok
+    int key0;          // absolute position of the first key of ktab[0]
+    int past;          // the sequence's cached tokens = absolute position of new key 0
+    int new_tile0;     // first tile of new keys a row of the query tile can see
+};
+// a suffix: key > limit (the window's lower edge), the lane half out of the key index as in mask_keys_above
+__device__ __forceinline__ void mask_keys_below(v16f (&sacc)[NKB], int limit_of_row, int hi) {
+    const int limit = limit_of_row - 4 * hi;
+#pragma unroll
+    for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sacc[kb][r] = 32 * kb + (r & 3) + 8 * (r >> 2) > limit ? sacc[kb][r] : -INFINITY;
+}
+
 // The walk.  Rows: row r = G * token + g of query tile tok0 .. tok0 + tq - 1 (wave w owns rows 32 w .. 32 w + 31); keys: pages
 // ktab[0 .. np) / vtab[0 .. np) holding `past` cached tokens counted from ktab[0] (past >= np * BN: no slot masked), then - with_new -
 // the n new tokens' fp16 k / v rows of KV head hkv in qkv.  Leaves the un-normalised O^T, the (lazy) running maximum and this lane
 // half's sum; returns whether this wave has a row to store (false: it only staged; the caller returns - behind the last barrier).
-template <bool INT4, class NEWKEYS>
+// WINDOW (a SlidingWindow in `win`): ktab / vtab and `past` count from the window's first page, and the new-key tiles from win.new_tile0.
+template <bool INT4, class NEWKEYS, class WINDOW = NoWindow>
 __device__ __forceinline__ bool walk_keys(uint8_t* smem, const _Float16* __restrict__ qkv, const int64_t* __restrict__ ktab,
                                           const int64_t* __restrict__ vtab, int num_heads, int num_kv_heads, int hkv, int G, int q_start, int n,
                                           int tok0, int tq, int np, int past, bool with_new, int64_t qkv_stride0, float scale_log2,
-                                          const NEWKEYS& newkeys, int lane, int wave, v16f (&oacc)[4], float& m_run, float& l_run) {
+                                          const NEWKEYS& newkeys, int lane, int wave, v16f (&oacc)[4], float& m_run, float& l_run,
+                                          const WINDOW win = WINDOW()) {
     constexpr int DHB = INT4 ? DH / 2 : DH;        // bytes per cached token and head
     constexpr int NQ = INT4 ? 1 : 2;               // 16-byte loads per thread, page and tensor
     uint8_t* const s_k = smem;                           // [2][16 KiB]  } the tile images of flash_tile.h
     uint8_t* const s_vt = smem + 2 * KS_BYTES;           // [2][16 KiB]  }
     const int nk_new = newkeys.count(n, tok0, tq);       // phase 2: new keys 0 .. nk_new - 1 are visible to some row
-    const int nn = with_new ? (nk_new + BN - 1) / BN : 0;
+    int nn = with_new ? (nk_new + BN - 1) / BN : 0;
+    if constexpr (WINDOW::ON) nn = with_new ? nn - win.new_tile0 : 0;      // ... in tiles new_tile0 ..
     const int ntiles = np + nn;
 
     const int li = lane & 31, hi = lane >> 5;
@@ -146,7 +177,10 @@ __device__ __forceinline__ bool walk_keys(uint8_t* smem, const _Float16* __restr
     // (commit), or a tile of new keys straight into the other buffers
     auto issue_next = [&](int t, int nbuf) {
         if (t + 1 < np) load_page(t + 1, nbuf);
-        else if (t + 1 < ntiles) load_new(t + 1 - np, nbuf);
+        else if (t + 1 < ntiles) {
+            if constexpr (WINDOW::ON) load_new(t + 1 - np + win.new_tile0, nbuf);
+            else load_new(t + 1 - np, nbuf);
+        }
     };
     auto commit_next = [&](int t, int nbuf) {
         if (t + 1 < np) commit_page(t + 1, nbuf);
@@ -185,13 +219,25 @@ __device__ __forceinline__ bool walk_keys(uint8_t* smem, const _Float16* __restr
         // A page is masked where it holds slots >= past (the sequence's last one only: key <= past - 1 - 64 t), a tile of new keys
         // where - and how - the policy says (wave-uniform tests)
         const bool page = t < np;
-        const int j0 = (t - np) * BN;
+        int j0 = (t - np) * BN;
+        if constexpr (WINDOW::ON) j0 += win.new_tile0 * BN;
         const bool need_mask = page ? t * BN + BN > past : newkeys.needs_mask(j0, tok_first, n);
         u32 pb[NKB][2][4];
         // (ONE block of 32 selects per tile body, whatever the tile is: a block per kind meets the other behind it, and the compiler
         //  carries copies of the 32 score registers to that merge - this kernel then spills)
-        softmax_tile_masked<true>(sacc, need_mask, [&](v16f (&s)[NKB], int hi_) { newkeys.mask(s, hi_, page, past - 1 - t * BN, j0, tok_ld, n); },
-                                  lane, scale_log2, m_run, l_run, oacc, pb);
+        if constexpr (WINDOW::ON) {
+            // the tile's first key at or below the lower edge of the wave's last row -> the lower mask too: this lane's row keeps the
+            // tile's keys > lim (the masks the tile has anyway are applied with it: where they were not needed they change nothing)
+            const int k0 = page ? win.key0 + t * BN : win.past + j0;
+            const int lim = win.below + tok_ld - k0;
+            softmax_tile_masked<true>(sacc, need_mask || win.below + tok_last >= k0, [&](v16f (&s)[NKB], int hi_) {
+                newkeys.mask(s, hi_, page, past - 1 - t * BN, j0, tok_ld, n);
+                mask_keys_below(s, lim, hi_);
+            }, lane, scale_log2, m_run, l_run, oacc, pb);
+        } else {
+            softmax_tile_masked<true>(sacc, need_mask, [&](v16f (&s)[NKB], int hi_) { newkeys.mask(s, hi_, page, past - 1 - t * BN, j0, tok_ld, n); },
+                                      lane, scale_log2, m_run, l_run, oacc, pb);
+        }
         pv_tile(smem, bufc, lane, va, pb, oacc);
         commit_next(t, buf ^ 1);
         tiles_landed();
@@ -200,7 +246,10 @@ __device__ __forceinline__ bool walk_keys(uint8_t* smem, const _Float16* __restr
     // staging and the barrier (a loop of its own: a skip path that rejoins the computing path inside the loop is a control-flow
     // merge the 64 O accumulators would be carried through - flash_prefill.hip)
     int nt_w = 0;
-    if (wave_rows) nt_w = np + newkeys.tiles(tok_last, nn);
+    if (wave_rows) {
+        if constexpr (WINDOW::ON) nt_w = np + newkeys.tiles(tok_last, nn + win.new_tile0) - win.new_tile0;
+        else nt_w = np + newkeys.tiles(tok_last, nn);
+    }
     // (two copies of the body, one per LDS buffer - every ds_read address a loop-invariant register + an immediate; an odd tile
     //  count leaves from the middle: a third copy behind the loop keeps its hoisted address registers alive across the loop)
     int t = 0;

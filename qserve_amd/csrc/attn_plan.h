@@ -134,6 +134,31 @@ inline LongPlan plan_decode_long(int batch, int Hkv, int G, int max_blocks, bool
     return p;
 }
 
+// ---- sliding-window decode attention (qs_single_query_attention_window, attention_window.hip) ------------------------------------
+// The long planner's form with the chain bound of a WINDOW in place of the table's: a sequence walks the pages that hold a token of
+// [length - window, length - 1), at most window / 64 + 2 of them wherever the window starts and ends within its pages (+ 1 for each
+// ragged end), and never more than the table has.  The grid is still a function of the table and the window alone, so a captured
+// launch stays valid while the lengths grow and the window moves.  window <= 0 = no window: the table's bound.
+//   WINDOW_MIN_PAGES = 2    } STARTING values, LONG_MIN_PAGES and LONG_SPLITS_CAP taken over unmeasured: scripts/bench_window_attention.py
+//   WINDOW_SPLITS_CAP = 32  } -> profiles/window_attention.txt is the sweep that is to fix them.  The fill counts are the long
+//                             kernel's measured ones: the same workgroup, the same LDS budget.
+constexpr int WINDOW_MIN_PAGES = 2;
+constexpr int WINDOW_SPLITS_CAP = 32;
+inline int window_chain_pages(int max_blocks, int window) {
+    const long chain = window > 0 ? (long)window / PAGE + 2 : (long)max_blocks;
+    return chain < max_blocks ? (int)chain : max_blocks;
+}
+inline LongPlan plan_decode_window(int batch, int Hkv, int G, int max_blocks, int window, bool int4, size_t capacity) {
+    const long blocks = (long)batch * Hkv;
+    LongPlan p = {1, LONG_WAVES, WINDOW_MIN_PAGES};
+    if (blocks <= 0 || blocks >= 512) return p;
+    long s = (int4 ? LONG_FILL_KV4 : LONG_FILL_KV8) / blocks;
+    const int chain = window_chain_pages(max_blocks, window);
+    if (s > chain / WINDOW_MIN_PAGES) s = chain / WINDOW_MIN_PAGES;
+    p.splits = s > 1 ? fit_splits((int)s, decode_split_bytes((int)blocks, G), capacity, WINDOW_SPLITS_CAP) : 1;
+    return p;
+}
+
 // ---- append attention: geometry of a launch - the ONE statement of it (the plan entries and the launchers all ask here) --------
 struct AppendPlan {
     int tile_tokens, q_tiles, waves;

@@ -88,6 +88,9 @@ TINY = dict(name="tiny-llama", hidden=256, heads=4, kv_heads=2, inter=512, layer
 MIXTRAL_8X7B = dict(name="Mixtral-8x7B", hidden=4096, heads=32, kv_heads=8, inter=14336, layers=32, vocab=32000, rope_theta=1e6,
                     eps=1e-5, experts=8, experts_per_token=2)
 TINY_MOE = dict(TINY, name="tiny-moe", experts=4, experts_per_token=2)
+# sliding-window attention: `sliding_window` = W, the token at position p attends to positions p - W + 1 .. p (Mistral-7B-v0.1)
+MISTRAL_7B = dict(name="Mistral-7B", hidden=4096, heads=32, kv_heads=8, inter=14336, layers=32, vocab=32000, rope_theta=1e4, eps=1e-5,
+                  sliding_window=4096)
 
 
 class W4A8Linear:
@@ -202,6 +205,12 @@ class DecodeEngine:
         fork() and admit(copy_rows=) need to let several rows share the whole pages of one text ("Forks").  With both off
         the pool is uncounted and everything launches what it did."""
         self.cfg, self.B, self.dev = cfg, batch, torch.device(device)
+        # sliding-window attention (cfg["sliding_window"], Mistral): W >= 1 - the token at position p sees key j iff p - W < j <= p -, or 0:
+        # none, and the engine launches exactly what it always did.  With a window every attention of the engine is one of the two
+        # windowed entries (long_decode / append with window=); the entries that have no windowed kernel refuse (_no_window).  The
+        # cache is written and kept as without a window: no ring-buffer tables, no release of the pages that fell out of the window.
+        self.window = int(cfg.get("sliding_window") or 0)
+        assert self.window >= 0, f"DecodeEngine: sliding_window={cfg.get('sliding_window')} (None / absent = off, or a window >= 1)"
         # mixture of experts: (experts, experts per token), or None for a dense model - which launches exactly what it always did
         self.moe = (int(cfg["experts"]), int(cfg["experts_per_token"])) if cfg.get("experts") else None
         if self.moe is not None:
@@ -505,6 +514,10 @@ class DecodeEngine:
         return ids
 
     # ---- beam search (qserve_amd.beams, csrc/beam_select.hip) ------------------------------------------------------------------------
+    def _no_window(self, what, why):
+        """What the entries refuse that have no sliding-window kernel - never a silently un-windowed result."""
+        assert not self.window, f"{what}: the config has sliding_window={self.window} - {why}"
+
     def _no_beams(self, what, why):
         """What the entries refuse that cannot run while set_beams is on."""
         assert self.beams is None, f"{what}: beam search is on (set_beams) - {why}; set_beams(None) first"
@@ -870,6 +883,8 @@ class DecodeEngine:
         -> gate_up -> silu_and_mul+quant -> down -> residual.  All sequences have `prompt_len` tokens.  Leaves the
         cache filled, `hidden` = last-token states, `tokens` = first sampled token, lengths = prompt_len + 1."""
         from .flash import flash_attn_varlen_func
+        if self.window:      # the flash provider has no window: the same prompt as ONE chunk of the windowed append path, past = 0
+            return self.prefill_chunked(prompt_len, prompt_len, tokens)
         self._prefill_entry("prefill")
         cfg, B, dev = self.cfg, self.B, self.dev
         assert self.with_lm_head and prompt_len + 1 <= self.max_len
@@ -919,10 +934,12 @@ class DecodeEngine:
         """The `attend` of a _prompt_pass that is `append.append` over the pass's sequences' rows of tables[li]; `past0`: the largest
         `base` of the pass's sequences (the hint is a bound of base + c0)."""
         from . import append as appendmod      # (looked up per call: `appendmod.append` is the seam tests wrap)
-        # (max_past = c0, known on the host: a long past at a small batch is cut into page ranges - append_attention_split.hip)
+        # (max_past = c0, known on the host: a long past at a small batch is cut into page ranges - append_attention_split.hip; under a
+        #  sliding window the chain is bounded by the window and the launch un-split - append_window.hip)
         def attend(li, qkv, cu, past, n, c0, live):
+            how = dict(window=self.window) if self.window else dict(max_past=past0 + c0)
             return appendmod.append(qkv, cu, past, tables[li] if live is None else tables[li][live], self.H, self.Hkv, self.size_per_token,
-                                    self.rope_base, self.int4, max_seqlen_q=n, max_past=past0 + c0)
+                                    self.rope_base, self.int4, max_seqlen_q=n, **how)
         return attend
 
     def score(self, tokens, lens=None, chunk=None):
@@ -1018,6 +1035,7 @@ class DecodeEngine:
         chunking).  Single GPU, with the lm_head."""
         from . import append as appendmod
         self._prefill_entry("prefill_shared")
+        self._no_window("prefill_shared", "shared-prefix attention (append_shared) has no windowed form; prefill_chunked")
         cfg, B, dev = self.cfg, self.B, self.dev
         self._single_gpu("prefill_shared")
         assert self.pager is None, \
@@ -1271,6 +1289,8 @@ class DecodeEngine:
         every row's pages released; a set_stopping(stop, 0) behind it freezes every row by the at-the-limit rule.  That is the state
         admit() fills row by row and serve() starts from.  Single GPU, with the lm_head."""
         self._single_gpu("enable_drafting")
+        self._no_window("enable_drafting", "drafts are verified through tree attention (append_tree), which has no windowed form; "
+                                           "admit() and serve(), which keep their texts in this history, wait for the same kernel")
         assert 1 <= int(min_match) <= int(max_ngram) <= draftingmod.MAX_NGRAM, \
             f"enable_drafting: 1 <= min_match <= max_ngram <= {draftingmod.MAX_NGRAM}"
         assert 0 <= int(pad_token) < self.cfg["vocab"], \
@@ -1953,6 +1973,7 @@ class DecodeEngine:
         from . import append as appendmod
         par = [int(p) for p in (parents.tolist() if hasattr(parents, "tolist") else parents)]
         self._single_gpu(what)
+        self._no_window(what, "tree attention (append_tree) has no windowed form: a verification would see keys below the window")
         self._no_beams(what, "beams under speculation are out of scope: a verification keeps one path per row")
         assert 1 <= len(par) <= appendmod.MAX_TREE and par[0] == -1 and all(0 <= p < i for i, p in enumerate(par) if i), \
             f"{what}: parents[0] = -1 (the root), every other node hangs off an earlier one; at most 64 nodes"
@@ -2037,11 +2058,13 @@ class DecodeEngine:
         cfg, B = self.cfg, self.B
         q, k, v = qkv.split([self.H * 128, self.Hkv * 128, self.Hkv * 128], dim=-1)
         q, k, v = q.reshape(B, self.H, 128), k.reshape(B, self.Hkv, 128), v.reshape(B, self.Hkv, 128)
-        if self.max_len > 12288:
+        if self.window or self.max_len > 12288:
             # a table of more than 192 entries: fused_attention's dispatcher has only its VALU kernel for it - the split-KV matrix-core
-            # entry instead (long_decode.py; its ranges follow `lengths` on the device), then the quantiser as the un-fused pair
+            # entry instead (long_decode.py; its ranges follow `lengths` on the device), then the quantiser as the un-fused pair.
+            # A sliding window: the same entry's windowed form at every table length (ranges over the window's pages)
+            how = dict(window=self.window) if self.window else {}
             attn = long_decode.single_query_attention_long(q, k, v, self.tables[li], self.lengths, self.size_per_token, self.max_len,
-                                                           self.rope_base, self.int4)
+                                                           self.rope_base, self.int4, **how)
             self._quant(self.q_attn, attn.reshape(B, -1), self.q_sum, self.q_scale)
         elif self.fuse_pairs:  # attention + invoke_quant(_fuse_sum) of its output in one call (bit-identical pair fusion)
             fusedmod.single_query_attention_quant(

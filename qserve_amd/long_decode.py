@@ -20,11 +20,16 @@ def page_ranges(length, splits, min_pages):
 
 
 def single_query_attention_long(q, k, v, kv_pointers, length_per_sample, size_per_token, timestep, rotary_base, int4_kv_cache=True,
-                                memory_max_seqlen=8192, num_splits=0):
+                                memory_max_seqlen=8192, num_splits=0, window=0):
     """q [B, H, 128] / k, v [B, Hkv, 128] fp16 views of the qkv buffer (un-rotated new token), kv_pointers int64 [B, 2, max_blocks],
     length_per_sample int32 [B] (the new token included) or None (every sequence has `timestep` cached tokens) -> fp16 [B, H, 128].
     rotary_base: a base or a registered profile's key (qserve_amd/rope.py).  num_splits: 0 = the planner's count for the table, >= 1 = that
-    many page ranges per sequence and KV head (cut to 64 and to the split-KV workspace)."""
+    many page ranges per sequence and KV head (cut to 64 and to the split-KV workspace).
+    window: 0 = none; W >= 1 = sliding-window attention through `qs_single_query_attention_window` (csrc/attention_window.hip): the new
+    token at position p sees key j iff p - W < j <= p - the last W - 1 cached tokens and itself -, the page ranges are cut from the
+    window's pages, and the new token's K / V are written as without a window."""
+    if int(window) < 0:
+        raise RuntimeError(f"long_decode.single_query_attention_long: window={window} (0 = none, >= 1 = a sliding window of that many keys)")
     for n, t in (("q", q), ("k", k), ("v", v)):
         expect(t, torch.float16, n, contiguous=False)
     expect(kv_pointers, torch.int64, "kv_pointers")
@@ -39,10 +44,13 @@ def single_query_attention_long(q, k, v, kv_pointers, length_per_sample, size_pe
         if tuple(length_per_sample.shape) != (batch,):
             raise RuntimeError("length_per_sample must have shape (batch_size)")
     out = torch.empty((q.size(0), nheads, headdim), dtype=q.dtype, device=q.device)
+    args = (ptr(q), ptr(k), ptr(v), ptr(kv_pointers), ptr(length_per_sample), ptr(out), batch, nheads, nheads_kv, headdim, q.stride(0),
+            k.stride(0), kv_pointers.size(-1), int(memory_max_seqlen), 64, int(size_per_token), int(timestep), 128, float(rotary_base), 1,
+            int(bool(int4_kv_cache)), 1)
     with guard(q):
-        check(lib.qs_single_query_attention_long(ptr(q), ptr(k), ptr(v), ptr(kv_pointers), ptr(length_per_sample), ptr(out), batch, nheads,
-                                                 nheads_kv, headdim, q.stride(0), k.stride(0), kv_pointers.size(-1), int(memory_max_seqlen),
-                                                 64, int(size_per_token), int(timestep), 128, float(rotary_base), 1,
-                                                 int(bool(int4_kv_cache)), 1, int(num_splits), stream()),
-              "long_decode.single_query_attention_long")
+        if int(window) > 0:
+            check(lib.qs_single_query_attention_window(*args, int(window), int(num_splits), stream()),
+                  "long_decode.single_query_attention_long")
+        else:
+            check(lib.qs_single_query_attention_long(*args, int(num_splits), stream()), "long_decode.single_query_attention_long")
     return out

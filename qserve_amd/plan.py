@@ -42,6 +42,16 @@ def attention_long_plan(batch, num_heads, num_kv_heads, max_blocks, int4_kv_cach
     return dict(splits=buf[0], waves=buf[1], min_pages=buf[2])
 
 
+def attention_window_plan(batch, num_heads, num_kv_heads, max_blocks, window, int4_kv_cache=True):
+    """-> dict(splits, waves, min_pages): `attention_long_plan` for a sliding window of `window` keys
+    (`qs_single_query_attention_window_plan`): the ranges are cut from the window's pages, at most window // 64 + 2 of them whatever the
+    text's length, so splits <= min(max_blocks, window // 64 + 2) // min_pages; a function of the table and the window alone."""
+    buf = (C.c_int * 3)()
+    check(lib.qs_single_query_attention_window_plan(batch, num_heads, num_kv_heads, max_blocks, int(window), int(bool(int4_kv_cache)),
+                                                    C.cast(buf, C.c_void_p)), "attention window plan")
+    return dict(splits=buf[0], waves=buf[1], min_pages=buf[2])
+
+
 def append_attention_plan(batch, max_seqlen_q, num_heads, num_kv_heads):
     """-> dict(tile_tokens, q_tiles, waves): the append attention launcher's geometry (`qs_append_attention_plan`).  One
     workgroup serves `tile_tokens` new tokens of one KV head with all its query heads; all zero for an empty launch."""
