@@ -1302,6 +1302,31 @@ int qs_beam_select(const void* logits, int64_t row_stride, int n_vocab, const fl
 int qs_rows_move(const int32_t* parent, int batch, const void* const* bases, const int64_t* row_bytes, int num, int32_t* error,
                  qs_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Per-head Q/K RMSNorm (Qwen3's self_attn.q_norm / k_norm; no reference counterpart).  Between the qkv projection and the rotation every
+ * query head and every key head is normalised over its own 128 dimensions.  It cannot be folded into weights - it follows the projection,
+ * per token and per head - so it is a launch of its own, IN PLACE on the packed fp16 qkv rows, in front of whichever entry rotates them
+ * (qs_apply_bias_rope_update_kv_cache, the append and tree writers, the decode attentions).  Capturable, nothing allocated, no workspace,
+ * no atomics.  csrc/qk_norm_rows.hip.
+ *
+ * qkv fp16 [num_tokens, >= (H + 2 Hkv) * 128] with row stride qkv_stride0 (in halves; padded rows are accepted as the attention entries
+ * accept them).  The first (H + Hkv) * 128 halves of a row - the q heads, then the k heads - are rewritten; the v heads and any padding
+ * behind them are neither read nor written.  q_weight, k_weight fp16 [128]: one vector for every query head, one for every key head.
+ *
+ * The rule is transformers' Qwen3RMSNorm on an fp16 input.  Per head slice x (128 halves) with its weight w:
+ *     r = 1 / sqrt(mean(float(x)^2) + eps)      float32; the sum of the squares in a fixed order
+ *     t = fp16_rn(float(x) * r)
+ *     y = fp16_rn(float(w) * float(t))
+ * The weight is w itself, not 1 + w (Gemma's convention is not built).  eps > 0 is required, so an all-zero head stays all zero.  The
+ * result is a function of the inputs alone: bit-identical run to run and eager against graph replay.
+ *
+ * QS_EINVAL before any device call: qkv, q_weight or k_weight null; eps not > 0; num_tokens < 0; H or Hkv < 1 or H % Hkv != 0;
+ * qkv_stride0 < (H + 2 Hkv) * 128 or not a multiple of 8; qkv or a weight not 16-byte aligned; num_tokens * (H + Hkv) > 2^27.
+ * QS_ENOSUP: head_dim != 128.  num_tokens == 0: QS_OK, no launch.
+ * ---------------------------------------------------------------------------------------------------------- */
+int qs_qk_norm_rows(void* qkv, const void* q_weight, const void* k_weight, int num_tokens, int num_heads, int num_kv_heads, int head_dim,
+                    int64_t qkv_stride0, float eps, qs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -137,6 +137,7 @@ SIGNATURES = {
     "qs_pages_fork": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _vp]),
     "qs_beam_select": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "qs_rows_move": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp]),
+    "qs_qk_norm_rows": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i64, _f, _vp]),
 }
 
 

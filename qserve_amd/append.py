@@ -26,6 +26,9 @@ group; `shared_prefix_groups` builds the three device arrays that describe the g
 
 `past = 0` is the prefill pair (apply_bias_rope_update_kv_cache + flash_attn_varlen_func), `n = 1` is single_query_attention.
 
+`qk_norm_rows`: the per-head RMSNorm of the q and k heads (Qwen3), in place on the packed qkv rows, in front of ANY of the writers above
+and of the decode attentions - a launch of its own (csrc/qk_norm_rows.hip), because every one of them rotates inside its kernel.
+
 Tree-draft verification (several drafted candidates per position, verified in one pass): the n <= 64 new rows of a sequence are the
 nodes of a tree in topological order, `tree_mask` int64 [T] holds one 64-bit word per row (bit j of node i's word: "node i sees new
 token j of its own sequence"; `tree_masks_from_parents` builds ancestor-closed words):
@@ -78,6 +81,31 @@ def append_rope_update_kv_cache(qkv, cu_seqlens_q, past_lens, kv_pointers, num_h
         check(lib.qs_append_rope_update_kv_cache(ptr(qkv), ptr(cu_seqlens_q), ptr(past_lens), ptr(kv_pointers), qkv.size(0), batch,
                                                  kv_pointers.size(-1), int(num_heads), int(num_kv_heads), 64, int(size_per_token),
                                                  128, float(rope_theta), int(bool(int4_kv)), 1, stream()), what)
+
+
+def qk_norm_rows(qkv, q_weight, k_weight, num_heads, num_kv_heads, eps):
+    """Per-head RMSNorm of the q and k heads (Qwen3's q_norm / k_norm), IN PLACE on the packed fp16 `qkv` rows [T, >= (H + 2 Hkv) * 128]
+    (a padded row stride is accepted), BEFORE whatever rotates them: per 128-half head slice x, y = fp16(w * fp16(x / sqrt(mean(x^2) +
+    eps))) with `q_weight` for the H query heads and `k_weight` for the Hkv key heads, both fp16 [128].  The v heads and the padding are
+    not touched.  include/qserve_amd.h (qs_qk_norm_rows) has the rule; csrc/qk_norm_rows.hip the kernel.  Returns `qkv`."""
+    what = "append.qk_norm_rows"
+    expect(qkv, torch.float16, "qkv", contiguous=False)
+    expect(q_weight, torch.float16, "q_weight")
+    expect(k_weight, torch.float16, "k_weight")
+    H, Hkv = int(num_heads), int(num_kv_heads)
+    if H <= 0 or Hkv <= 0 or H % Hkv != 0:
+        raise RuntimeError(f"{what}: bad head counts H={H} Hkv={Hkv}")
+    if qkv.dim() != 2 or qkv.size(1) < (H + 2 * Hkv) * 128 or qkv.stride(1) != 1:
+        raise RuntimeError(f"{what}: qkv must be [tokens, >= (H + 2 Hkv) * 128] = [T, >= {(H + 2 * Hkv) * 128}] with contiguous rows, got "
+                           f"{tuple(qkv.shape)} with strides {tuple(qkv.stride())}")
+    if tuple(q_weight.shape) != (128,) or tuple(k_weight.shape) != (128,):
+        raise RuntimeError(f"{what}: q_weight and k_weight must be [128], got {tuple(q_weight.shape)} and {tuple(k_weight.shape)}")
+    if not float(eps) > 0.0:
+        raise RuntimeError(f"{what}: eps={eps} (must be > 0)")
+    with guard(qkv):
+        check(lib.qs_qk_norm_rows(ptr(qkv), ptr(q_weight), ptr(k_weight), qkv.size(0), H, Hkv, 128,
+                                  qkv.stride(0), float(eps), stream()), what)
+    return qkv
 
 
 def _window(window, what, **unsupported):

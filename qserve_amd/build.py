@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 BUILD = os.path.join(HERE, "_build")
 LIB = os.path.join(HERE, "libqserve_amd.so")
-SOURCES = ["lib.hip", "gemm_w4a8.hip", "gemm_w4a8_lds.hip", "gemm_w4a8_tiled.hip", "gemm_w4a8_wide.hip", "gemm_w4a8_ring.hip", "gemm_w8a8.hip", "attention.hip", "attention_mfma.hip", "attention_mfma8.hip", "attention_long.hip", "attention_window.hip", "flash_prefill.hip", "append_attention.hip", "append_window.hip", "append_attention_split.hip", "append_tree.hip", "tree_accept.hip", "sample_rows.hip", "penalize_rows.hip", "ngram_draft.hip", "stop_update.hip", "page_pool.hip", "logprob_rows.hip", "score_rows.hip", "constrain_rows.hip", "lora_rows.hip", "lora_prompt.hip", "moe_route.hip", "gemm_w4a8_moe.hip", "gemm_w4a8_moe_tiled.hip", "append_shared.hip", "beam_select.hip", "fused_small.hip", "direct_allreduce.hip"]
+SOURCES = ["lib.hip", "gemm_w4a8.hip", "gemm_w4a8_lds.hip", "gemm_w4a8_tiled.hip", "gemm_w4a8_wide.hip", "gemm_w4a8_ring.hip", "gemm_w8a8.hip", "attention.hip", "attention_mfma.hip", "attention_mfma8.hip", "attention_long.hip", "attention_window.hip", "flash_prefill.hip", "append_attention.hip", "append_window.hip", "append_attention_split.hip", "append_tree.hip", "tree_accept.hip", "sample_rows.hip", "penalize_rows.hip", "ngram_draft.hip", "stop_update.hip", "page_pool.hip", "logprob_rows.hip", "score_rows.hip", "constrain_rows.hip", "lora_rows.hip", "lora_prompt.hip", "moe_route.hip", "gemm_w4a8_moe.hip", "gemm_w4a8_moe_tiled.hip", "append_shared.hip", "beam_select.hip", "qk_norm_rows.hip", "fused_small.hip", "direct_allreduce.hip"]
 ARCH = "gfx950"
 # per-source flags: the grouped MoE tile and the LoRA prompt form are compiled without packed fp32 VALU forms (their float32 steps are
 # scalar, op by op).  lora_rows.hip holds the rows and the grouped form in one unit, so one setting serves both: the default one, WITH

@@ -91,6 +91,10 @@ TINY_MOE = dict(TINY, name="tiny-moe", experts=4, experts_per_token=2)
 # sliding-window attention: `sliding_window` = W, the token at position p attends to positions p - W + 1 .. p (Mistral-7B-v0.1)
 MISTRAL_7B = dict(name="Mistral-7B", hidden=4096, heads=32, kv_heads=8, inter=14336, layers=32, vocab=32000, rope_theta=1e4, eps=1e-5,
                   sliding_window=4096)
+# per-head Q/K RMSNorm: `qk_norm` = True, every query and key head is normalised over its 128 dimensions between the qkv projection and the
+# rotation (Qwen3's self_attn.q_norm / k_norm; `qk_norm_eps` defaults to `eps`).  No qkv bias, a plain rotary base, SwiGLU: the rest is Llama's
+QWEN3_8B = dict(name="Qwen3-8B", hidden=4096, heads=32, kv_heads=8, inter=12288, layers=36, vocab=151936, rope_theta=1e6, eps=1e-6,
+                qk_norm=True)
 
 
 class W4A8Linear:
@@ -218,6 +222,16 @@ class DecodeEngine:
                 "DecodeEngine: a mixture-of-experts config runs on one GPU - neither expert nor tensor parallelism of the experts is built"
             assert 1 <= self.moe[1] <= min(self.moe[0], moemod.MAX_TOP_K) and self.moe[0] <= moemod.MAX_EXPERTS, \
                 f"DecodeEngine: experts={self.moe[0]} (<= {moemod.MAX_EXPERTS}), experts_per_token={self.moe[1]} (1 .. min(experts, {moemod.MAX_TOP_K}))"
+        # per-head Q/K RMSNorm (cfg["qk_norm"], Qwen3): every layer owns fp16 `q_norm` / `k_norm` [128], and ONE append.qk_norm_rows runs on
+        # the layer's qkv rows in _layer_stack, behind the qkv GEMM (and its LoRA delta) and in front of the writer / decode attention of
+        # every path.  Absent or False: the engine launches exactly what it always did and draws exactly the weights it always drew.
+        # Under tensor parallelism every rank normalises its own heads with the full 128-entry weights.
+        self.qk_norm = bool(cfg.get("qk_norm"))
+        self.qk_norm_eps = float(cfg.get("qk_norm_eps", cfg["eps"]))
+        assert not (self.qk_norm and self.moe is not None), \
+            "DecodeEngine: qk_norm on a mixture-of-experts config is refused - Qwen3-MoE (128 experts, 8 per token) is beyond what the " \
+            "expert kernels take, and no other mixture-of-experts family normalises q and k"
+        assert not self.qk_norm or self.qk_norm_eps > 0.0, f"DecodeEngine: qk_norm_eps={self.qk_norm_eps} (must be > 0)"
         # fuse_pairs: issue (residual add + layer norm) and (silu_and_mul + quant) as one launch each
         # (qserve_amd/fused.py: bit-identical to the op pairs; False = the reference's exact op-by-op sequence)
         self.fuse_pairs = fuse_pairs
@@ -276,6 +290,22 @@ class DecodeEngine:
             self.norm_w = weights["norm"].to(self.dev)
             if with_lm_head:
                 self.embed, self.lm_head = weights["embed"].to(self.dev), weights["lm_head"].to(self.dev)
+        if self.qk_norm and weights is None:
+            # a generator of their own, so that no other weight of the engine moves - and one that does not depend on the rank: the two
+            # vectors are per head DIMENSION, every tensor-parallel rank holds the same ones
+            qk_gen = torch.Generator(device=self.dev).manual_seed(seed + 7919)
+            for L in self.layers:
+                L.update(q_norm=(torch.rand((128,), device=self.dev, generator=qk_gen) + 0.5).half(),
+                         k_norm=(torch.rand((128,), device=self.dev, generator=qk_gen) + 0.5).half())
+        elif weights is not None:
+            for li, (L, Lw) in enumerate(zip(self.layers, weights["layers"])):
+                have = [n for n in ("q_norm", "k_norm") if Lw.get(n) is not None]
+                assert len(have) == (2 if self.qk_norm else 0), \
+                    f"DecodeEngine: layer {li} of the weights has {have or 'neither q_norm nor k_norm'} and the config says " \
+                    f"qk_norm={self.qk_norm} - a Qwen3 checkpoint needs qk_norm=True, and qk_norm=True needs both tensors"
+                for n in have:
+                    L[n] = Lw[n].to(self.dev).half().contiguous()
+                    assert tuple(L[n].shape) == (128,), f"DecodeEngine: layer {li} {n} is {tuple(L[n].shape)}, not [128]"
         # ---- paged KV pools (cache_engine.py:59-115) and pointer tables (model_runner.py:396-414)
         self.max_len = prompt_len + max_new
         self.mb = (self.max_len + 63) // 64 + 1            # README.md:369 page budget rule (+1 page)
@@ -723,6 +753,7 @@ class DecodeEngine:
         # set_lora: lora_rows behind every base GEMM (and its bias), on that GEMM's quantised input.  A linear with an adapter takes the
         # path a linear with a bias takes: no planes form, no silu * mul epilogue - the delta has to be added in between
         lora = self._lora_plan(h.size(0), lora_ids) if self._lora else None
+        from . import append as appendmod
 
         def lora_add(li, name, out, xq):
             if lora is not None:
@@ -771,6 +802,8 @@ class DecodeEngine:
                 norm_quant(h, L["ln1"])
             L["qkv"](qa, q_scale, q_sum, qkv)
             lora_add(li, "qkv", qkv, qa)
+            if self.qk_norm:                                         # Qwen3: per-head RMSNorm of q and k, in front of every rotation
+                appendmod.qk_norm_rows(qkv, L["q_norm"], L["k_norm"], self.H, self.Hkv, self.qk_norm_eps)
             attention(li, qkv)
             if self.moe is not None:
                 # the sparse MLP (mixtral_w4a8_unpad.py:279-374): the router reads the UN-quantised normed rows, the experts the quantised

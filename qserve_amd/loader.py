@@ -112,7 +112,8 @@ def load_llama_w4a8(state, cfg, group_size=-1, tp_rank=0, tp_world=1, load_norm_
     """state: {name: tensor} in the reference checkpoint naming (or an iterable of pairs, e.g. iterate_checkpoint(dir)).
     cfg: dict with hidden, heads, kv_heads, inter, layers (qserve_amd.decode configs).
     Returns {"layers": [{"qkv","o","gate_up","down": {tensor dicts}, "ln1","ln2"}], "norm", "embed", "lm_head"} for this
-    rank.  `load_norm_weights=False` mirrors the reference (`if "norm" in name: continue`): norms stay ones."""
+    rank.  `load_norm_weights=False` mirrors the reference (`if "norm" in name: continue`): norms stay ones.  With cfg["qk_norm"]
+    (Qwen3) every layer also carries "q_norm" and "k_norm" fp16 [128] from `self_attn.{q,k}_norm.weight`."""
     if not isinstance(state, dict):
         state = dict(state)
     H, Hkv, hid = cfg["heads"], cfg["kv_heads"], cfg["hidden"]
@@ -143,6 +144,18 @@ def load_llama_w4a8(state, cfg, group_size=-1, tp_rank=0, tp_world=1, load_norm_
         layers.append(dict(qkv=dev(qkv), o=dev(o), gate_up=dev(gate_up), down=dev(down),
                            ln1=ln1.to(device) if device is not None else ln1,
                            ln2=ln2.to(device) if device is not None else ln2))
+        # Qwen3's per-head q_norm / k_norm [128]: learned, applied per head DIMENSION, so every rank takes the whole vectors.  They are
+        # always loaded (`load_norm_weights` is about the layer norms the reference leaves at one; these have no such default), and a
+        # checkpoint and a config that disagree about them are an error, either way round.
+        qk = {n: state.get(p + f"self_attn.{n}.weight") for n in ("q_norm", "k_norm")}
+        have = [n for n, t in qk.items() if t is not None]
+        if len(have) != (2 if cfg.get("qk_norm") else 0):
+            raise RuntimeError(f"load_llama_w4a8: layer {li} of the checkpoint has {have or 'neither q_norm nor k_norm'} and the config says "
+                               f"qk_norm={bool(cfg.get('qk_norm'))} - a Qwen3 checkpoint needs qk_norm=True, and qk_norm=True needs both tensors")
+        for n in have:
+            if tuple(qk[n].shape) != (hd,):
+                raise RuntimeError(f"load_llama_w4a8: {p}self_attn.{n}.weight is {tuple(qk[n].shape)}, not [{hd}]")
+            layers[-1][n] = dev({n: qk[n].half()})[n]
     out = dict(layers=layers)
     norm = state["model.norm.weight"].half() if load_norm_weights and "model.norm.weight" in state else ones()
     for name, key, t in (("norm", None, norm), ("embed", "model.embed_tokens.weight", None), ("lm_head", "lm_head.weight", None)):
